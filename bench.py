@@ -22,7 +22,19 @@ the PnP stage consumes seeded synthetic keypoints (landmarks projected through r
 1 px noise, 10 % outliers) of the same shape; the decode stage still runs on the network's
 heatmaps inside the timed region.  Nothing is skipped or cached between steps.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+A plain run (no --full) sets up, warms up, times the K steps, writes the last timed step's outputs when --dump-outputs DIR
+is given, and prints the line: `ms_per_step` is the wall time of the K timed steps / K.  Everything else the line can carry
+(roofline pass, device clock / power sampler, CPU-oracle baseline, post-run chain check) runs only with --full; in a plain run
+those fields are null.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed, as .npy files --
+  keypoints.npy    float32 (B, 11, 3)  rank 0's decoded key points [x, y, maxval] (what the forward + decode returned)
+  rotation.npy     float64 (N, 3, 3)   R of every frame of the step (N = ranks x B, rank 0's host rows)
+  translation.npy  float64 (N, 3)      t
+  status.npy       float64 (N,)        inlier count (0 = no pose)
+The inputs are seeded, so two builds run with the same arguments can be compared file for file (64 MB at most in all).
+
+Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects (--full only):
   roofline      dominant kernel class (largest summed time), from HIP events recorded around every
                 launch (scpose_hrnet_forward_profiled, on the launch stream) of PROF_STEPS extra steps that run
                 right after the timed region -- the K timed steps themselves carry no per-launch events, only
@@ -78,7 +90,12 @@ def parse():
     ap.add_argument("--model", default="w48", choices=["w48", "w32"])
     ap.add_argument("--image", type=int, default=None)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16"])
-    ap.add_argument("--cpu-frames", type=int, default=32, help="frames of the CPU-oracle baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the roofline pass, the CPU-oracle baseline and the post-run chain check, and sample "
+                         "the device clock / power during the timed region (a plain run does none of these; their fields are null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (key points, R, t, status) as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--cpu-frames", type=int, default=32, help="frames of the CPU-oracle baseline sample (0 = skip; --full only)")
     ap.add_argument("--events", action="store_true",
                     help="BASELINE configs[4] side line: HRNet-W32 256x256, f16 MFMA kernels, mixed RGB + event-frame batch")
     ap.add_argument("--graph", type=int, default=-1,
@@ -108,11 +125,30 @@ def parse():
     ap.add_argument("--pipeline-batch", type=int, default=16, help="the loader's batch (TEST.BATCH_SIZE_PER_GPU; 16 in the reference's shipped events-config.yaml:74)")
     ap.add_argument("--pipeline-workers", type=int, default=max(1, min(32, (os.cpu_count() or 1) // 4)), help="loader workers (default: what the CLI picks, parallel.auto_workers)")
     ap.add_argument("--no-chain-check", action="store_true",
-                    help="skip the post-run key-point / pose check on the 64 W48 fixture frames (about 15 s: the constructed checkpoint is rebuilt from its seed)")
+                    help="skip the post-run key-point / pose check on the 64 W48 fixture frames (about 15 s: the constructed checkpoint is rebuilt from its seed; "
+                         "--full only)")
     ap.add_argument("--cpu-stub", action="store_true",
                     help="(tests only) run the multi-rank step loop on CPU tensors over gloo with a stand-in engine: exercises the sharding, "
                          "gather, timing and printing code, measures nothing")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """arrays: name -> float32 / float64 ndarray; writes path/<name>.npy.  A step's outputs are 236 bytes per frame, so the limit
+    would take ~280 000 frames per step, far beyond what one device holds at these geometries."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py --dump-outputs: %d bytes of outputs, over the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def cpu_baseline(cfg, sd, image, nframes, kp_sample):
@@ -441,6 +477,7 @@ def main():
         graphs = None
     done = [None, None]
     counter = [0]
+    last_kp = [None]    # the decoded key points of the latest step (--dump-outputs)
 
     prof_ms = {}
     fwd_events = []     # (start, end) events around the forward of every timed step (two records per step, no per-launch events)
@@ -476,6 +513,7 @@ def main():
             side.wait_event(fwd_done)
             if kp is None:
                 kp = ops.decode(heat[k], center, scale, True)
+            last_kp[0] = kp
             ops.pnp_epnp_ransac(kp if args.chained else kp_syn, lm, Kc, dc, rows=block[k])   # the kernel writes [R, t, status] rows itself
             if world > 1:
                 dist.all_gather_into_tensor(gathered[k], block[k])
@@ -506,7 +544,7 @@ def main():
     for _ in range(args.warmup):
         step(False)
     barrier()
-    sampler = DeviceSampler(local_rank, pci_address(local_rank)) if (rank == 0 and not stub) else None
+    sampler = DeviceSampler(local_rank, pci_address(local_rank)) if (rank == 0 and not stub and args.full) else None
     if sampler:
         sampler.start()
     t0 = time.perf_counter()
@@ -516,6 +554,13 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     device_state = sampler.stop() if sampler else None
+    if rank == 0:
+        # the last timed step's results, before anything else runs (the roofline steps of --full refill the same host buffers)
+        host = host.clone()
+        if args.dump_outputs:
+            rows = host.numpy()
+            dump_outputs(args.dump_outputs, {"keypoints": last_kp[0].float().cpu().numpy(), "rotation": rows[:, 0:9].reshape(-1, 3, 3),
+                                             "translation": rows[:, 9:12], "status": rows[:, 12]})
     elapsed_own = elapsed
     rccl = None
     if world > 1:
@@ -540,12 +585,13 @@ def main():
     fwd_unprofiled_ms = sum(a.elapsed_time(b) for a, b in fwd_events) / max(len(fwd_events), 1)
     # Roofline pass, AFTER the timed region: per-launch HIP events cost ~2.5 ms per forward (~280 records
     # that break back-to-back dispatch), so the steps that carry them are not part of `value`; the same pipelined step
-    # (decode / PnP of the previous step beside the forward) runs PROF_STEPS more times on the same resident inputs.
+    # (decode / PnP of the previous step beside the forward) runs PROF_STEPS more times on the same resident inputs.  --full only.
     prof_steps = 0
-    for i in range(PROF_STEPS):     # every rank: the step contains the all-gather
-        step(True)
-        prof_steps += 1
-    barrier()
+    if args.full:
+        for i in range(PROF_STEPS):     # every rank: the step contains the all-gather
+            step(True)
+            prof_steps += 1
+        barrier()
 
     if rank == 0:
         ok = int((host[:, 12] > 0).sum().item())
@@ -553,9 +599,9 @@ def main():
         # ---- roofline of the dominant kernel class (largest summed time over the profiled steps) ----
         ridge = MFMA_PEAK_TFLOPS * 1e12 / (HBM_PEAK_GBS * 1e9)     # flop per byte above which the MFMA peak binds
         total_ms = sum(v[0] for v in prof_ms.values())
-        sha = source_hash()
+        sha = source_hash() if args.full else None
         try:
-            traffic_db = json.load(open(os.path.join(ROOT, "profiles", "roofline_traffic.json")))
+            traffic_db = json.load(open(os.path.join(ROOT, "profiles", "roofline_traffic.json"))) if args.full else {}
         except (OSError, ValueError):
             traffic_db = {}
 
@@ -608,16 +654,19 @@ def main():
         launches_per_fwd = sum(v[1] for v in prof_ms.values()) / max(prof_steps, 1)
         gap_us = max(0.0, (total_ms / max(prof_steps, 1) - fwd_unprofiled_ms) * 1e3 / max(launches_per_fwd, 1))
         ranked = sorted(prof_ms.items(), key=lambda kv: -kv[1][0])
-        roof = describe(ranked[0][0], *ranked[0][1])
-        roof["profiled_steps"] = prof_steps
-        roof["dispatch_gap_us_per_launch"] = round(gap_us, 2)
-        roof["src_sha"] = sha
-        # the next kernel classes by share of the forward, each against its own roofline (same definitions);
-        # class = kind:10*ksize+stride|nterms:Cin:Cout (kind 0 stem, 1 conv, 2 fuse sum, 3 fused BasicBlock, 4 head gather, 5 fused stem, 6 fused Bottleneck, 7 fused tail, 8 fuse row 0 + down hops of branch 0, 9 branch chain (all BasicBlocks of a branch); '@pixels' where a layer shape runs at two map sizes)
-        roof["next_classes"] = [{k: v for k, v in describe(k2, *v2).items()
-                                 if k in ("class", "share_of_forward", "avg_launch_us", "avg_launch_us_gap_corrected", "bound", "achieved", "unit", "frac", "frac_gap_corrected", "frac_of_sustained", "traffic")}
-                                for k2, v2 in ranked[1:6]]
-        fwd_ms = sum(v[0] for v in prof_ms.values()) / max(prof_steps, 1)   # sum of per-launch event intervals (event overhead included)
+        roof = None
+        fwd_ms = None
+        if prof_steps:
+            roof = describe(ranked[0][0], *ranked[0][1])
+            roof["profiled_steps"] = prof_steps
+            roof["dispatch_gap_us_per_launch"] = round(gap_us, 2)
+            roof["src_sha"] = sha
+            # the next kernel classes by share of the forward, each against its own roofline (same definitions);
+            # class = kind:10*ksize+stride|nterms:Cin:Cout (kind 0 stem, 1 conv, 2 fuse sum, 3 fused BasicBlock, 4 head gather, 5 fused stem, 6 fused Bottleneck, 7 fused tail, 8 fuse row 0 + down hops of branch 0, 9 branch chain (all BasicBlocks of a branch); '@pixels' where a layer shape runs at two map sizes)
+            roof["next_classes"] = [{k: v for k, v in describe(k2, *v2).items()
+                                     if k in ("class", "share_of_forward", "avg_launch_us", "avg_launch_us_gap_corrected", "bound", "achieved", "unit", "frac", "frac_gap_corrected", "frac_of_sustained", "traffic")}
+                                    for k2, v2 in ranked[1:6]]
+            fwd_ms = round(sum(v[0] for v in prof_ms.values()) / prof_steps, 3)   # sum of per-launch event intervals (event overhead included)
         cpu = None
         stub_check = None
         if stub:   # every rank's block must sit at its place in rank 0's host buffer, in frame order, with that rank's own frames behind it
@@ -628,7 +677,7 @@ def main():
                 want = fr.reshape(B, -1).float().mean(1).double().numpy()
                 blk = hb[r * B:(r + 1) * B]
                 stub_check = stub_check and bool((blk[:, 0] == r).all() and (blk[:, 1] == np.arange(B)).all() and np.array_equal(blk[:, 2], want))
-        if world == 1 and args.cpu_frames > 0 and not stub:
+        if args.full and world == 1 and args.cpu_frames > 0 and not stub:
             cpu = cpu_baseline(cfg, sd, image, args.cpu_frames, kp_np)
         st = eng.stats(image, image)
         periods = [] if stub else [a.elapsed_time(b) for a, b in zip(step_end_events[:-1], step_end_events[1:])]
@@ -656,7 +705,7 @@ def main():
                             "note": "landmarks are drawn up to one crop pixel (side / 128 frame px) from their projection (synthetic.landmark_frames)"}
         # (N = 1 only: it is a property of one device's kernels, and the other ranks of a multi-GPU run should not wait ~15 s at the process
         # group's tear-down while rank 0 rebuilds the constructed checkpoint)
-        if chain_report is None and world == 1 and not stub and not args.events and args.model == "w48" and args.dtype in ("bf16", "f16") and not args.no_chain_check:
+        if args.full and chain_report is None and world == 1 and not stub and not args.events and args.model == "w48" and args.dtype in ("bf16", "f16") and not args.no_chain_check:
             chain_report = chain_check(ops, syn, dev, args.dtype)
         line = {
             "metric": "STUB: multi-rank step loop on CPU tensors over gloo, nothing is computed or measured (--cpu-stub)" if stub else
@@ -677,12 +726,13 @@ def main():
                        "decode": "inside the network's last kernel (scpose_hrnet_forward_decode: last fuse sum + final_layer + arg-max / quarter-pixel / back-transform, no heat-map written)" if fused
                                  else "scpose_decode on the heat-maps, on the side stream",
                        "roofline_pass": "%d eager steps with per-launch HIP events, after the timed region; same launch list as the timed forward (%s)" % (
-                           prof_steps, "fused tail with the decode inside" if fused else "forward, then scpose_decode on the side stream"),
+                           prof_steps, "fused tail with the decode inside" if fused else "forward, then scpose_decode on the side stream") if prof_steps
+                                        else "not run (--full runs it)",
                        "decoded_keypoints": "fed to PnP" if args.chained else "computed every step and left on the device: PnP consumes the synthetic key points (SURVEY 8d: random-init heat-maps carry no pose)",
                        "launches_per_forward": st["launches"], "gflop_per_frame": round(st["flops_per_frame"] / 1e9, 3),
                        "act_mbytes_per_frame": round(st["act_bytes_per_frame"] / 1e6, 2)},
             "hrnet_forward_ms": round(fwd_unprofiled_ms, 3),          # un-instrumented forwards of the timed steps (two events per step)
-            "hrnet_forward_ms_sum_of_profiled_launches": round(fwd_ms, 3),
+            "hrnet_forward_ms_sum_of_profiled_launches": fwd_ms,
             "hrnet_tflops": round(st["flops_per_frame"] * B / (fwd_unprofiled_ms / 1e3) / 1e12, 2),
             "poses_ok": ok, "poses_total": world * B,
             "step_ms": step_ms,

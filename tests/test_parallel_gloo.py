@@ -102,7 +102,7 @@ def test_bench_step_loop_two_ranks_over_gloo(capfd):
     multi-GPU run is not the first execution of that code.  Both launch modes: `bench.py --gpus 2` starting its
     ranks itself (parallel.spawn_local_ranks, file-store rendezvous) and the driver's torch.distributed.run."""
     import subprocess
-    args = ["--cpu-stub", "--gpus", "2", "--image", "32", "--batch", "16", "--steps", "4", "--warmup", "2"]
+    args = ["--cpu-stub", "--full", "--gpus", "2", "--image", "32", "--batch", "16", "--steps", "4", "--warmup", "2"]   # --full: the roofline pass
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "SCPOSE_RDZV_FILE")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=300, env=env, cwd="/tmp")
     assert r.returncode == 0, r.stderr[-2000:]
@@ -121,3 +121,30 @@ def test_bench_step_loop_two_ranks_over_gloo(capfd):
     assert r.returncode == 0, r.stderr[-2000:]
     line = _stub_line(r.stdout)
     assert line["n_gpus"] == 2 and line["stub_check"] is True and line["poses_ok"] == 32
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps, runs none of the --full extras, and --dump-outputs writes the
+    last timed step's outputs as float32 / float64 .npy files that are identical from run to run (one rank, `--cpu-stub`)."""
+    import subprocess
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "SCPOSE_RDZV_FILE")}
+    got = []
+    for run in range(2):
+        out = tmp_path / ("out%d" % run)
+        args = ["--cpu-stub", "--gpus", "1", "--image", "32", "--batch", "8", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)]
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=300, env=env, cwd="/tmp")
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = _stub_line(r.stdout)
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["poses_total"] == 8
+        assert line["roofline"] is None and line["cpu_baseline"] is None and line["chain"] is None and line["device_state"] is None
+        files = sorted(os.listdir(out))
+        assert files == ["keypoints.npy", "rotation.npy", "status.npy", "translation.npy"]
+        arrs = {f[:-4]: np.load(out / f) for f in files}
+        assert arrs["keypoints"].dtype == np.float32 and arrs["keypoints"].shape == (8, 11, 3)
+        assert all(arrs[k].dtype == np.float64 for k in ("rotation", "translation", "status"))
+        assert arrs["rotation"].shape == (8, 3, 3) and arrs["translation"].shape == (8, 3) and arrs["status"].shape == (8,)
+        assert (arrs["status"] == 11).all()      # the stand-in PnP's status column: the dump holds the step's rows
+        got.append(arrs)
+    assert all(np.array_equal(got[0][k], got[1][k]) for k in got[0])
+

@@ -5,7 +5,7 @@ out=${1:-gpurun_out/sweep}; shift
 batches=${@:-"32 64 128 256 512"}
 mkdir -p "$out"
 for b in $batches; do
-  python3 bench.py --batch "$b" --steps 12 --warmup 4 --cpu-frames 0 > "$out/bench_b$b.json" 2> "$out/bench_b$b.err" || echo "batch $b failed" >&2
+  python3 bench.py --full --batch "$b" --steps 12 --warmup 4 --cpu-frames 0 > "$out/bench_b$b.json" 2> "$out/bench_b$b.err" || echo "batch $b failed" >&2
 done
 python3 - "$out" $batches <<'PY'
 import json, sys

@@ -14,7 +14,7 @@ cd /tmp && export TMPDIR=/tmp
 W=2; K=4
 run_passes() {   # <name> <passes> <bench args...>
   name=$1; passes=$2; shift 2
-  B="python3 $root/bench.py --steps $K --warmup $W --cpu-frames 0 --no-chain-check $*"   # (no post-run chain check under the profiler: its 64-frame forward would be attributed to the headline classes)
+  B="python3 $root/bench.py --full --steps $K --warmup $W --cpu-frames 0 --no-chain-check $*"   # (no post-run chain check under the profiler: its 64-frame forward would be attributed to the headline classes)
   d=$out/$name; mkdir -p $d
   rocprofv3 --kernel-trace -d $d/trace -o t --output-format csv -- $B > $d/bench_under_trace.json 2> $d/trace.err
   for p in $passes; do
@@ -44,8 +44,8 @@ python3 tools_dev/condense_prof.py $out/w48_b256 w48 256 bf16 $W > $out/condense
 python3 tools_dev/condense_prof.py $out/w32_b64 w32 64 bf16 $W >> $out/condense.log 2>&1
 python3 tools_dev/condense_prof.py $out/events_b64 w32 64 f16 $W >> $out/condense.log 2>&1
 # the un-profiled lines
-python3 bench.py > $out/bench.json 2> $out/bench.err
-python3 bench.py --events --batch 64 --cpu-frames 0 > $out/bench_events.json 2>/dev/null
-python3 bench.py --model w32 --batch 64 --cpu-frames 0 > $out/bench_w32_b64.json 2>/dev/null
+python3 bench.py --full > $out/bench.json 2> $out/bench.err
+python3 bench.py --full --events --batch 64 --cpu-frames 0 > $out/bench_events.json 2>/dev/null
+python3 bench.py --full --model w32 --batch 64 --cpu-frames 0 > $out/bench_w32_b64.json 2>/dev/null
 find $out -name "*.csv" -size +1M -delete
 tail -3 $out/condense.log; ls $out

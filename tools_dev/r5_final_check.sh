@@ -5,5 +5,5 @@ out=$root/gpurun_out/${1:-r5_final_check}; mkdir -p $out
 timeout 2400 python -m pytest tests -m gpu -x -q > $out/tests_gpu.txt 2>&1; tail -3 $out/tests_gpu.txt
 python -m pytest tests/test_gpu_chain.py -m gpu -q -s 2>&1 | grep -E "W48 384|max \|HIP" | tee $out/chain_px.txt
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee $out/smoke.txt
-python bench.py > $out/bench.json 2> $out/bench.err; python -c "
+python bench.py --full > $out/bench.json 2> $out/bench.err; python -c "
 import json; d=json.load(open('$out/bench.json')); print(d['value'], d['ms_per_step'], d['hrnet_forward_ms'], d['roofline']['class'], d['roofline']['frac'], d['roofline']['traffic'], d['cpu_baseline']['value'])"

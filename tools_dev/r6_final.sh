@@ -6,7 +6,7 @@ out=$root/gpurun_out/${1:-r6_final}; mkdir -p $out
 timeout 2400 python -m pytest tests -m gpu -x -q > $out/tests_gpu.txt 2>&1; tail -3 $out/tests_gpu.txt
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee $out/smoke.txt
 bash tools_dev/profile_round.sh round6_final > $out/profile_round.log 2>&1; tail -2 $out/profile_round.log
-python bench.py > $out/bench.json 2> $out/bench.err; python -c "
+python bench.py --full > $out/bench.json 2> $out/bench.err; python -c "
 import json; d=json.load(open('$out/bench.json')); print(d['value'], d['ms_per_step'], d['hrnet_forward_ms'], d['roofline']['class'], d['roofline']['frac'], d['roofline']['traffic'], d['cpu_baseline']['value'], d['chain']['kp_px_max'], d['device_state'])"
 for b in 16 256; do
   python bench.py --pipeline --pipeline-frames 8192 --pipeline-batch $b > $out/pipeline_8192_b$b.json 2> $out/pipeline.err

@@ -15,7 +15,7 @@ for round in 1 2 3; do
 done
 for v in "SCPOSE_X=0" "SCPOSE_DEV=1 SCPOSE_LIB=$lib SCPOSE_CHAIN=0"; do
   for b in 16 256; do
-    o=$(env $v python bench.py --model w32 --batch $b --cpu-frames 0 --steps 20 --graph 0 2>>$out/bench_err.txt | python -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print(d['value'], d['ms_per_step'], d['hrnet_forward_ms'], [(c['class'], c['avg_launch_us'], c['share_of_forward']) for c in [r]+r['next_classes']][:6])")
+    o=$(env $v python bench.py --full --model w32 --batch $b --cpu-frames 0 --steps 20 --graph 0 2>>$out/bench_err.txt | python -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print(d['value'], d['ms_per_step'], d['hrnet_forward_ms'], [(c['class'], c['avg_launch_us'], c['share_of_forward']) for c in [r]+r['next_classes']][:6])")
     echo "[w32 b$b eager ${v##*libscpose_hip.so}] $o" | tee -a $out/bench_ab.txt
   done
 done
