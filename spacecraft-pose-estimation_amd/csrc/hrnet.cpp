@@ -16,6 +16,7 @@
 #include <stdarg.h>
 #include <new>
 
+#include <algorithm>
 #include <map>
 #include <string>
 #include <vector>
@@ -161,9 +162,22 @@ struct Builder {
   void parallel_begin(int kind) { ++epoch; serial = false; lane = 0; par_kind = kind; }   // the ops pushed until parallel_end() share one epoch
   void parallel_end() { serial = true; lane = 0; }
 
-  int new_tensor(int C, int ds) {
+  // Every tensor an op writes is named where it is created (scpose_hrnet_forward_tap): the reference module path that produces
+  // it -- "layer1.<b>", "transition<k>.<i>[.<j>]", "stage<S>.<M>.branches.<B>.<K>[.conv1|.conv2]", "stage<S>.<M>.fuse_layers.<i>.<j>[.<k>]",
+  // "stage<S>.<M>.out<i>", "<head>.tapmap".  Only the f32 levels of the hrnet_cms pyramid (OP_HEAD) stay unnamed.
+  int new_tensor(int C, int ds, const std::string& name) {
     net->tensors.push_back(TensorDesc{C, ds, -1});
-    return (int)net->tensors.size() - 1;
+    const int t = (int)net->tensors.size() - 1;
+    if (!name.empty()) net->taps.emplace_back(name, t);
+    return t;
+  }
+  void rename_tap(int t, const std::string& name) { for (auto& tp : net->taps) if (tp.second == t) tp.first = name; }
+  void drop_tap(int t) {
+    for (size_t i = 0; i < net->taps.size(); ++i) if (net->taps[i].second == t) { net->taps.erase(net->taps.begin() + i); --i; }
+  }
+  // a convolution's output is named after its module: "<x>.0" (a Sequential(conv, bn)) -> "<x>", "<x>.convK" -> itself
+  static std::string tensor_name(const std::string& cname) {
+    return cname.size() > 2 && cname.compare(cname.size() - 2, 2, ".0") == 0 ? cname.substr(0, cname.size() - 2) : cname;
   }
   // y = [relu](conv_bn(x) [+ res]);  returns output tensor id (or -2 for heatmaps)
   int conv(int x, const std::string& cname, const std::string& bname, int cout, int ks, int stride,
@@ -180,7 +194,7 @@ struct Builder {
     Op op{};
     op.kind = OP_CONV; op.in = x; op.res = res; op.conv = (int)net->convs.size() - 1;
     op.relu = relu; op.out_f32 = to_heatmaps;
-    op.out = to_heatmaps ? -2 : new_tensor(cout, ds);
+    op.out = to_heatmaps ? -2 : new_tensor(cout, ds, tensor_name(cname));
     push(op);
     return op.out;
   }
@@ -190,7 +204,7 @@ struct Builder {
   // never written or read.  (The sum is formed in the fp32 accumulators, i.e. without the 16-bit rounding the
   // stored residual would get.)
   int conv_cat(int xa, const std::string& ca, const std::string& bna, int xb, const std::string& cb,
-               const std::string& bnb, int cout, bool relu) {
+               const std::string& bnb, int cout, bool relu, const std::string& name) {
     if (status != SCPOSE_OK) return -1;
     const int c1 = net->tensors[xa].C, c2 = net->tensors[xb].C;
     std::vector<float> w1, b1, w2, b2;
@@ -211,7 +225,7 @@ struct Builder {
     Op op{};
     op.kind = OP_CONV; op.in = xa; op.in2 = xb + 1; op.res = -1; op.conv = (int)net->convs.size() - 1;
     op.relu = relu; op.out_f32 = 0;
-    op.out = new_tensor(cout, net->tensors[xa].ds);
+    op.out = new_tensor(cout, net->tensors[xa].ds, name);
     push(op);
     return op.out;
   }
@@ -240,7 +254,7 @@ struct Builder {
     if (status != SCPOSE_OK) { set_error("hrnet_create: uploading the fused Bottleneck weights failed"); return -1; }
     Op op{};
     op.kind = OP_BNECK; op.in = x; op.res = -1; op.conv = (int)net->bnecks.size() - 1; op.relu = 1;
-    op.out = new_tensor(256, net->tensors[x].ds);
+    op.out = new_tensor(256, net->tensors[x].ds, p);
     push(op);
     return op.out;
   }
@@ -252,7 +266,9 @@ struct Builder {
     if (planes == 64 && net->tensors[x].C == 256 && bottleneck_fusable(256, 64, 256) && !(bn_env && atoi(bn_env) == 0)) return bottleneck(x, p);
     int y = conv(x, p + ".conv1", p + ".bn1", planes, 1, 1, true);
     y = conv(y, p + ".conv2", p + ".bn2", planes, 3, 1, true);
-    return conv(y, p + ".conv3", p + ".bn3", 4 * planes, 1, 1, true, x);
+    y = conv(y, p + ".conv3", p + ".bn3", 4 * planes, 1, 1, true, x);
+    if (y >= 0) rename_tap(y, p);
+    return y;
   }
   // BasicBlock relu(conv2(relu(conv1(x))) + x): one fused launch when the pair qualifies, else two convolutions
   int basic_block(int x, const std::string& p, int C) {
@@ -260,10 +276,12 @@ struct Builder {
     const size_t first = net->convs.size(), first_op = net->ops.size();
     const int u = conv(x, p + ".conv1", p + ".bn1", C, 3, 1, true);
     const int t = conv(u, p + ".conv2", p + ".bn2", C, 3, 1, true, x);
+    if (t >= 0) rename_tap(t, p);   // the block's output; "<p>.conv1" stays while the two convolutions are separate launches
     if (status != SCPOSE_OK || net->tensors[x].C != C) return t;
     if (!block_fusable(net->convs[first], net->convs[first + 1])) return t;
-    // replace the two ops by one; the intermediate tensor u stays unused (never planned: last_use < 0)
+    // replace the two ops by one; the intermediate tensor u stays unused (never planned: last_use < 0) and is no tap
     net->ops.resize(first_op);
+    drop_tap(u);
     if (serial) epoch -= 2;   // the two replaced ops' epochs
     Op op{};
     op.kind = OP_BLOCK; op.in = x; op.res = -1; op.conv = (int)first; op.conv2 = (int)first + 1; op.relu = 1;
@@ -342,12 +360,12 @@ struct Builder {
     net->convs.push_back(pc);
     Op cv{};
     cv.kind = OP_CONV; cv.in = y; cv.res = -1; cv.conv = (int)net->convs.size() - 1;
-    cv.out = new_tensor(cout, net->tensors[y].ds);
+    cv.out = new_tensor(cout, net->tensors[y].ds, name + ".tapmap");
     push(cv);
     Op op{};
     op.kind = OP_HEAD; op.in = cv.out; op.res = prev; op.conv = -1; op.head = b;
     // an f32 map of J x (S*h) x (S*w) occupies as many bytes as 2*J*S*S 16-bit channels at the branch resolution
-    op.out = to_heatmaps ? -2 : new_tensor(2 * J * S * S, net->tensors[y].ds);
+    op.out = to_heatmaps ? -2 : new_tensor(2 * J * S * S, net->tensors[y].ds, "");
     push(op);
     return op.out;
   }
@@ -377,23 +395,23 @@ struct Builder {
     op.nterms = nb - 1;
     for (int k = 0; k < nb - 1; ++k) { op.term[k] = low[k]; op.shift[k] = k + 1; }
     op.nouts = nb - 1;
-    for (int i = 1; i < nb; ++i) { op.outs[i - 1] = new_tensor(i == 1 ? cur[1] : c0, ds + 1); first->push_back(op.outs[i - 1]); }
-    op.out = new_tensor(c0, ds);
+    for (int i = 1; i < nb; ++i) { op.outs[i - 1] = new_tensor(i == 1 ? cur[1] : c0, ds + 1, fmt2(fp, i)); first->push_back(op.outs[i - 1]); }
+    op.out = new_tensor(c0, ds, fp.substr(0, fp.size() - 11) + "out0");   // fp = "<module>.fuse_layers"
     push(op);
     return op.out;
   }
-  static std::string fmt2(const std::string& fp, int i) {   // "<fp>.<i>.0.0": row i, source branch 0, hop 0
+  static std::string fmt2(const std::string& fp, int i) {   // "<fp>.<i>.0.0": row i, source branch 0, hop 0 (its conv + bn: ".0", ".1")
     char buf[256];
     snprintf(buf, sizeof(buf), "%s.%d.0.0", fp.c_str(), i);
     return buf;
   }
-  int fuse(const std::vector<int>& terms, const std::vector<int>& shifts, int C, int ds) {
+  int fuse(const std::vector<int>& terms, const std::vector<int>& shifts, int C, int ds, const std::string& name) {
     if (status != SCPOSE_OK) return -1;
     Op op{};
     op.kind = OP_FUSE; op.in = -1; op.res = -1; op.conv = -1; op.relu = 1;
     op.nterms = (int)terms.size();
     for (int k = 0; k < op.nterms; ++k) { op.term[k] = terms[k]; op.shift[k] = shifts[k]; }
-    op.out = new_tensor(C, ds);
+    op.out = new_tensor(C, ds, name);
     push(op);
     return op.out;
   }
@@ -443,19 +461,18 @@ int32_t hrnet_build(scpose_hrnet* net, Weights& W) {
     SCP_CHECK_HIP(hipMemcpy(net->d_stemf_b2, pb2.data(), 64 * 4, hipMemcpyHostToDevice));
     Op stem{};
     stem.kind = OP_STEM2; stem.in = -2; stem.res = -1; stem.conv = -1; stem.relu = 1;
-    stem.out = B.new_tensor(64, 2);
+    stem.out = B.new_tensor(64, 2, "stem2");
     B.push(stem);
     x = stem.out;
   } else {
     Op stem{};
     stem.kind = OP_STEM; stem.in = -2; stem.res = -1; stem.conv = -1; stem.relu = 1;
-    stem.out = B.new_tensor(64, 1);
+    stem.out = B.new_tensor(64, 1, "stem1");
     B.push(stem);
     x = stem.out;
-    net->taps.emplace_back("stem1", x);
     x = B.conv(x, "conv2", "bn2", 64, 3, 2, true);
+    if (x >= 0) B.rename_tap(x, "stem2");
   }
-  net->taps.emplace_back("stem2", x);
 
   // ---- layer1: 4 Bottlenecks (64 -> 256) ----
   for (int b = 0; b < 4; ++b) {
@@ -474,15 +491,16 @@ int32_t hrnet_build(scpose_hrnet* net, Weights& W) {
     int y = B.conv(x, p + ".conv1", p + ".bn1", 64, 1, 1, true);
     y = B.conv(y, p + ".conv2", p + ".bn2", 64, 3, 1, true);
     int nx = -2;
-    if (cat) nx = B.conv_cat(y, p + ".conv3", p + ".bn3", x, p + ".downsample.0", p + ".downsample.1", 256, true);
+    if (cat) nx = B.conv_cat(y, p + ".conv3", p + ".bn3", x, p + ".downsample.0", p + ".downsample.1", 256, true, p);
     if (nx == -2) {   // not concatenated (disabled or the packing does not allow the split)
       if (b == 0 && cat) res = B.conv(x, p + ".downsample.0", p + ".downsample.1", 256, 1, 1, false);
       nx = B.conv(y, p + ".conv3", p + ".bn3", 256, 1, 1, true, res);
+      if (nx >= 0) B.rename_tap(nx, p);
     }
     x = nx;
   }
 
-  net->taps.emplace_back("layer1", x);
+  net->taps.emplace_back("layer1", x);   // the same tensor as "layer1.3" (kept: the oracle's forward(taps=) names it so)
   std::vector<int> ylist{x};
   std::vector<int> pre{256};
   for (int si = 0; si < 3; ++si) {
@@ -573,7 +591,7 @@ int32_t hrnet_build(scpose_hrnet* net, Weights& W) {
           }
           T[i][0] = t;
           if (B.status != SCPOSE_OK) break;
-          outs.push_back(B.fuse(T[i], S[i], cur[i], net->tensors[xs[i]].ds));
+          outs.push_back(B.fuse(T[i], S[i], cur[i], net->tensors[xs[i]].ds, fmt("%s.out%d", mp.c_str(), i)));
         }
         B.parallel_end();
       } else {
@@ -598,13 +616,12 @@ int32_t hrnet_build(scpose_hrnet* net, Weights& W) {
           }
         }
         if (B.status != SCPOSE_OK) break;
-        outs.push_back(B.fuse(terms, shifts, cur[i], net->tensors[xs[i]].ds));
+        outs.push_back(B.fuse(terms, shifts, cur[i], net->tensors[xs[i]].ds, fmt("%s.out%d", mp.c_str(), i)));
       }
       B.parallel_end();
       }
       xs = outs;
       if (B.status != SCPOSE_OK) break;
-      net->taps.emplace_back(mp + ".out0", xs[0]);
     }
     if (B.status != SCPOSE_OK) break;
     ylist = xs;
@@ -646,6 +663,16 @@ int32_t hrnet_build(scpose_hrnet* net, Weights& W) {
     return SCPOSE_E_MISSING;
   }
   if (B.status != SCPOSE_OK) return B.status;
+  // every tensor an op writes is a tap (named at new_tensor), except the heat-maps and the f32 levels of the hrnet_cms pyramid
+  {
+    std::vector<char> named(net->tensors.size(), 0);
+    for (const auto& tp : net->taps) named[tp.second] = 1;
+    for (const Op& op : net->ops) {
+      if (op.kind != OP_HEAD && op.out >= 0 && !named[op.out]) { set_error("hrnet_create: op output tensor %d has no tap name", op.out); return SCPOSE_E_INVALID; }
+      for (int k = 0; k < op.nouts; ++k)
+        if (!named[op.outs[k]]) { set_error("hrnet_create: op output tensor %d has no tap name", op.outs[k]); return SCPOSE_E_INVALID; }
+    }
+  }
   SCP_CHECK_HIP(hipMalloc(&net->d_sched, net->ops.size() * 16 * sizeof(uint32_t)));
   SCP_CHECK_HIP(hipMemset(net->d_sched, 0, net->ops.size() * 16 * sizeof(uint32_t)));
   net->chain_at.assign(net->ops.size(), -1);
@@ -903,7 +930,8 @@ int32_t hrnet_forward(scpose_hrnet* net, const void* in, int in_fmt, int n, int 
                            net->desc.dtype, ptr(op.out), st);
     }
     if (rc != SCPOSE_OK) return rc;
-    if (stop_tensor >= 0 && op.out == stop_tensor) break;   // scpose_hrnet_forward_tap: the tensor is still intact in the arena
+    if (stop_tensor >= 0 && (op.out == stop_tensor || (op.nouts > 0 && std::find(op.outs, op.outs + op.nouts, stop_tensor) != op.outs + op.nouts)))
+      break;   // scpose_hrnet_forward_tap: the tensor is still intact in the arena (fuse_down also writes the first down hops)
   }
   if (lanes) { const int32_t rc = join_lanes(); if (rc != SCPOSE_OK) return rc; }
   st = st0;

@@ -478,8 +478,14 @@ class HrnetEngine:
         return HrnetGraph(self, x, fmt, (n, h, w), out, concurrent)
 
     def tap_names(self):
-        buf = ctypes.create_string_buffer(4096)
-        nat.check(nat.lib().scpose_hrnet_tap_names(self._h, buf, 4096), "hrnet_tap_names")
+        cap = 4096
+        while True:   # every op output is a tap: W48 offers well over 4 KB of names; grow until the library accepts the buffer
+            buf = ctypes.create_string_buffer(cap)
+            rc = nat.lib().scpose_hrnet_tap_names(self._h, buf, cap)
+            if rc == 0 or cap >= 1 << 24:
+                break
+            cap *= 4
+        nat.check(rc, "hrnet_tap_names")
         return buf.value.decode().split(",")
 
     def forward_tap(self, x, tap):

@@ -3,10 +3,14 @@ against torch's CPU float32 conv2d on identical 16-bit-rounded operands.
 
 Tolerance: the kernel accumulates in fp32 and rounds once to bf16 (8 significand bits), so
 agreement is required to 2 bf16 ulps of the result scale: |d| <= 1e-2*|ref| + 1e-2*rms(ref).
+Also, element-wise against the float64 result rounded once (tests/op_bound.py): one grid step + K 2^-24 S, and no rounding
+bias.
 """
 import pytest
 import torch
 import torch.nn.functional as F
+
+import op_bound as OB
 
 pytestmark = pytest.mark.gpu
 
@@ -116,6 +120,8 @@ def test_conv_matches_cpu(gpu_ops, case, dtype):
     bad = (got - ref).abs() > tol
     assert not bad.any(), "max |d| %.4g (tol %.4g) at %d/%d elements" % (
         (got - ref).abs().max(), tol.min(), int(bad.sum()), bad.numel())
+    ref64, E, _ = OB.conv_ref(x, _rnd(w, tdt), b, s, dtype, res=res, relu=relu)
+    OB.check(got, ref64, E, dtype, "conv", bias_check=got.numel() >= 4096)
 
 
 def test_conv_f32_nchw_output_with_joint_padding(gpu_ops):
@@ -184,6 +190,12 @@ def test_fused_basic_block_matches_two_convs(gpu_ops, shape, dtype):
     tol = 1.5e-2 * ref.abs() + 1.5e-2 * ref.pow(2).mean().sqrt()
     assert not ((got - ref).abs() > tol).any(), "fused vs CPU: max |d| %.4g" % (got - ref).abs().max()
     assert not ((got - two).abs() > tol).any(), "fused vs unfused HIP: max |d| %.4g" % (got - two).abs().max()
+    # as a composite against float64: the intermediate's allowance (its fp32 error, then a grid step) carried through conv2
+    mid64, E1, _ = OB.conv_ref(x, _rnd(w1, tdt), b1, 1, dtype, relu=True)
+    E1 = E1 + OB.u16(mid64.abs() + E1, dtype)
+    ref64, E2, _ = OB.conv_ref(mid64, _rnd(w2, tdt), b2, 1, dtype, res=x, relu=True)
+    E2 = E2 + F.conv2d(E1, _rnd(w2, tdt).double().abs(), None, 1, 1)
+    OB.check(got, ref64, E2, dtype, "fused block", bias_check=got.numel() >= 4096)
 
 
 EQUIVARIANCE = [  # cin cout k s H   N  res   -- one shape per kernel family at batch sizes that fill the persistent grid
