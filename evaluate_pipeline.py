@@ -48,6 +48,8 @@ def parse_args(argv=None):
     p.add_argument("--regression_opts", nargs="*", default=[], help="extra yacs KEY VAL overrides for tools/test.py")
     p.add_argument("--nproc_per_node", type=int, default=1)
     p.add_argument("--no_overlay", action="store_true")
+    p.add_argument("--pnp_refine", choices=("none", "lm"), default="none",
+                   help="stage 3: passed to export_predicted_poses_real.py (lm: Levenberg-Marquardt refinement of the poses)")
     return p.parse_args(argv)
 
 
@@ -116,7 +118,8 @@ def main(argv=None):
              "--pose_annotations", pred, "--landmarks_file", under("pose", a.landmarks_file),
              "--calibration_file_path", a.calibration_file_path if os.path.isabs(a.calibration_file_path)
              else os.path.join(ROOT, a.calibration_file_path), "--output_dir", j["pose_out"]]
-            + (["--no_overlay"] if a.no_overlay else []), STAGE_DIRS["pose"])
+            + (["--no_overlay"] if a.no_overlay else []) + (["--pnp_refine", a.pnp_refine] if a.pnp_refine != "none" else []),
+            STAGE_DIRS["pose"])
     return [j["pose_out"] for j in jobs]
 
 

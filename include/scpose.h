@@ -294,6 +294,27 @@ int32_t scpose_pnp_epnp_ransac_rows(const float* kp_xyc, const double* landmarks
                                     int32_t min_pts, double thr_decay, int32_t thr_iters,
                                     int32_t max_iters, double reproj_err, double confidence,
                                     double* rows, void* stream);
+/* (ABI 7, additive) The same solve, then optionally a Levenberg-Marquardt refinement of every solved frame (status > 0) and the
+ * final point set as a bit mask -- the `inliers` output of cv2.solvePnPRansac, which export_predicted_poses_real.py:199 unpacks
+ * and ignores.  The refinement restates cv2.solvePnPRefineLM from OpenCV's documentation (unpinned against cv2): parameters
+ * (rvec, tvec), residuals = projection (pinhole + k1,k2,p1,p2,k3) of the float32-rounded landmark minus the raw float32 image
+ * point, over the final fit's points (the RANSAC inliers; all 5 points for n == 5; the 4 points of the P3P branch for n == 4);
+ * step (J^T J + lambda diag(J^T J)) d = -J^T r, lambda_0 = 1e-3, / 10 on a cost decrease, * 10 (step rejected) otherwise;
+ * stops after refine_iters iterations or once a step with |d| <= FLT_EPSILON |p| has been tried (TermCriteria(EPS + COUNT, 20,
+ * FLT_EPSILON)).  The
+ * refined cost is never above the starting one; a non-finite refined pose keeps the unrefined one; status is unchanged.
+ * Each frame's result is bit-identical whatever the batch size and the frame's position in the batch.
+ *   refine_iters  0..100; 0: no refinement -- R / t / rvec / status / rows bit-identical to scpose_pnp_epnp_ransac / _rows
+ *   rot, tvec, rvec, status  the per-array outputs of scpose_pnp_epnp_ransac (rvec may be NULL), or all NULL when rows != NULL
+ *   rows          device f64 N x 13 as in scpose_pnp_epnp_ransac_rows, or NULL; exactly one of the two output forms is given
+ *   inliers       device u64 N or NULL: bit k set = landmark k (landmark order, not compacted order) is in the final point set;
+ *                 popcount = status for status > 0, 0 for failed frames */
+int32_t scpose_pnp_epnp_ransac_refine(const float* kp_xyc, const double* landmarks, const double* K,
+                                      const double* dist, int32_t n, int32_t j, double conf_thr0,
+                                      int32_t min_pts, double thr_decay, int32_t thr_iters,
+                                      int32_t max_iters, double reproj_err, double confidence,
+                                      int32_t refine_iters, double* rot, double* tvec, double* rvec,
+                                      int32_t* status, double* rows, uint64_t* inliers, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Single-layer entry points (unit-level parity of the kernels the forward is made of).

@@ -2,7 +2,8 @@
 """Drop-in for the reference's pose_estimation/export_predicted_poses_real.py (:126-236): same six
 required arguments, same opencv_poses.json + overlay JPEGs; the per-frame cv2.solvePnPRansac
 loop is one batched launch of the HIP EPnP+RANSAC kernel.  --no_overlay skips the debug JPEGs
-(image I/O dominates the reference script's wall-clock; the poses do not depend on it)."""
+(image I/O dominates the reference script's wall-clock; the poses do not depend on it).  --pnp_refine lm adds a
+Levenberg-Marquardt refinement of each pose on its inliers (default none: the reference's poses, byte for byte)."""
 import argparse
 import os
 import sys
@@ -14,6 +15,7 @@ import scpose  # noqa: E402,F401
 from importlib import import_module  # noqa: E402
 
 pose_export = import_module("spacecraft-pose-estimation_amd.pose_export")
+PNP_REFINE_ITERS = {"none": 0, "lm": 20}     # --pnp_refine -> refine_iters (20: cv2.solvePnPRefineLM's default criteria)
 
 
 def main():
@@ -26,10 +28,13 @@ def main():
     parser.add_argument("--output_dir", required=True, type=str, help="output directory")
     parser.add_argument("--no_overlay", action="store_true", help="do not write the per-frame reprojection JPEGs")
     parser.add_argument("--with_status", action="store_true", help="add the per-frame RANSAC status to the JSON records")
+    parser.add_argument("--pnp_refine", choices=("none", "lm"), default="none",
+                        help="lm: Levenberg-Marquardt refinement of each pose on its RANSAC inliers (20 iterations, "
+                             "as cv2.solvePnPRefineLM); none (default): the reference's EPnP poses")
     args = parser.parse_args()
     pose_export.export(args.frames_dir, args.detection_annotations, args.pose_annotations, args.landmarks_file,
                        args.calibration_file_path, args.output_dir, overlay=not args.no_overlay,
-                       include_status=args.with_status)
+                       include_status=args.with_status, refine_iters=PNP_REFINE_ITERS[args.pnp_refine])
 
 
 if __name__ == "__main__":

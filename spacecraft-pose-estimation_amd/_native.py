@@ -91,6 +91,9 @@ SYMBOLS = {
                                          c_void_p, c_void_p, c_void_p, c_void_p]),
     "scpose_pnp_epnp_ransac_rows": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_double,
                                               c_int32, c_double, c_int32, c_int32, c_double, c_double, c_void_p, c_void_p]),
+    "scpose_pnp_epnp_ransac_refine": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_double,
+                                                c_int32, c_double, c_int32, c_int32, c_double, c_double, c_int32,
+                                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "scpose_conv_create": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                      POINTER(c_void_p)]),
     "scpose_conv_destroy": (c_int32, [c_void_p]),

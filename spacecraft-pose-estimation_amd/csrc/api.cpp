@@ -88,6 +88,25 @@ extern "C" int32_t scpose_pnp_epnp_ransac_rows(const float* kp_xyc, const double
                     static_cast<hipStream_t>(stream), rows);
 }
 
+extern "C" int32_t scpose_pnp_epnp_ransac_refine(const float* kp_xyc, const double* landmarks, const double* K,
+                                                 const double* dist, int32_t n, int32_t j, double conf_thr0,
+                                                 int32_t min_pts, double thr_decay, int32_t thr_iters,
+                                                 int32_t max_iters, double reproj_err, double confidence,
+                                                 int32_t refine_iters, double* rot, double* tvec, double* rvec,
+                                                 int32_t* status, double* rows, uint64_t* inliers, void* stream) {
+  // argument errors are reported before the n == 0 return, so that they can be checked without a device
+  SCP_REQUIRE(refine_iters >= 0 && refine_iters <= 100, "pnp_refine: refine_iters=%d (0..100)", refine_iters);
+  const bool arrays = rot || tvec || rvec || status;
+  SCP_REQUIRE(arrays != (rows != nullptr),
+              "pnp_refine: give exactly one output form: rot/tvec/status[/rvec], or rows (with rot/tvec/rvec/status NULL)");
+  SCP_REQUIRE(rows || (rot && tvec && status), "pnp_refine: rot, tvec and status are required in the per-array form");
+  if (n == 0) return SCPOSE_OK;
+  SCP_REQUIRE(kp_xyc && landmarks && K, "pnp_refine: null argument");
+  return pnp_launch(kp_xyc, landmarks, K, dist, n, j, conf_thr0, min_pts, thr_decay, thr_iters, max_iters, reproj_err,
+                    confidence, rot, tvec, rvec, status, static_cast<hipStream_t>(stream), rows, refine_iters,
+                    reinterpret_cast<unsigned long long*>(inliers));
+}
+
 extern "C" int32_t scpose_conv_create(const float* weight, const float* bias, int32_t cout,
                                       int32_t cin, int32_t ksize, int32_t stride, int32_t dtype,
                                       scpose_conv_t* out) {

@@ -33,6 +33,7 @@ static constexpr int kMaxJ = 64;
 // and a batch of frames takes half as many CUs away from the convolution kernels of the next forward (bench.py runs the
 // PnP stage beside it); the ordered replay below is independent of the batch width, so the results do not change.
 static constexpr int kPW = 32;
+static constexpr int kMaxRefineIters = 100;   // scpose_pnp_epnp_ransac_refine: refine_iters in [0, 100]
 
 struct PnpArgs {
   const float* kp;          // N x J x 3
@@ -49,6 +50,12 @@ struct PnpArgs {
   int min_pts, thr_iters, max_iters;
   double reproj_err, confidence;
   int dbg_no_spec;          // development (SCPOSE_PNP_SPEC=0): ignore the speculative final fits
+  static constexpr bool kRefine = false;
+};
+struct PnpRefineArgs : PnpArgs {   // scpose_pnp_epnp_ransac_refine
+  int refine_iters;                // Levenberg-Marquardt iterations after the final fit (lm_refine), 0..kMaxRefineIters
+  unsigned long long* inliers;     // N or null: bit j = landmark j is in the final fit's point set
+  static constexpr bool kRefine = true;
 };
 
 struct Cam { double fx, fy, cx, cy, k[5]; };
@@ -943,10 +950,171 @@ __device__ int ransac_update_num_iters(double p, double ep, int model_points, in
   return denom >= 0 || -num >= max_iters * (-denom) ? max_iters : (int)rint(num / denom);
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Levenberg-Marquardt refinement of a solved pose (scpose_pnp_epnp_ransac_refine; opt-in, pnp_kernel<PnpRefineArgs> only).
+// Restated from OpenCV's documentation of solvePnPRefineLM, unpinned against cv2 (no cv2 here, as for oracle/pnp_ref.c):
+// parameters p = (rvec, tvec), residuals project_point(X_i) - (raw float32 image point i) over the final fit's point set,
+// analytic 2 x 6 Jacobian per point, step (J^T J + lambda diag(J^T J)) d = -J^T r with lambda_0 = 1e-3, accept when the
+// cost sum r^2 drops (lambda / 10), else reject (lambda * 10; counts as an iteration), stop after refine_iters iterations or
+// once a step with |d| <= FLT_EPSILON |p| has been tried (TermCriteria(EPS + COUNT, 20, FLT_EPSILON)).  tests/pnp_lm_restated.py is the same algorithm
+// in NumPy.  Lane i owns compacted point i; the sums over points are one xor butterfly per entry, a fixed order that gives
+// every lane the same bits, so a frame's result does not depend on the batch or on its place in it.
+// ------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// Residual (2) and Jacobian rows d(u, v) / d(rvec, tvec) (2 x 6) of one point at pose p; R = rodrigues_vec2mat(p).
+__device__ __forceinline__ void lm_point(const Cam& cam, const double p[6], const double R[9], const double* X, const double* uv,
+                                         double res[2], double Jr[12]) {
+  double u, v;
+  project_point(cam, R, p + 3, X, &u, &v);
+  res[0] = u - uv[0]; res[1] = v - uv[1];
+  const double Y[3] = {R[0] * X[0] + R[1] * X[1] + R[2] * X[2], R[3] * X[0] + R[4] * X[1] + R[5] * X[2],
+                       R[6] * X[0] + R[7] * X[1] + R[8] * X[2]};
+  // d(R X) / d rvec = -[R X]x (r r^T + [r]x (I - R)) / theta^2 (Rodrigues derivative); -[X]x at the identity branch
+  double M[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  const double th2 = p[0] * p[0] + p[1] * p[1] + p[2] * p[2];
+  if (sqrt(th2) >= DBL_EPSILON) {
+    const double S[9] = {0, -p[2], p[1], p[2], 0, -p[0], -p[1], p[0], 0};
+    const double E[9] = {1 - R[0], -R[1], -R[2], -R[3], 1 - R[4], -R[5], -R[6], -R[7], 1 - R[8]};
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++)
+        M[3 * i + j] = (p[i] * p[j] + (S[3 * i] * E[j] + S[3 * i + 1] * E[3 + j] + S[3 * i + 2] * E[6 + j])) / th2;
+  }
+  double dY[9];   // dY[3 * i + j] = d Y_i / d r_j = -(Y x M_col_j)_i
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    const double m0 = M[j], m1 = M[3 + j], m2 = M[6 + j];
+    dY[j] = -(Y[1] * m2 - Y[2] * m1);
+    dY[3 + j] = -(Y[2] * m0 - Y[0] * m2);
+    dY[6 + j] = -(Y[0] * m1 - Y[1] * m0);
+  }
+  const double Pc[3] = {Y[0] + p[3], Y[1] + p[4], Y[2] + p[5]};
+  const double iz = 1. / Pc[2], x = Pc[0] * iz, y = Pc[1] * iz;
+  const double k1 = cam.k[0], k2 = cam.k[1], p1 = cam.k[2], p2 = cam.k[3], k3 = cam.k[4];
+  const double r2 = x * x + y * y;
+  const double cdist = 1 + k1 * r2 + k2 * r2 * r2 + k3 * r2 * r2 * r2, dc = k1 + 2 * k2 * r2 + 3 * k3 * r2 * r2;
+  const double dxx = cdist + 2 * x * x * dc + 2 * p1 * y + 6 * p2 * x, dxy = 2 * x * y * dc + 2 * p1 * x + 2 * p2 * y;
+  const double dyx = 2 * x * y * dc + 2 * p1 * x + 2 * p2 * y, dyy = cdist + 2 * y * y * dc + 6 * p1 * y + 2 * p2 * x;
+  // d(u, v) / d Pc: diag(fx, fy) * distortion (2 x 2) * perspective division (2 x 3)
+  const double du[3] = {cam.fx * dxx * iz, cam.fx * dxy * iz, -cam.fx * (dxx * x + dxy * y) * iz};
+  const double dv[3] = {cam.fy * dyx * iz, cam.fy * dyy * iz, -cam.fy * (dyx * x + dyy * y) * iz};
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    Jr[j] = du[0] * dY[j] + du[1] * dY[3 + j] + du[2] * dY[6 + j];
+    Jr[6 + j] = dv[0] * dY[j] + dv[1] * dY[3 + j] + dv[2] * dY[6 + j];
+    Jr[3 + j] = du[j];
+    Jr[9 + j] = dv[j];
+  }
+}
+
+// (A + lambda diag(A)) d = -g by Cholesky; A packed upper triangle (row-major, 21).  false when the matrix is not positive definite.
+__device__ __forceinline__ bool lm_solve(const double A[21], const double g[6], double lambda, double d[6]) {
+  double L[36], y[6];
+#pragma unroll
+  for (int i = 0, k = 0; i < 6; i++)
+#pragma unroll
+    for (int j = i; j < 6; j++, k++) {
+      L[6 * j + i] = A[k];    // lower triangle of the symmetric matrix
+      if (j == i) L[6 * i + i] = A[k] + lambda * A[k];
+    }
+#pragma unroll
+  for (int j = 0; j < 6; j++) {
+    double s = L[6 * j + j];
+#pragma unroll
+    for (int k = 0; k < j; k++) s -= L[6 * j + k] * L[6 * j + k];
+    if (!(s > 0)) return false;
+    L[6 * j + j] = sqrt(s);
+#pragma unroll
+    for (int i = j + 1; i < 6; i++) {
+      double t = L[6 * i + j];
+#pragma unroll
+      for (int k = 0; k < j; k++) t -= L[6 * i + k] * L[6 * j + k];
+      L[6 * i + j] = t / L[6 * j + j];
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    double s = -g[i];
+#pragma unroll
+    for (int k = 0; k < i; k++) s -= L[6 * i + k] * y[k];
+    y[i] = s / L[6 * i + i];
+  }
+#pragma unroll
+  for (int i = 5; i >= 0; i--) {
+    double s = y[i];
+#pragma unroll
+    for (int k = i + 1; k < 6; k++) s -= L[6 * k + i] * d[k];
+    d[i] = s / L[6 * i + i];
+  }
+  return true;
+}
+
+// Refines (rvec, tvec) in place on the compacted points of `set` (>= 4).  Wave-uniform: all 64 lanes call it.
+__device__ void lm_refine(const Cam& cam, const double* s_obj, const double* s_img, unsigned long long set, int lane,
+                          int iters, double rvec[3], double tvec[3]) {
+  const bool mine = (set >> lane) & 1ULL;
+  double p[6] = {rvec[0], rvec[1], rvec[2], tvec[0], tvec[1], tvec[2]};
+  double A[21], g[6], cost;
+  double res[2] = {0, 0}, Jr[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  auto eval = [&](const double* q) {   // this lane's residual and Jacobian at q, and the wave's cost
+    if (mine) {
+      double R[9];
+      rodrigues_vec2mat(q, R);
+      lm_point(cam, q, R, s_obj + 3 * lane, s_img + 2 * lane, res, Jr);
+    }
+    return wave_sum(res[0] * res[0] + res[1] * res[1]);
+  };
+  auto normal_eq = [&]() {
+#pragma unroll
+    for (int i = 0, k = 0; i < 6; i++)
+#pragma unroll
+      for (int j = i; j < 6; j++, k++) A[k] = wave_sum(Jr[i] * Jr[j] + Jr[6 + i] * Jr[6 + j]);
+#pragma unroll
+    for (int i = 0; i < 6; i++) g[i] = wave_sum(Jr[i] * res[0] + Jr[6 + i] * res[1]);
+  };
+  cost = eval(p);
+  normal_eq();
+  double lambda = 1e-3;
+  for (int it = 0; it < iters; it++) {
+    double d[6];
+    if (!lm_solve(A, g, lambda, d)) { lambda *= 10; continue; }
+    double nd = 0, np = 0, q[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++) { nd += d[i] * d[i]; np += p[i] * p[i]; q[i] = p[i] + d[i]; }
+    const double c = eval(q);
+    if (c < cost) {
+#pragma unroll
+      for (int i = 0; i < 6; i++) p[i] = q[i];
+      cost = c;
+      normal_eq();
+      lambda /= 10;
+    } else {
+      lambda *= 10;
+    }
+    if (sqrt(nd) <= FLT_EPSILON * sqrt(np)) break;   // converged: the step (taken if it lowered the cost) is below FLT_EPSILON |p|
+  }
+  bool fin = true;
+#pragma unroll
+  for (int i = 0; i < 6; i++) fin = fin && isfinite(p[i]);
+  if (fin) {
+    for (int i = 0; i < 3; i++) { rvec[i] = p[i]; tvec[i] = p[3 + i]; }
+  }
+}
+
 // One wave per frame, a few frames per workgroup (blockDim = 64 x frames; the waves share nothing but the CU).  A wave of
 // this kernel owns a whole SIMD (512 registers: the spills of the 12 x 12 solves live in AGPRs), so a CU that holds even one
 // frame cannot take a convolution workgroup of the next forward, which bench.py runs beside this kernel.
-__global__ __launch_bounds__(256) void pnp_kernel(const PnpArgs a) {
+// Args = PnpArgs: scpose_pnp_epnp_ransac / _rows.  Args = PnpRefineArgs adds lm_refine and the inlier masks behind `if constexpr`,
+// so the PnpArgs instantiation compiles to the same instructions as before refinement existed.
+template <class Args>
+__global__ __launch_bounds__(256) void pnp_kernel(const Args a) {
+  constexpr bool kRefine = Args::kRefine;
   extern __shared__ __attribute__((aligned(16))) double smem_all[];
   const int J = a.J;                         // the per-point arrays are sized by the launch's J (pnp_launch), not by kMaxJ
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -997,17 +1165,20 @@ __global__ __launch_bounds__(256) void pnp_kernel(const PnpArgs a) {
   e.obj = s_obj; e.uc = cam.cx; e.vc = cam.cy; e.fu = cam.fx; e.fv = cam.fy;
   double* ut = s_ut + (lane & (kPW - 1));    // wave-uniform solves: lanes l and l + kPW write the same values to the same slots
   const int model_points = 5;
+  unsigned long long fin_set = 0;            // refinement: the final fit's points, compacted order (wave-uniform)
 
   if (n < 4) {
     status = -1;
   } else if (n == 4) {
     // OpenCV switches to its P3P kernel for exactly four points and skips RANSAC (solve_p3p above); no pose -> -2 like a failed RANSAC
     status = solve_p3p(cam, s_obj, s_u32, lane, rvec, tvec) ? 4 : -2;
+    fin_set = 0xfULL;
   } else if (n == model_points) {
     PtSet ps{(1ULL << n) - 1ULL, 0u, n, false};
     e.us = s_u32;
     solve_epnp(e, ps, ut, rvec, tvec);
     status = n;
+    fin_set = ps.mask;
   } else {
     int niters = a.max_iters > 1 ? a.max_iters : 1;
     int max_good = 0;
@@ -1088,6 +1259,7 @@ __global__ __launch_bounds__(256) void pnp_kernel(const PnpArgs a) {
     if (max_good <= 0) {
       status = -2;
     } else {
+      fin_set = best_mask;
       const unsigned long long hit = __ballot(spec_lane && spec_mask == best_mask);
       if (hit != 0ULL && !SCP_DEV_ONLY(a.dbg_no_spec)) {   // the final fit has already been computed by a speculative lane
         const int src = __builtin_ctzll(hit);
@@ -1100,6 +1272,16 @@ __global__ __launch_bounds__(256) void pnp_kernel(const PnpArgs a) {
         status = ps.n;
       }
     }
+  }
+
+  unsigned long long lm_mask = 0;
+  if constexpr (kRefine) {
+    if (status > 0 && a.refine_iters > 0 && isfinite(rvec[0]) && isfinite(rvec[1]) && isfinite(rvec[2]) && isfinite(tvec[0]) &&
+        isfinite(tvec[1]) && isfinite(tvec[2]))
+      lm_refine(cam, s_obj, s_img, fin_set, lane, a.refine_iters, rvec, tvec);
+    // compacted position -> landmark index: lane j holds landmark j, at position popcount(sel below j) when selected
+    const int pos = __popcll(sel & ((1ULL << lane) - 1ULL));
+    lm_mask = __ballot(((sel >> lane) & 1ULL) && ((fin_set >> pos) & 1ULL));
   }
 
   if (lane == 0) {
@@ -1120,13 +1302,16 @@ __global__ __launch_bounds__(256) void pnp_kernel(const PnpArgs a) {
       a.status[frame] = status;
     }
     if (a.rvec) for (int k = 0; k < 3; k++) a.rvec[(size_t)frame * 3 + k] = rvec[k];
+    if constexpr (kRefine) { if (a.inliers) a.inliers[frame] = status > 0 ? lm_mask : 0ULL; }
   }
 }
 
 int32_t pnp_launch(const float* kp_xyc, const double* landmarks, const double* K, const double* dist,
                    int N, int J, double conf_thr0, int min_pts, double thr_decay, int thr_iters,
                    int max_iters, double reproj_err, double confidence, double* rot, double* tvec,
-                   double* rvec, int32_t* status, hipStream_t stream, double* rows) {
+                   double* rvec, int32_t* status, hipStream_t stream, double* rows, int refine_iters,
+                   unsigned long long* inliers) {
+  SCP_REQUIRE(refine_iters >= 0 && refine_iters <= kMaxRefineIters, "pnp: refine_iters=%d (0..%d)", refine_iters, kMaxRefineIters);
   SCP_REQUIRE(J >= 1 && J <= kMaxJ, "pnp: J=%d landmarks (1..%d)", J, kMaxJ);
   SCP_REQUIRE(confidence > 0 && confidence < 1, "pnp: confidence %g must be in (0,1)", confidence);
   SCP_REQUIRE(N >= 0, "pnp: N=%d", N);
@@ -1141,9 +1326,19 @@ int32_t pnp_launch(const float* kp_xyc, const double* landmarks, const double* K
   int fpw = 2;
   { static const char* e = dev_env("SCPOSE_PNP_FPW"); if (kDevBuild && e && atoi(e) >= 1 && atoi(e) <= 4 && atoi(e) * per_frame <= 160 * 1024) fpw = atoi(e); }   // development: frames per workgroup
   const size_t lds = per_frame * fpw;
+  if (refine_iters > 0 || inliers) {   // opt-in refinement / inlier masks: the second kernel; the default launch below is unchanged
+    static LdsOptIn big_lds_refine;
+    { const int32_t rc = lds_opt_in(reinterpret_cast<const void*>(pnp_kernel<PnpRefineArgs>), 160 * 1024, &big_lds_refine); if (rc != SCPOSE_OK) return rc; }
+    PnpRefineArgs ra;
+    static_cast<PnpArgs&>(ra) = a;
+    ra.refine_iters = refine_iters; ra.inliers = inliers;
+    hipLaunchKernelGGL(pnp_kernel<PnpRefineArgs>, dim3((N + fpw - 1) / fpw), dim3(64 * fpw), lds, stream, ra);
+    SCP_CHECK_HIP(hipGetLastError());
+    return SCPOSE_OK;
+  }
   static LdsOptIn big_lds;   // per device (common.h); opted in once for the whole LDS
-  { const int32_t rc = lds_opt_in(reinterpret_cast<const void*>(pnp_kernel), 160 * 1024, &big_lds); if (rc != SCPOSE_OK) return rc; }
-  hipLaunchKernelGGL(pnp_kernel, dim3((N + fpw - 1) / fpw), dim3(64 * fpw), lds, stream, a);
+  { const int32_t rc = lds_opt_in(reinterpret_cast<const void*>(pnp_kernel<PnpArgs>), 160 * 1024, &big_lds); if (rc != SCPOSE_OK) return rc; }
+  hipLaunchKernelGGL(pnp_kernel<PnpArgs>, dim3((N + fpw - 1) / fpw), dim3(64 * fpw), lds, stream, a);
   SCP_CHECK_HIP(hipGetLastError());
   return SCPOSE_OK;
 }

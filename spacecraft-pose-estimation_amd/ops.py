@@ -243,11 +243,16 @@ def heatmap_accumulate(acc, x, div=1.0):
 
 # ------------------------------------------------------------------ PnP
 def pnp_epnp_ransac(kp_xyc, landmarks, K, dist, conf_thr0=0.95, min_pts=15, thr_decay=0.8, thr_iters=100,
-                    max_iters=10000, reproj_err=15.0, confidence=0.99, want_rvec=False, rows=None):
+                    max_iters=10000, reproj_err=15.0, confidence=0.99, want_rvec=False, rows=None, refine_iters=0,
+                    want_inliers=False):
     """kp_xyc (N,J,3) f32 device; landmarks (J,3), K (3,3), dist (5,) f64 device.
-    Returns rot (N,3,3) f64, tvec (N,3) f64, status (N,) i32 [, rvec (N,3)].
+    Returns rot (N,3,3) f64, tvec (N,3) f64, status (N,) i32 [, rvec (N,3)] [, inliers (N,J) bool].
     rows: a contiguous (N,13) f64 device buffer -> the kernel writes [R (9), t (3), status] per frame straight into it
-    (scpose_pnp_epnp_ransac_rows) and `rows` is returned: the block a rank all-gathers and copies to the host."""
+    (scpose_pnp_epnp_ransac_rows) and `rows` is returned: the block a rank all-gathers and copies to the host
+    (`(rows, inliers)` with want_inliers).
+    refine_iters (0..100): Levenberg-Marquardt iterations on each solved frame's final point set after the final fit
+    (scpose_pnp_epnp_ransac_refine; 20 = cv2.solvePnPRefineLM's default).  want_inliers: also return that point set per frame,
+    inliers[i, j] = landmark j was used.  With both at their defaults the existing entry points are called, as before."""
     _need_cuda(kp_xyc, landmarks, K, dist)
     kp = kp_xyc.contiguous().float()
     n, j, _ = kp.shape
@@ -265,11 +270,20 @@ def pnp_epnp_ransac(kp_xyc, landmarks, K, dist, conf_thr0=0.95, min_pts=15, thr_
         dd = torch.cat([dd, torch.zeros(1, dtype=torch.float64, device=dd.device)])
     elif dd.numel() != 5:
         raise nat.NativeError("pnp_epnp_ransac: %d distortion coefficients; supported are 4 or 5 (k1,k2,p1,p2[,k3])" % dd.numel())
+    refine = refine_iters != 0 or want_inliers
+    inl = torch.zeros((n,), dtype=torch.int64, device=dev) if want_inliers else None   # uint64 bit masks, landmark order
     if rows is not None:
         if want_rvec:     # the gather block has no rvec column: refuse instead of silently returning one tensor
             raise nat.NativeError("pnp_epnp_ransac: rows=... excludes want_rvec (the (N, 13) block is [R, t, status]); call without rows for rvec")
         if tuple(rows.shape) != (n, 13) or rows.dtype != torch.float64 or not rows.is_contiguous() or rows.device != dev:
             raise nat.NativeError("pnp_epnp_ransac: rows must be a contiguous float64 (%d, 13) tensor on %s" % (n, dev))
+        if refine:
+            nat.check(nat.lib().scpose_pnp_epnp_ransac_refine(_ptr(kp), _ptr(lm), _ptr(Kd), _ptr(dd), n, j, conf_thr0, min_pts,
+                                                              thr_decay, thr_iters, max_iters, reproj_err, confidence,
+                                                              int(refine_iters), None, None, None, None, _ptr(rows),
+                                                              _ptr(inl), _stream()),
+                      "pnp_epnp_ransac_refine")
+            return (rows, _mask_bits(inl, j)) if want_inliers else rows
         nat.check(nat.lib().scpose_pnp_epnp_ransac_rows(_ptr(kp), _ptr(lm), _ptr(Kd), _ptr(dd), n, j, conf_thr0, min_pts, thr_decay,
                                                         thr_iters, max_iters, reproj_err, confidence, _ptr(rows), _stream()),
                   "pnp_epnp_ransac_rows")
@@ -278,10 +292,23 @@ def pnp_epnp_ransac(kp_xyc, landmarks, K, dist, conf_thr0=0.95, min_pts=15, thr_
     tv = torch.empty((n, 3), dtype=torch.float64, device=dev)
     rv = torch.empty((n, 3), dtype=torch.float64, device=dev)
     st = torch.empty((n,), dtype=torch.int32, device=dev)
+    if refine:
+        nat.check(nat.lib().scpose_pnp_epnp_ransac_refine(_ptr(kp), _ptr(lm), _ptr(Kd), _ptr(dd), n, j, conf_thr0, min_pts,
+                                                          thr_decay, thr_iters, max_iters, reproj_err, confidence,
+                                                          int(refine_iters), _ptr(rot), _ptr(tv), _ptr(rv), _ptr(st), None,
+                                                          _ptr(inl), _stream()),
+                  "pnp_epnp_ransac_refine")
+        out = (rot, tv, st, rv) if want_rvec else (rot, tv, st)
+        return out + (_mask_bits(inl, j),) if want_inliers else out
     nat.check(nat.lib().scpose_pnp_epnp_ransac(_ptr(kp), _ptr(lm), _ptr(Kd), _ptr(dd), n, j, conf_thr0, min_pts, thr_decay,
                                                thr_iters, max_iters, reproj_err, confidence, _ptr(rot), _ptr(tv), _ptr(rv),
                                                _ptr(st), _stream()), "pnp_epnp_ransac")
     return (rot, tv, st, rv) if want_rvec else (rot, tv, st)
+
+
+def _mask_bits(masks, j):
+    """(N,) int64 holding uint64 landmark bit masks -> (N, J) bool."""
+    return ((masks.unsqueeze(1) >> torch.arange(j, device=masks.device, dtype=torch.int64)) & 1).bool()
 
 
 # ------------------------------------------------------------------ HRNet engine

@@ -65,7 +65,9 @@ def draw_overlay(frames_dir, file_name, out_path, bbox, K, R, T, landmarks):
 
 
 def export(frames_dir, detection_annotations, pose_annotations, landmarks_file, calibration_file_path, output_dir,
-           overlay=True, include_status=False):
+           overlay=True, include_status=False, refine_iters=0):
+    """refine_iters > 0: Levenberg-Marquardt refinement of every solved pose on its final point set (ops.pnp_epnp_ransac);
+    0 keeps the reference's EPnP-only poses."""
     Path(output_dir).mkdir(parents=True, exist_ok=True)
     landmarks = read_landmarks(landmarks_file)
     with open(calibration_file_path, "r") as f:
@@ -79,7 +81,8 @@ def export(frames_dir, detection_annotations, pose_annotations, landmarks_file, 
     preds = np.array(loadmat(pose_annotations)["preds"], dtype=np.float32)
     n = min(len(image_ids), preds.shape[0])           # zip() semantics of :174-175
     min_pts = 15                                       # :192
-    R, T, status = solve_poses(preds[:n], landmarks, K, dist, min_pts=min_pts)
+    kw = {"refine_iters": refine_iters} if refine_iters else {}   # only when asked: stand-ins of ops.pnp_epnp_ransac need not know it
+    R, T, status = solve_poses(preds[:n], landmarks, K, dist, min_pts=min_pts, **kw)
     poses = []
     if parallel.world()[1] != 0:
         return poses
