@@ -250,6 +250,41 @@ int32_t scpose_crop_warp_roi(const uint8_t* windows, const int64_t* offsets, con
                              const int32_t* roi_xywh, const double* minv, int32_t n, int32_t out_h,
                              int32_t out_w, int32_t swap_rb, uint8_t* crops, void* stream);
 
+/* Event stream -> event frames: stage 0 of the reference's event pipeline, v2e/convert_aedats.py = `e2v.py --dvs_exposure
+ * duration 10000 --dvs_vid_full_scale 2` (v2e/v2ecore/renderer.py: render_events_to_frames, accumulate_event_frame;
+ * v2ecore/v2e_utils.py: hist2d_numba_seq) followed by cv2.undistort of every frame.  Additive in ABI 7.
+ * The stream is time-sorted and lives in device memory as separate columns: t (i64 ticks, |t| < 2^53), x, y (i32), p (i8 or
+ * i32; ON is p == 1, anything else is OFF; not read when fold_polarity != 0).
+ *
+ * scpose_events_frame_bounds: frame k takes the events [searchsorted(t, starts[k], left), searchsorted(t, starts[k+1], right)),
+ * the end clamped to n_events - 1 (the reference never draws the last event of a stream); an event exactly on a boundary is
+ * counted in both neighbouring frames.
+ *   starts   device f64 F + 1: the frame start times, accumulated on the host by repeated float64 addition as the reference
+ *            does (event_render.py: frame_schedule)
+ *   bounds   device i64 F x 2: [begin, end) of every frame's slice of the stream
+ *
+ * scpose_events_render: histogram (row = y, column = x, events outside the frame dropped) of every frame's slice, every
+ * polarity counted +1 (fold_polarity != 0, what e2v.py does) or ON minus OFF; the sum is clipped to [-full_scale, full_scale]
+ * AFTER summation and mapped through gray_lut (device u8, 2 * full_scale + 1 entries for c = -full_scale ... full_scale; the
+ * reference's uint8(((c + fs) / float(2 * fs)) * 255), built on the host) to three equal channels.
+ *   K, dist     device f64 3 x 3 row-major and [k1, k2, p1, p2, k3]: undistort every frame as cv2.undistort(img, K, dist) does
+ *               (source position through the forward distortion model in float64, new camera matrix = K, quantised to 1/32 px,
+ *               the fixed-point bilinear tap of scpose_crop_warp, border 0); both NULL: no undistortion
+ *   frames      device u8 F x h x w x 3: the (undistorted) frames, back to back: the `frames` of scpose_crop_warp with
+ *               offsets[k] = k * h * w * 3
+ *   distorted   device u8 F x h x w x 3 or NULL: also keep the frames before undistortion
+ *   workspace   caller-owned, scpose_events_workspace_bytes(F, h, w); only used when K is given
+ * Frames may be rendered in chunks (bounds + 2 * k, any F): chunked output equals one call.  Integer counters in LDS, no
+ * global atomic: the output is bitwise deterministic.  F == 0 is a no-op; full_scale 1..127; w <= 40896 (one row of counters
+ * must fit the LDS), h, w <= 32767, h * w <= 2^24. */
+int32_t scpose_events_workspace_bytes(int32_t n_frames, int32_t h, int32_t w, size_t* bytes);
+int32_t scpose_events_frame_bounds(const int64_t* t, int64_t n_events, const double* starts, int32_t n_frames,
+                                   int64_t* bounds, void* stream);
+int32_t scpose_events_render(const int32_t* x, const int32_t* y, const void* p, int32_t p_itemsize, const int64_t* bounds,
+                             int32_t n_frames, int32_t h, int32_t w, int32_t full_scale, int32_t fold_polarity,
+                             const uint8_t* gray_lut, const double* K, const double* dist, uint8_t* frames,
+                             uint8_t* distorted, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Flip test (cfg.TEST.FLIP_TEST, lib/core/function.py:347-366): out = (a + flip_back(b)) * 0.5 where b
  * is the forward of the x-flipped input; flip_back (lib/utils/transforms.py:15-29) mirrors b in x and
  * swaps the joints of each flip pair; shift != 0 applies the TEST.SHIFT_HEATMAP column shift (:361-363).

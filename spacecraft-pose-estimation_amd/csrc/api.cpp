@@ -40,6 +40,49 @@ extern "C" int32_t scpose_crop_warp_roi(const uint8_t* windows, const int64_t* o
                           static_cast<hipStream_t>(stream), roi_xywh);
 }
 
+static int32_t events_shape_ok(int32_t f, int32_t h, int32_t w) {
+  SCP_REQUIRE(f >= 0, "events: F=%d", f);
+  SCP_REQUIRE(h > 0 && w > 0 && h <= 32767 && w <= 32767 && w <= events_max_width() && (int64_t)h * w <= (1 << 24),
+              "events: frame %dx%d (HxW) not supported: 1..32767 each, W <= %d, H*W <= 2^24", h, w, events_max_width());
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_events_workspace_bytes(int32_t n_frames, int32_t h, int32_t w, size_t* bytes) {
+  SCP_REQUIRE(bytes, "events_workspace_bytes: null argument");
+  const int32_t rc = events_shape_ok(n_frames, h, w);
+  if (rc != SCPOSE_OK) return rc;
+  *bytes = (size_t)n_frames * h * w;      // the gray plane the undistortion pass samples
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_events_frame_bounds(const int64_t* t, int64_t n_events, const double* starts, int32_t n_frames,
+                                              int64_t* bounds, void* stream) {
+  SCP_REQUIRE(n_frames >= 0 && n_events >= 0, "events_frame_bounds: F=%d n_events=%lld", n_frames, (long long)n_events);
+  if (n_frames == 0) return SCPOSE_OK;
+  SCP_REQUIRE(starts && bounds && (t || n_events == 0), "events_frame_bounds: null argument");
+  return events_frame_bounds_launch(t, n_events, starts, n_frames, bounds, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t scpose_events_render(const int32_t* x, const int32_t* y, const void* p, int32_t p_itemsize,
+                                        const int64_t* bounds, int32_t n_frames, int32_t h, int32_t w, int32_t full_scale,
+                                        int32_t fold_polarity, const uint8_t* gray_lut, const double* K, const double* dist,
+                                        uint8_t* frames, uint8_t* distorted, void* workspace, size_t workspace_bytes,
+                                        void* stream) {
+  // argument errors are reported before the F == 0 return, so that they can be checked without a device
+  const int32_t rc = events_shape_ok(n_frames, h, w);
+  if (rc != SCPOSE_OK) return rc;
+  SCP_REQUIRE(full_scale >= 1 && full_scale <= 127, "events_render: full_scale=%d (1..127)", full_scale);
+  SCP_REQUIRE(fold_polarity || p_itemsize == 1 || p_itemsize == 4, "events_render: p_itemsize=%d (1: int8, 4: int32)", p_itemsize);
+  SCP_REQUIRE((K == nullptr) == (dist == nullptr), "events_render: give K and dist together, or neither (no undistortion)");
+  if (n_frames == 0) return SCPOSE_OK;
+  SCP_REQUIRE(x && y && bounds && gray_lut && frames && (fold_polarity || p), "events_render: null argument");
+  SCP_REQUIRE(!K || (workspace && workspace_bytes >= (size_t)n_frames * h * w),
+              "events_render: undistortion needs a workspace of scpose_events_workspace_bytes() = %zu bytes (got %zu)",
+              (size_t)n_frames * h * w, workspace ? workspace_bytes : (size_t)0);
+  return events_render_launch(x, y, p, p_itemsize, bounds, n_frames, h, w, full_scale, fold_polarity, gray_lut, K, dist, frames,
+                              distorted, static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
 extern "C" int32_t scpose_flip_merge(const float* a, const float* b, const int32_t* perm, int32_t n, int32_t j,
                                      int32_t h, int32_t w, int32_t shift, float* out, void* stream) {
   if (n == 0) return SCPOSE_OK;

@@ -242,6 +242,12 @@ int32_t fuse_sum_launch(const void* const* terms, const int32_t* shifts, int nte
                         int H, int W, int dtype, void* out, hipStream_t stream);
 int32_t crop_warp_launch(const uint8_t* frames, const int64_t* offsets, const int32_t* hw, const double* minv,
                          int N, int oh, int ow, int swap_rb, uint8_t* out, hipStream_t stream, const int32_t* roi = nullptr);
+// events.hip: event stream -> event frames (v2e/convert_aedats.py: e2v.py's renderer + cv2.undistort)
+int events_max_width();       // widest frame whose single row of int32 counters fits the LDS band
+int32_t events_frame_bounds_launch(const int64_t* t, int64_t n, const double* starts, int F, int64_t* bounds, hipStream_t stream);
+int32_t events_render_launch(const int32_t* x, const int32_t* y, const void* p, int p_bytes, const int64_t* bounds, int F,
+                             int H, int W, int fs, int fold, const uint8_t* lut, const double* K, const double* dist,
+                             uint8_t* frames, uint8_t* distorted, uint8_t* workspace, hipStream_t stream);
 int32_t head_gather_launch(const void* taps, const float* bias, const float* prev, int N, int J, int H, int W,
                            int K, int S, int dtype, float* out, hipStream_t stream);
 int32_t heatmap_accumulate_launch(float* acc, const float* x, float div, size_t count, hipStream_t stream);

@@ -13,6 +13,7 @@
 // One thread per output pixel; the 3 channels of a tap are 3 adjacent bytes; output is the uint8
 // NHWC tensor the stem kernel consumes (its ToTensor/Normalize is fused there).
 #include "common.h"
+#include "bilinear_fixed.h"
 
 #pragma clang fp contract(off)
 
@@ -37,17 +38,10 @@ __global__ __launch_bounds__(256) void crop_warp_kernel(const uint8_t* __restric
     // warp can touch instead of 1920 x 1200 x 3 bytes per frame); coordinates, weights and the frame border stay those of the whole frame
     const int rx = roi ? roi[4 * n] : 0, ry = roi ? roi[4 * n + 1] : 0, rw = roi ? roi[4 * n + 2] : sw, rh = roi ? roi[4 * n + 3] : sh;
     const double xs = (double)x, ys = (double)y;
-    auto sat_int = [](double v) -> long long {      // cv::saturate_cast<int>(double): cvRound + clamp to int32
-      v = rint(v);
-      return (long long)(v < -2147483648.0 ? -2147483648.0 : (v > 2147483647.0 ? 2147483647.0 : v));
-    };
-    const long long X = (sat_int((m[1] * ys + m[2]) * 1024.0) + 16 + sat_int(m[0] * xs * 1024.0)) >> 5;
-    const long long Y = (sat_int((m[4] * ys + m[5]) * 1024.0) + 16 + sat_int(m[3] * xs * 1024.0)) >> 5;
-    long long x0 = X >> 5, y0 = Y >> 5;
-    x0 = x0 < -32768 ? -32768 : (x0 > 32767 ? 32767 : x0);      // saturate_cast<short>
-    y0 = y0 < -32768 ? -32768 : (y0 > 32767 ? 32767 : y0);
-    const int a = (int)(X & 31), b = (int)(Y & 31);
-    const int w00 = (32 - a) * (32 - b) * 32, w01 = a * (32 - b) * 32, w10 = (32 - a) * b * 32, w11 = a * b * 32;
+    const long long X = (sat_round_int32((m[1] * ys + m[2]) * 1024.0) + 16 + sat_round_int32(m[0] * xs * 1024.0)) >> 5;
+    const long long Y = (sat_round_int32((m[4] * ys + m[5]) * 1024.0) + 16 + sat_round_int32(m[3] * xs * 1024.0)) >> 5;
+    const long long x0 = sat_int16(X >> 5), y0 = sat_int16(Y >> 5);
+    const BilinearTap bil((int)(X & 31), (int)(Y & 31));      // bilinear_fixed.h: the tap shared with events.hip
     uint8_t res[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -55,8 +49,7 @@ __global__ __launch_bounds__(256) void crop_warp_kernel(const uint8_t* __restric
         const bool ok = yy >= 0 && yy < sh && xx >= 0 && xx < sw && yy >= ry && yy < ry + rh && xx >= rx && xx < rx + rw;
         return ok ? (int)src[((size_t)(yy - ry) * rw + (size_t)(xx - rx)) * 3 + c] : 0;
       };
-      const int v = (tap(y0, x0) * w00 + tap(y0, x0 + 1) * w01 + tap(y0 + 1, x0) * w10 + tap(y0 + 1, x0 + 1) * w11 + 16384) >> 15;
-      res[c] = (uint8_t)(v > 255 ? 255 : v);
+      res[c] = bil(tap(y0, x0), tap(y0, x0 + 1), tap(y0 + 1, x0), tap(y0 + 1, x0 + 1));
     }
     uint8_t* o = out + gid * 3;
     o[0] = swap_rb ? res[2] : res[0];

@@ -1,0 +1,108 @@
+"""Event stream -> event frames: the host side of stage 0 of the reference's event pipeline.
+
+The reference's entry script first runs v2e/convert_aedats.py: `e2v.py --dvs_exposure duration 10000 --dvs_vid_full_scale 2`
+on every scene's events.csv (t, x, y, p per line) histograms the events of each 10 000-tick window into a frame
+(v2e/v2ecore/renderer.py: render_events_to_frames), writes event-frames-distorted/<t>.bmp, and cv2.undistort turns every frame
+into event-frames/<t>.bmp.  Here the histogram, the gray mapping and the undistortion are HIP kernels (csrc/events.hip,
+ops.render_events); this module holds what stays on the host: the frame schedule (a handful of float64 additions), the CSV
+reader and the scene driver that the CLI v2e/convert_aedats.py calls."""
+import os
+
+import numpy as np
+
+MAX_EXACT_TICK = 2 ** 53      # int64 ticks are compared as float64 (as the reference's searchsorted does): exact below 2^53
+
+
+def gray_table(full_scale):
+    """uint8 (2 * fs + 1,): the gray value of the clipped count c = -fs ... fs, the reference's
+    (img * 255).astype(np.uint8) with img = (c + fs) / float(2 * fs) (renderer.py: normalize_frame), float64, truncated.
+    fs = 2: 0, 63, 127, 191, 255."""
+    fs = int(full_scale)
+    if fs < 1:
+        raise ValueError("full_scale must be >= 1 (got %d)" % fs)
+    c = np.arange(-fs, fs + 1, dtype=np.float64)
+    return (((c + fs) / float(fs * 2)) * 255).astype(np.uint8)
+
+
+def frame_schedule(t_first, t_before_last, t_last, interval, max_frames=None):
+    """The frames the reference's renderer writes for a time-sorted stream (DURATION mode), from three of its stamps:
+    t_first = t[0], t_before_last = t[n - 2], t_last = t[n - 1].  Returns (starts float64 (F + 1,), names list of F str).
+
+    Frame k takes the events [searchsorted(t, starts[k], 'left'), searchsorted(t, starts[k + 1], 'right')): an event exactly on
+    a boundary is in both neighbouring frames.  starts[0] = t[0] and starts[k + 1] = starts[k] + interval by REPEATED float64
+    addition (not t0 + k * interval: they differ for non-integer intervals); the interval itself is 1 / (1 / interval) as the
+    renderer derives it from its frame rate.  As soon as a frame's end reaches n - 1 the renderer clamps it there and stops
+    without writing: the last event of a stream is never drawn and the last, partial frame never written.  A frame is
+    therefore written exactly while t[n - 2] > starts[k + 1].  Its name is '{:.0f}'.format(starts[k + 1] + interval / 2): the
+    start time is advanced before the mid-time is taken."""
+    interval = float(interval)
+    if not interval > 0.0:
+        raise ValueError("interval must be positive (got %r)" % interval)
+    if max(abs(int(t_first)), abs(int(t_last))) >= MAX_EXACT_TICK:
+        raise ValueError("time stamps beyond 2^53 ticks cannot be compared exactly as float64")
+    if not int(t_first) <= int(t_before_last) <= int(t_last):
+        raise ValueError("the event stream must be sorted by time")
+    step = 1.0 / (1.0 / interval)
+    start = np.float64(np.int64(t_first))
+    starts, names = [start], []
+    while max_frames is None or len(names) < max_frames:
+        nxt = start + step
+        if not np.int64(t_before_last) > nxt:
+            break
+        start = nxt
+        starts.append(start)
+        names.append("{:.0f}".format(start + step / 2))
+        if len(names) > 50000000:
+            raise ValueError("more than 5e7 frames: interval %r is too small for this stream" % interval)
+    return np.asarray(starts, dtype=np.float64), names
+
+
+def read_events_csv(path, delim_whitespace=False, swap_xy=False, microseconds_timestamp=False, milliseconds_timestamp=False):
+    """events.csv -> (t, x, y, p) int64 arrays the way v2e/e2v.py reads it: no header, '#' comments, columns t, x, y, p
+    (t, y, x, p with swap_xy), everything cast to int64 (fractions truncated), and under the two time-stamp flags the
+    in-place division of the int64 stamps by 1e6 / 1e3, which truncates toward zero again."""
+    import pandas as pd
+    names = ["t", "y", "x", "p"] if swap_xy else ["t", "x", "y", "p"]
+    df = pd.read_csv(path, header=None, comment="#", sep=r"\s+" if delim_whitespace else ",", names=names)
+    ev = df[["t", "x", "y", "p"]].values.astype(np.int64)
+    if microseconds_timestamp:
+        ev[:, 0] = ev[:, 0] / 1000000.0
+    elif milliseconds_timestamp:
+        ev[:, 0] = ev[:, 0] / 1000.0
+    return ev[:, 0].copy(), ev[:, 1].copy(), ev[:, 2].copy(), ev[:, 3].copy()
+
+
+def write_bmp(path, frame):
+    """HxWx3 uint8 -> 24-bit BMP.  The three channels of an event frame are equal, so channel order is not an issue."""
+    from PIL import Image
+    Image.fromarray(np.ascontiguousarray(frame), "RGB").save(path, format="BMP")
+
+
+def render_scene(scene_dir, hw, K=None, dist=None, interval=10000.0, full_scale=2, write_distorted=True, device=None,
+                 chunk_frames=256, **csv_flags):
+    """scene_dir/events.csv -> scene_dir/event-frames/<t>.bmp (undistorted when K / dist are given) and, with
+    write_distorted, scene_dir/event-frames-distorted/<t>.bmp: the directory contract of the reference's convert_aedats.py.
+    The stream is uploaded once and rendered on the device (ops.render_events); frames come back chunk_frames at a time.
+    Returns the list of frame names."""
+    import torch
+    from . import ops
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    t, x, y, p = read_events_csv(os.path.join(scene_dir, "events.csv"), **csv_flags)
+    out_dir = os.path.join(scene_dir, "event-frames"); dis_dir = os.path.join(scene_dir, "event-frames-distorted")
+    os.makedirs(out_dir, exist_ok=True)
+    if write_distorted:
+        os.makedirs(dis_dir, exist_ok=True)
+    frames, names = ops.render_events(torch.from_numpy(t).to(dev), torch.from_numpy(x.astype(np.int32)).to(dev),
+                                      torch.from_numpy(y.astype(np.int32)).to(dev), None, hw, interval=interval,
+                                      full_scale=full_scale, fold_polarity=True, K=K, dist=dist,
+                                      want_distorted=write_distorted)
+    h, w = int(hw[0]), int(hw[1])
+    und = frames["flat"].view(-1, h, w, 3)
+    for k0 in range(0, len(names), chunk_frames):
+        host = und[k0:k0 + chunk_frames].cpu().numpy()
+        hdis = frames["distorted"][k0:k0 + chunk_frames].cpu().numpy() if write_distorted else None
+        for i, name in enumerate(names[k0:k0 + chunk_frames]):
+            write_bmp(os.path.join(out_dir, name + ".bmp"), host[i])
+            if write_distorted:
+                write_bmp(os.path.join(dis_dir, name + ".bmp"), hdis[i])
+    return names

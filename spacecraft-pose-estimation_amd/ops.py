@@ -185,6 +185,60 @@ def pack_frames(frames):
             "hw": torch.tensor(hw, dtype=torch.int32).reshape(-1, 2)}
 
 
+def render_events(t, x, y, p, hw, interval=10000.0, full_scale=2, fold_polarity=True, K=None, dist=None, max_frames=None,
+                  want_distorted=False):
+    """Event stream -> event frames on the device: the reference's stage 0 (v2e/convert_aedats.py = e2v.py's renderer in DURATION
+    mode + cv2.undistort) without a file.  t int64 ticks (time-sorted, not checked), x, y int32, p int8 / int32 (ON is p == 1;
+    may be None with fold_polarity, which counts every event +1 as e2v.py does): device tensors of one length.  hw = (H, W).
+    K (3x3) and dist [k1, k2, p1, p2, k3] (arrays or tensors) undistort every frame; both None: frames stay distorted.
+    Returns (frames_dict, names): frames_dict in pack_frames() form with "flat" on the device -- F x H x W x 3 uint8 back to
+    back, accepted as is by crop_warp -- plus "distorted" (F, H, W, 3) with want_distorted; names = the reference's file stems
+    (event_render.frame_schedule).  Three stamps (t[0], t[n-2], t[n-1]) are read back for the schedule: one small sync."""
+    from . import event_render as er
+    if p is None and not fold_polarity:
+        raise ValueError("render_events: fold_polarity=False needs the polarity column")
+    _need_cuda(t, x, y, p)
+    n = int(t.numel())
+    if t.dtype != torch.int64 or x.dtype != torch.int32 or y.dtype != torch.int32 or x.numel() != n or y.numel() != n:
+        raise ValueError("render_events: t must be int64, x and y int32, all of one length")
+    if p is not None and (p.dtype not in (torch.int8, torch.int32) or p.numel() != n):
+        raise ValueError("render_events: p must be int8 or int32 of the stream's length")
+    if (K is None) != (dist is None):
+        raise ValueError("render_events: give K and dist together, or neither")
+    t, x, y = t.contiguous(), x.contiguous(), y.contiguous()
+    p = p.contiguous() if p is not None else None
+    dev = t.device
+    h, w = int(hw[0]), int(hw[1])
+    lut = er.gray_table(full_scale)
+    if n >= 2:
+        first, before_last, last = t[torch.tensor([0, n - 2, n - 1], device=dev)].tolist()
+        starts, names = er.frame_schedule(first, before_last, last, interval, max_frames)
+    else:
+        starts, names = np.zeros(1), []
+    f = len(names)
+    lib = nat.lib()
+    ws = c_size_t()
+    nat.check(lib.scpose_events_workspace_bytes(f, h, w, ctypes.byref(ws)), "events_workspace_bytes")
+    frames = torch.empty((f, h, w, 3), dtype=torch.uint8, device=dev)
+    out = {"flat": frames.view(-1), "offsets": torch.arange(f, dtype=torch.int64) * (h * w * 3),
+           "hw": torch.tensor([[h, w]] * f, dtype=torch.int32).reshape(-1, 2)}
+    distorted = torch.empty((f, h, w, 3), dtype=torch.uint8, device=dev) if want_distorted else None
+    if want_distorted:
+        out["distorted"] = distorted
+    with torch.cuda.device(dev):
+        starts_d = torch.from_numpy(starts).to(dev)
+        bounds = torch.empty((f, 2), dtype=torch.int64, device=dev)
+        lut_d = torch.from_numpy(lut).to(dev)
+        k_d = torch.as_tensor(np.asarray(K.cpu() if torch.is_tensor(K) else K, dtype=np.float64).reshape(3, 3)).to(dev) if K is not None else None
+        d_d = torch.as_tensor(np.asarray(dist.cpu() if torch.is_tensor(dist) else dist, dtype=np.float64).reshape(5)).to(dev) if dist is not None else None
+        work = torch.empty(ws.value if K is not None else 0, dtype=torch.uint8, device=dev)
+        nat.check(lib.scpose_events_frame_bounds(_ptr(t), n, _ptr(starts_d), f, _ptr(bounds), _stream()), "events_frame_bounds")
+        nat.check(lib.scpose_events_render(_ptr(x), _ptr(y), _ptr(p), p.element_size() if p is not None else 0, _ptr(bounds), f, h, w,
+                                           int(full_scale), int(bool(fold_polarity)), _ptr(lut_d), _ptr(k_d), _ptr(d_d), _ptr(frames),
+                                           _ptr(distorted), _ptr(work), work.numel(), _stream()), "events_render")
+    return out, names
+
+
 def warp_window(trans, out_wh, frame_hw):
     """[x0, y0, w, h]: a window of the frame that contains every pixel crop_warp reads for this affine (host side, NumPy).  The
     corners of the output grid go through the inverse map exactly as the kernel derives it; the fixed-point coordinates deviate
