@@ -285,6 +285,36 @@ int32_t scpose_events_render(const int32_t* x, const int32_t* y, const void* p, 
                              const uint8_t* gray_lut, const double* K, const double* dist, uint8_t* frames,
                              uint8_t* distorted, void* workspace, size_t workspace_bytes, void* stream);
 
+/* (ABI 7, additive) The other two exposure modes of the reference's renderer (`e2v.py --dvs_exposure count N` and
+ * `--dvs_exposure area_count M D`): they produce the bounds array scpose_events_render takes, whose histogram, clip and gray
+ * table are unchanged.  n_events is the length of the stream; a frame is written only while its end is < n_events - 1.
+ *
+ * scpose_events_count_frames / _count_bounds: COUNT N (N >= 1), frame k = [kN, (k+1)N); F = (n_events - 2) / N frames
+ * (0 below 2 events), known on the host.  _count_bounds writes the first n_frames <= F of them.
+ *
+ * scpose_events_area_bounds: AREA_COUNT M D (M >= 2, D >= 1).  Event i belongs to area (x // D, y // D) of the
+ * (1 + w // D) x (1 + h // D) grid, floor division and Python's negative wraparound (x in [-nw * D, nw * D), y likewise).  A
+ * frame starts at s with every area counter at zero and ends at the first e >= s whose area has received M events in [s, e];
+ * it is [s, e) and e opens the next frame.  Computed as a suffix minimum over a stable sort of (area, index) and a log-depth
+ * chain extraction (csrc/events_exposure.hip): no per-frame serial step, no global atomic, bitwise deterministic.
+ *   x, y          device i32 n_events; n_events <= 2^31 - 1
+ *   bounds        device i64 capacity x 2; capacity >= (n_events - 2) / (M - 1), the most frames a stream can hold
+ *   count_status  device i64 [2] <- [F, status]: status 0 ok, 1 a coordinate off the area grid (the reference raises
+ *                 IndexError there; F = 0 and nothing is written), 2 internal capacity error (F = 0)
+ *   workspace     caller-owned, scpose_events_area_bounds_workspace_bytes(n_events, M, D, h, w)
+ * The frame count is only known on the device: read count_status back before sizing the frames of scpose_events_render.
+ *
+ * scpose_events_bounds_midpoints: mids[k] = (t[begin_k] + t[end_k]) / 2 (an int64 sum, then float64): the reference's frame
+ * time in both modes, whose '{:.0f}' is the frame's file stem.  t device i64, bounds device i64 n_frames x 2, mids device f64. */
+int32_t scpose_events_count_frames(int64_t n_events, int64_t count, int64_t* n_frames);
+int32_t scpose_events_count_bounds(int64_t n_events, int64_t count, int64_t n_frames, int64_t* bounds, void* stream);
+int32_t scpose_events_area_bounds_workspace_bytes(int64_t n_events, int64_t area_count, int32_t area_dimension, int32_t h,
+                                                  int32_t w, size_t* bytes);
+int32_t scpose_events_area_bounds(const int32_t* x, const int32_t* y, int64_t n_events, int64_t area_count,
+                                  int32_t area_dimension, int32_t h, int32_t w, int64_t* bounds, int64_t capacity,
+                                  int64_t* count_status, void* workspace, size_t workspace_bytes, void* stream);
+int32_t scpose_events_bounds_midpoints(const int64_t* t, const int64_t* bounds, int64_t n_frames, double* mids, void* stream);
+
 /* Flip test (cfg.TEST.FLIP_TEST, lib/core/function.py:347-366): out = (a + flip_back(b)) * 0.5 where b
  * is the forward of the x-flipped input; flip_back (lib/utils/transforms.py:15-29) mirrors b in x and
  * swaps the joints of each flip pair; shift != 0 applies the TEST.SHIFT_HEATMAP column shift (:361-363).

@@ -87,6 +87,12 @@ SYMBOLS = {
     "scpose_events_frame_bounds": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p]),
     "scpose_events_render": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "scpose_events_count_frames": (c_int32, [c_int64, c_int64, POINTER(c_int64)]),
+    "scpose_events_count_bounds": (c_int32, [c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    "scpose_events_area_bounds_workspace_bytes": (c_int32, [c_int64, c_int64, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
+    "scpose_events_area_bounds": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p, c_int64,
+                                            c_void_p, c_void_p, c_size_t, c_void_p]),
+    "scpose_events_bounds_midpoints": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "scpose_heatmap_accumulate": (c_int32, [c_void_p, c_void_p, c_float, c_int64, c_void_p]),
     "scpose_flip_merge": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
                                     c_void_p]),

@@ -83,6 +83,70 @@ extern "C" int32_t scpose_events_render(const int32_t* x, const int32_t* y, cons
                               distorted, static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
 }
 
+static const int64_t kMaxExposureEvents = 2147483647;      // indices are int32 inside the AREA_COUNT kernels
+
+extern "C" int32_t scpose_events_count_frames(int64_t n_events, int64_t count, int64_t* n_frames) {
+  SCP_REQUIRE(n_frames, "events_count_frames: null argument");
+  SCP_REQUIRE(count >= 1, "events_count_frames: count=%lld: COUNT exposure needs at least 1 event per frame", (long long)count);
+  SCP_REQUIRE(n_events >= 0, "events_count_frames: n_events=%lld", (long long)n_events);
+  *n_frames = n_events >= 2 ? (n_events - 2) / count : 0;   // frame k is written while (k + 1) * count < n - 1
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_events_count_bounds(int64_t n_events, int64_t count, int64_t n_frames, int64_t* bounds, void* stream) {
+  int64_t f = 0;
+  const int32_t rc = scpose_events_count_frames(n_events, count, &f);
+  if (rc != SCPOSE_OK) return rc;
+  SCP_REQUIRE(n_frames >= 0 && n_frames <= f, "events_count_bounds: n_frames=%lld, the stream holds %lld COUNT frames",
+              (long long)n_frames, (long long)f);
+  if (n_frames == 0) return SCPOSE_OK;
+  SCP_REQUIRE(bounds, "events_count_bounds: null argument");
+  return events_count_bounds_launch(count, n_frames, bounds, static_cast<hipStream_t>(stream));
+}
+
+static int32_t area_args_ok(int64_t n, int64_t M, int32_t D, int32_t h, int32_t w) {
+  const int32_t rc = events_shape_ok(0, h, w);
+  if (rc != SCPOSE_OK) return rc;
+  SCP_REQUIRE(n >= 0 && n <= kMaxExposureEvents, "events_area_bounds: n_events=%lld (0 .. 2^31 - 1)", (long long)n);
+  SCP_REQUIRE(M >= 2, "events_area_bounds: area_count=%lld: an area must receive at least 2 events (the reference never ends "
+              "a frame below that)", (long long)M);
+  SCP_REQUIRE(D >= 1, "events_area_bounds: area_dimension=%d (>= 1)", D);
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_events_area_bounds_workspace_bytes(int64_t n_events, int64_t area_count, int32_t area_dimension, int32_t h,
+                                                            int32_t w, size_t* bytes) {
+  SCP_REQUIRE(bytes, "events_area_bounds_workspace_bytes: null argument");
+  const int32_t rc = area_args_ok(n_events, area_count, area_dimension, h, w);
+  if (rc != SCPOSE_OK) return rc;
+  *bytes = events_area_workspace_bytes(n_events, area_count, area_dimension, h, w);
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_events_area_bounds(const int32_t* x, const int32_t* y, int64_t n_events, int64_t area_count,
+                                             int32_t area_dimension, int32_t h, int32_t w, int64_t* bounds, int64_t capacity,
+                                             int64_t* count_status, void* workspace, size_t workspace_bytes, void* stream) {
+  const int32_t rc = area_args_ok(n_events, area_count, area_dimension, h, w);
+  if (rc != SCPOSE_OK) return rc;
+  const int64_t fcap = n_events >= 2 ? (n_events - 2) / (area_count - 1) : 0;
+  SCP_REQUIRE(capacity >= fcap, "events_area_bounds: capacity=%lld < (n_events - 2) / (area_count - 1) = %lld",
+              (long long)capacity, (long long)fcap);
+  const size_t need = events_area_workspace_bytes(n_events, area_count, area_dimension, h, w);
+  SCP_REQUIRE(workspace && workspace_bytes >= need, "events_area_bounds: workspace of %zu bytes needed (got %zu)", need,
+              workspace ? workspace_bytes : (size_t)0);
+  SCP_REQUIRE(count_status && (bounds || fcap == 0) && ((x && y) || n_events == 0), "events_area_bounds: null argument");
+  return events_area_bounds_launch(x, y, n_events, area_count, area_dimension, h, w, bounds, capacity, count_status,
+                                   static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t scpose_events_bounds_midpoints(const int64_t* t, const int64_t* bounds, int64_t n_frames, double* mids,
+                                                  void* stream) {
+  SCP_REQUIRE(n_frames >= 0, "events_bounds_midpoints: n_frames=%lld", (long long)n_frames);
+  if (n_frames == 0) return SCPOSE_OK;
+  SCP_REQUIRE(t && bounds && mids, "events_bounds_midpoints: null argument");
+  return events_bounds_midpoints_launch(t, bounds, n_frames, mids, static_cast<hipStream_t>(stream));
+}
+
 extern "C" int32_t scpose_flip_merge(const float* a, const float* b, const int32_t* perm, int32_t n, int32_t j,
                                      int32_t h, int32_t w, int32_t shift, float* out, void* stream) {
   if (n == 0) return SCPOSE_OK;

@@ -248,6 +248,12 @@ int32_t events_frame_bounds_launch(const int64_t* t, int64_t n, const double* st
 int32_t events_render_launch(const int32_t* x, const int32_t* y, const void* p, int p_bytes, const int64_t* bounds, int F,
                              int H, int W, int fs, int fold, const uint8_t* lut, const double* K, const double* dist,
                              uint8_t* frames, uint8_t* distorted, uint8_t* workspace, hipStream_t stream);
+// events_exposure.hip: the frame bounds of the COUNT and AREA_COUNT exposure modes
+size_t events_area_workspace_bytes(int64_t n, int64_t M, int D, int h, int w);
+int32_t events_area_bounds_launch(const int32_t* x, const int32_t* y, int64_t n, int64_t M, int D, int h, int w, int64_t* bounds,
+                                  int64_t capacity, int64_t* count_status, uint8_t* workspace, hipStream_t stream);
+int32_t events_count_bounds_launch(int64_t N, int64_t F, int64_t* bounds, hipStream_t stream);
+int32_t events_bounds_midpoints_launch(const int64_t* t, const int64_t* bounds, int64_t F, double* mids, hipStream_t stream);
 int32_t head_gather_launch(const void* taps, const float* bias, const float* prev, int N, int J, int H, int W,
                            int K, int S, int dtype, float* out, hipStream_t stream);
 int32_t heatmap_accumulate_launch(float* acc, const float* x, float div, size_t count, hipStream_t stream);

@@ -78,11 +78,71 @@ def write_bmp(path, frame):
     Image.fromarray(np.ascontiguousarray(frame), "RGB").save(path, format="BMP")
 
 
+EXPOSURE_MODES = ("duration", "count", "area_count")
+
+
+def parse_dvs_exposure(dvs_exposure):
+    """e2v.py's --dvs_exposure tokens -> (mode, value, area_dimension), checked as v2ecore/v2e_args.py:
+    v2e_check_dvs_exposure_args does: the mode name is case-insensitive; duration and count take exactly one number (float()),
+    area_count exactly two (int(), so '500.5' is an error); area_dimension is None outside area_count.  ValueError otherwise."""
+    if not dvs_exposure:
+        raise ValueError("--dvs_exposure needs a mode: duration, count or area_count")
+    mode = str(dvs_exposure[0]).lower()
+    if mode not in EXPOSURE_MODES:
+        raise ValueError("unknown exposure mode %r: duration, count or area_count" % (dvs_exposure[0],))
+    if mode == "area_count" and len(dvs_exposure) != 3:
+        raise ValueError("area_count needs three parameters: 'area_count M D'; the frame ends when any D x D area has "
+                         "received M events")
+    if mode != "area_count" and len(dvs_exposure) != 2:
+        raise ValueError("duration or count needs two parameters, e.g. 'duration 10000' or 'count 3000'")
+    if mode != "area_count":
+        try:
+            return mode, float(dvs_exposure[1]), None
+        except (TypeError, ValueError):
+            raise ValueError("%s takes one number (got %r)" % (mode, dvs_exposure[1]))
+    try:
+        return mode, int(dvs_exposure[1]), int(dvs_exposure[2])
+    except (TypeError, ValueError):
+        raise ValueError("area_count must be M D: M the event count, D the area dimension in pixels (integers)")
+
+
+def exposure_kwargs(mode, value, area_dimension=None):
+    """ops.render_events keyword arguments of a parsed --dvs_exposure, with the arguments the reference would loop on forever
+    (count N < 1 after truncation, area_count M < 2) and D < 1 rejected."""
+    if mode == "duration":
+        return {"exposure": "duration", "interval": float(value)}
+    if mode == "count":
+        if int(value) < 1:
+            raise ValueError("count exposure needs at least 1 event per frame (got %r)" % (value,))
+        return {"exposure": "count", "event_count": int(value)}
+    if mode == "area_count":
+        if int(value) < 2:
+            raise ValueError("area_count exposure needs M >= 2 events per area (got %r)" % (value,))
+        if area_dimension is None or int(area_dimension) < 1:
+            raise ValueError("area_count exposure needs an area dimension D >= 1 (got %r)" % (area_dimension,))
+        return {"exposure": "area_count", "area_count": int(value), "area_dimension": int(area_dimension)}
+    raise ValueError("unknown exposure mode %r" % (mode,))
+
+
+def frame_times_path(output_folder, dvs_vid):
+    """checkAddSuffix(join(output_folder, dvs_vid), '-frame_times.txt') of the reference's renderer."""
+    fn = os.path.join(output_folder, dvs_vid)
+    suffix = "-frame_times.txt"
+    return fn if fn.endswith(suffix) else os.path.splitext(fn)[0] + suffix
+
+
+def frame_times_text(dvs_vid, times):
+    """The reference's frame-times file: a two-line header, then '{k}\\t{t:10.6f}' per written frame."""
+    return "# frame times for {}\n# frame# time(s)\n".format(dvs_vid) + "".join(
+        "{}\t{:10.6f}\n".format(k, float(tk)) for k, tk in enumerate(times))
+
+
 def render_scene(scene_dir, hw, K=None, dist=None, interval=10000.0, full_scale=2, write_distorted=True, device=None,
-                 chunk_frames=256, **csv_flags):
+                 chunk_frames=256, exposure=None, **csv_flags):
     """scene_dir/events.csv -> scene_dir/event-frames/<t>.bmp (undistorted when K / dist are given) and, with
     write_distorted, scene_dir/event-frames-distorted/<t>.bmp: the directory contract of the reference's convert_aedats.py.
     The stream is uploaded once and rendered on the device (ops.render_events); frames come back chunk_frames at a time.
+    exposure: None (DURATION over `interval`) or ops.render_events keyword arguments (exposure_kwargs) that replace it.
     Returns the list of frame names."""
     import torch
     from . import ops
@@ -92,10 +152,11 @@ def render_scene(scene_dir, hw, K=None, dist=None, interval=10000.0, full_scale=
     os.makedirs(out_dir, exist_ok=True)
     if write_distorted:
         os.makedirs(dis_dir, exist_ok=True)
+    mode = dict(exposure) if exposure is not None else {"interval": interval}
     frames, names = ops.render_events(torch.from_numpy(t).to(dev), torch.from_numpy(x.astype(np.int32)).to(dev),
-                                      torch.from_numpy(y.astype(np.int32)).to(dev), None, hw, interval=interval,
+                                      torch.from_numpy(y.astype(np.int32)).to(dev), None, hw,
                                       full_scale=full_scale, fold_polarity=True, K=K, dist=dist,
-                                      want_distorted=write_distorted)
+                                      want_distorted=write_distorted, **mode)
     h, w = int(hw[0]), int(hw[1])
     und = frames["flat"].view(-1, h, w, 3)
     for k0 in range(0, len(names), chunk_frames):

@@ -186,15 +186,31 @@ def pack_frames(frames):
 
 
 def render_events(t, x, y, p, hw, interval=10000.0, full_scale=2, fold_polarity=True, K=None, dist=None, max_frames=None,
-                  want_distorted=False):
+                  want_distorted=False, exposure="duration", event_count=None, area_count=None, area_dimension=None,
+                  want_times=False):
     """Event stream -> event frames on the device: the reference's stage 0 (v2e/convert_aedats.py = e2v.py's renderer in DURATION
     mode + cv2.undistort) without a file.  t int64 ticks (time-sorted, not checked), x, y int32, p int8 / int32 (ON is p == 1;
     may be None with fold_polarity, which counts every event +1 as e2v.py does): device tensors of one length.  hw = (H, W).
     K (3x3) and dist [k1, k2, p1, p2, k3] (arrays or tensors) undistort every frame; both None: frames stay distorted.
     Returns (frames_dict, names): frames_dict in pack_frames() form with "flat" on the device -- F x H x W x 3 uint8 back to
     back, accepted as is by crop_warp -- plus "distorted" (F, H, W, 3) with want_distorted; names = the reference's file stems
-    (event_render.frame_schedule).  Three stamps (t[0], t[n-2], t[n-1]) are read back for the schedule: one small sync."""
+    (event_render.frame_schedule).  Three stamps (t[0], t[n-2], t[n-1]) are read back for the schedule: one small sync.
+
+    exposure selects how a frame ends, as e2v.py's --dvs_exposure does (event_render.parse_dvs_exposure):
+      "duration"    every `interval` ticks (the default, above)
+      "count"       every event_count events (int(float(event_count)) >= 1): frame k = [kN, (k+1)N) of the stream
+      "area_count"  when any area_dimension x area_dimension area has received area_count events since the frame began
+                    (csrc/events_exposure.hip); a coordinate off the area grid raises ValueError
+    In both count modes the host reads back the frame count (area_count only) and one float64 per frame, the frame time
+    (t[begin] + t[end]) / 2 the stem is formatted from; never the stream.  want_times: frames_dict["times"] = those frame
+    times (float64 numpy, what the reference's frame-times file lists)."""
     from . import event_render as er
+    mode = str(exposure).lower()
+    if mode not in ("duration", "count", "area_count"):
+        raise ValueError("render_events: exposure must be 'duration', 'count' or 'area_count' (got %r)" % (exposure,))
+    if mode != "duration":
+        return _render_events_counted(t, x, y, p, hw, mode, event_count, area_count, area_dimension, full_scale, fold_polarity,
+                                      K, dist, max_frames, want_distorted, want_times)
     if p is None and not fold_polarity:
         raise ValueError("render_events: fold_polarity=False needs the polarity column")
     _need_cuda(t, x, y, p)
@@ -236,6 +252,97 @@ def render_events(t, x, y, p, hw, interval=10000.0, full_scale=2, fold_polarity=
         nat.check(lib.scpose_events_render(_ptr(x), _ptr(y), _ptr(p), p.element_size() if p is not None else 0, _ptr(bounds), f, h, w,
                                            int(full_scale), int(bool(fold_polarity)), _ptr(lut_d), _ptr(k_d), _ptr(d_d), _ptr(frames),
                                            _ptr(distorted), _ptr(work), work.numel(), _stream()), "events_render")
+    if want_times:
+        step = 1.0 / (1.0 / float(interval))
+        out["times"] = np.asarray([starts[k + 1] + step / 2 for k in range(f)], dtype=np.float64)
+    return out, names
+
+
+def _check_stream(t, x, y, p, fold_polarity, K, dist):
+    if p is None and not fold_polarity:
+        raise ValueError("render_events: fold_polarity=False needs the polarity column")
+    _need_cuda(t, x, y, p)
+    n = int(t.numel())
+    if t.dtype != torch.int64 or x.dtype != torch.int32 or y.dtype != torch.int32 or x.numel() != n or y.numel() != n:
+        raise ValueError("render_events: t must be int64, x and y int32, all of one length")
+    if p is not None and (p.dtype not in (torch.int8, torch.int32) or p.numel() != n):
+        raise ValueError("render_events: p must be int8 or int32 of the stream's length")
+    if (K is None) != (dist is None):
+        raise ValueError("render_events: give K and dist together, or neither")
+    return n
+
+
+def _render_events_counted(t, x, y, p, hw, mode, event_count, area_count, area_dimension, full_scale, fold_polarity, K, dist,
+                           max_frames, want_distorted, want_times):
+    """render_events for exposure = "count" / "area_count": the bounds come from csrc/events_exposure.hip, the frames from the
+    same scpose_events_render as the duration mode."""
+    from . import event_render as er
+    n = _check_stream(t, x, y, p, fold_polarity, K, dist)
+    t, x, y = t.contiguous(), x.contiguous(), y.contiguous()
+    p = p.contiguous() if p is not None else None
+    dev = t.device
+    h, w = int(hw[0]), int(hw[1])
+    lut = er.gray_table(full_scale)
+    lib = nat.lib()
+    with torch.cuda.device(dev):
+        if mode == "count":
+            if event_count is None:
+                raise ValueError("render_events: exposure='count' needs event_count")
+            N = int(float(event_count))
+            if N < 1:
+                raise ValueError("render_events: event_count must be >= 1 after truncation (got %r)" % (event_count,))
+            fc = c_int64()
+            nat.check(lib.scpose_events_count_frames(n, N, ctypes.byref(fc)), "events_count_frames")
+            f = fc.value if max_frames is None else min(fc.value, int(max_frames))
+            bounds = torch.empty((f, 2), dtype=torch.int64, device=dev)
+            nat.check(lib.scpose_events_count_bounds(n, N, f, _ptr(bounds), _stream()), "events_count_bounds")
+        else:
+            if area_count is None or area_dimension is None:
+                raise ValueError("render_events: exposure='area_count' needs area_count and area_dimension")
+            M, D = int(area_count), int(area_dimension)
+            if M < 2:
+                raise ValueError("render_events: area_count must be >= 2 (got %d)" % M)
+            if D < 1:
+                raise ValueError("render_events: area_dimension must be >= 1 (got %d)" % D)
+            ws = c_size_t()
+            nat.check(lib.scpose_events_area_bounds_workspace_bytes(n, M, D, h, w, ctypes.byref(ws)), "events_area_bounds_workspace_bytes")
+            cap = (n - 2) // (M - 1) if n >= 2 else 0
+            bounds = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=dev)
+            cs = torch.empty(2, dtype=torch.int64, device=dev)
+            work = torch.empty(ws.value, dtype=torch.uint8, device=dev)
+            nat.check(lib.scpose_events_area_bounds(_ptr(x), _ptr(y), n, M, D, h, w, _ptr(bounds), cap, _ptr(cs), _ptr(work), ws.value,
+                                                    _stream()), "events_area_bounds")
+            f_all, status = cs.tolist()                            # the one small read-back: [F, status]
+            del work
+            if status == 1:
+                raise ValueError("render_events: an event lies off the %d x %d area grid of area_dimension %d (x in [-%d, %d), "
+                                 "y in [-%d, %d))" % (1 + w // D, 1 + h // D, D, (1 + w // D) * D, (1 + w // D) * D,
+                                                      (1 + h // D) * D, (1 + h // D) * D))
+            if status != 0:
+                raise nat.NativeError("render_events: events_area_bounds status %d" % status)
+            f = f_all if max_frames is None else min(f_all, int(max_frames))
+            bounds = bounds[:f]
+        mids = torch.empty(f, dtype=torch.float64, device=dev)
+        nat.check(lib.scpose_events_bounds_midpoints(_ptr(t), _ptr(bounds), f, _ptr(mids), _stream()), "events_bounds_midpoints")
+        times = mids.cpu().numpy()
+        names = ["{:.0f}".format(v) for v in times.tolist()]
+        ws = c_size_t()
+        nat.check(lib.scpose_events_workspace_bytes(f, h, w, ctypes.byref(ws)), "events_workspace_bytes")
+        frames = torch.empty((f, h, w, 3), dtype=torch.uint8, device=dev)
+        out = {"flat": frames.view(-1), "offsets": torch.arange(f, dtype=torch.int64) * (h * w * 3),
+               "hw": torch.tensor([[h, w]] * f, dtype=torch.int32).reshape(-1, 2)}
+        distorted = torch.empty((f, h, w, 3), dtype=torch.uint8, device=dev) if want_distorted else None
+        if want_distorted:
+            out["distorted"] = distorted
+        lut_d = torch.from_numpy(lut).to(dev)
+        k_d = torch.as_tensor(np.asarray(K.cpu() if torch.is_tensor(K) else K, dtype=np.float64).reshape(3, 3)).to(dev) if K is not None else None
+        d_d = torch.as_tensor(np.asarray(dist.cpu() if torch.is_tensor(dist) else dist, dtype=np.float64).reshape(5)).to(dev) if dist is not None else None
+        work = torch.empty(ws.value if K is not None else 0, dtype=torch.uint8, device=dev)
+        nat.check(lib.scpose_events_render(_ptr(x), _ptr(y), _ptr(p), p.element_size() if p is not None else 0, _ptr(bounds), f, h, w,
+                                           int(full_scale), int(bool(fold_polarity)), _ptr(lut_d), _ptr(k_d), _ptr(d_d), _ptr(frames),
+                                           _ptr(distorted), _ptr(work), work.numel(), _stream()), "events_render")
+    if want_times:
+        out["times"] = times
     return out, names
 
 

@@ -1,0 +1,83 @@
+#!/usr/bin/env python3
+"""e2v: event frames from a DVS events CSV, the reference's v2e/e2v.py on the MI355X HIP path.
+
+Same arguments and defaults as the reference script.  Every frame the reference's renderer writes lands in
+    <output_folder>/event-frames/<t>.bmp        t = '{:.0f}' of the frame time; a later frame with the same stem overwrites
+                                                an earlier one, as the reference's imwrite does (frames are written in order)
+    <output_folder>/<dvs_vid stem>-frame_times.txt
+with all three exposure modes of --dvs_exposure: duration T, count N, area_count M D (event_render.parse_dvs_exposure).  The
+histogram, the gray mapping and the frame ends of the count modes run on the device (csrc/events.hip,
+csrc/events_exposure.hip).  No undistortion, as in e2v.py.  The AVI video is not written (there is no video encoder here);
+--no_preview and --avi_frame_rate are accepted and ignored."""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def e2v_args(parser):
+    parser.add_argument("--events_file", type=str, help="events CSV, one event per line: t, x, y, p (no header, '#' comments)")
+    parser.add_argument("--delim_whitespace", action="store_true", default=False,
+                        help="the CSV columns are separated by whitespace, not commas")
+    parser.add_argument("--swap_xy", action="store_true", default=False, help="the second CSV column is y and the third x")
+    parser.add_argument("--microseconds_timestamp", action="store_true", default=False,
+                        help="divide the time stamps by 1e6 (int64, truncated) before rendering")
+    parser.add_argument("--milliseconds_timestamp", action="store_true", default=False,
+                        help="divide the time stamps by 1e3 (int64, truncated) before rendering")
+    parser.add_argument("--avi_frame_rate", type=int, default=30, help="accepted and ignored: no AVI is written")
+    parser.add_argument("--dvs_vid", type=str, default="dvs-video.avi",
+                        help="name the frame-times file is derived from (<stem>-frame_times.txt); no AVI is written")
+    parser.add_argument("--dvs_vid_full_scale", type=int, default=2,
+                        help="events per pixel that map to full white")
+    parser.add_argument("--no_preview", action="store_true", default=False, help="accepted and ignored: there is no preview")
+    parser.add_argument("--dvs_exposure", nargs="+", type=str, default=["duration", "0.01"],
+                        help="Mode to finish DVS frame event integration: duration T (ticks of the time column), "
+                             "count N (N events per frame), area_count M D (the frame ends when any D x D pixel area "
+                             "has received M events)")
+    parser.add_argument("--output_folder", type=str, default=".", help="where event-frames/ and the frame-times file go")
+    parser.add_argument("--output_width", type=int, default=1280, help="frame width in pixels")
+    parser.add_argument("--output_height", type=int, default=720, help="frame height in pixels")
+    return parser
+
+
+def main(argv=None):
+    args = e2v_args(argparse.ArgumentParser(description="Event frames from an events CSV, on the device.")).parse_args(argv)
+    import numpy as np
+    import torch
+    import scpose  # noqa: F401
+    from importlib import import_module
+    er = import_module("spacecraft-pose-estimation_amd.event_render")
+    ops = import_module("spacecraft-pose-estimation_amd.ops")
+    mode, value, dim = er.parse_dvs_exposure(args.dvs_exposure)
+    kw = er.exposure_kwargs(mode, value, dim)
+    print("e2v: the AVI video (%s) is not written: no video encoder is available; frames go to %s" %
+          (args.dvs_vid, os.path.join(args.output_folder, "event-frames")), file=sys.stderr)
+    out_dir = os.path.join(args.output_folder, "event-frames")
+    os.makedirs(out_dir, exist_ok=True)
+    t, x, y, _ = er.read_events_csv(args.events_file, delim_whitespace=args.delim_whitespace, swap_xy=args.swap_xy,
+                                    microseconds_timestamp=args.microseconds_timestamp,
+                                    milliseconds_timestamp=args.milliseconds_timestamp)
+    h, w = args.output_height, args.output_width
+    times, names = [], []
+    if len(t) > 0:
+        dev = torch.device("cuda", torch.cuda.current_device())
+        frames, names = ops.render_events(torch.from_numpy(t).to(dev), torch.from_numpy(x.astype(np.int32)).to(dev),
+                                          torch.from_numpy(y.astype(np.int32)).to(dev), None, (h, w),
+                                          full_scale=args.dvs_vid_full_scale, fold_polarity=True, want_times=True, **kw)
+        times = frames["times"]
+        img = frames["flat"].view(-1, h, w, 3)
+        chunk = 256
+        for k0 in range(0, len(names), chunk):            # in frame order: a repeated stem keeps the later frame
+            host = img[k0:k0 + chunk].cpu().numpy()
+            for i, name in enumerate(names[k0:k0 + chunk]):
+                er.write_bmp(os.path.join(out_dir, name + ".bmp"), host[i])
+    with open(er.frame_times_path(args.output_folder, args.dvs_vid), "w") as f:
+        f.write(er.frame_times_text(args.dvs_vid, times))
+    print("e2v: %d frames (%s)" % (len(names), " ".join(args.dvs_exposure)))
+
+
+if __name__ == "__main__":
+    main()
