@@ -315,6 +315,37 @@ int32_t scpose_events_area_bounds(const int32_t* x, const int32_t* y, int64_t n_
                                   int64_t* count_status, void* workspace, size_t workspace_bytes, void* stream);
 int32_t scpose_events_bounds_midpoints(const int64_t* t, const int64_t* bounds, int64_t n_frames, double* mids, void* stream);
 
+/* events.csv on the device (csrc/events_csv.hip): the file's bytes -> the four columns scpose_events_frame_bounds /
+ * scpose_events_render take, rows in file order.  Replaces pd.read_csv(file, header=None, comment='#', delim_whitespace=...,
+ * names=[t, x, y, p]) + .values.astype(np.int64) of v2e/e2v.py:116-138 on the part of that reader's grammar where a row depends
+ * on its own line only; on that part the columns equal the reader's element for element.
+ *   accepted     line ends '\n', '\r\n', '\r', a last line without one; empty lines, lines of spaces / tabs and lines that start
+ *                with '#' are skipped; a '#' later in a line cuts it; exactly four fields per row, separated by ',' with spaces /
+ *                tabs around fields ignored (delim_whitespace == 0) or by runs of spaces / tabs (!= 0); a field is
+ *                [+-]? digits [. digits] or [+-]? . digits, its value the integer part (truncation toward zero, as the
+ *                reader's float64 column cast to int64 gives); t fits int64, x and y int32, p int8
+ *   unsupported  (status SCPOSE_CSV_UNSUPPORTED, n_rows = 0, column contents unspecified -- never a different answer): any other
+ *                byte outside a comment (exponents, quotes, hex, nan, inf), an empty field, fewer or more than four fields, a
+ *                value out of range, spaces / tabs followed by '#', a column that holds a '.' in one field and more than 15
+ *                digit characters in one field (the reader's float64 column is exact only up to 15 digits), a line whose part
+ *                before any '#' is 64 KiB or longer (one thread walks a line), and directly after
+ *                a '\r' without '\n': a row that begins with a space / tab (comma mode), a line of only spaces / tabs
+ *                (whitespace mode) -- the reader's tokenizer gives both a meaning of its own
+ *   data         device u8 n_bytes, 16-byte aligned; offsets are 64-bit throughout, files above 2^31 bytes are untested
+ *   swap_xy      != 0: the second field goes to y and the third to x
+ *   t_divisor    0: none; 1e6 / 1e3: t <- (int64)((double)t / t_divisor), the reader's --microseconds_timestamp /
+ *                --milliseconds_timestamp
+ *   t, x, y, p   device i64 / i32 / i32 / i8, capacity rows each; (n_bytes + 1) / 8 rows always suffice (a row takes 8 bytes)
+ *   count_status device i64 [2] <- [n_rows, status]: status 0 ok, SCPOSE_CSV_UNSUPPORTED, SCPOSE_CSV_CAPACITY (more rows than
+ *                capacity: n_rows = 0).  The row count is only known on the device: read count_status back once.
+ *   workspace    caller-owned, 16-byte aligned, scpose_events_csv_workspace_bytes(n_bytes)
+ * No allocation, no synchronisation; two calls on the same bytes give bitwise equal outputs. */
+enum { SCPOSE_CSV_UNSUPPORTED = 1, SCPOSE_CSV_CAPACITY = 2 };
+int32_t scpose_events_csv_workspace_bytes(int64_t n_bytes, size_t* bytes);
+int32_t scpose_events_csv_parse(const uint8_t* data, int64_t n_bytes, int32_t delim_whitespace, int32_t swap_xy, double t_divisor,
+                                int64_t* t, int32_t* x, int32_t* y, int8_t* p, int64_t capacity, int64_t* count_status,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
 /* Flip test (cfg.TEST.FLIP_TEST, lib/core/function.py:347-366): out = (a + flip_back(b)) * 0.5 where b
  * is the forward of the x-flipped input; flip_back (lib/utils/transforms.py:15-29) mirrors b in x and
  * swaps the joints of each flip pair; shift != 0 applies the TEST.SHIFT_HEATMAP column shift (:361-363).

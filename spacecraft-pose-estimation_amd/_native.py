@@ -21,6 +21,7 @@ if os.environ.get("SCPOSE_DEV") == "1":
 
 DT_BF16, DT_F16 = 0, 1
 IN_F32_NCHW, IN_U8_NHWC = 0, 1
+CSV_UNSUPPORTED, CSV_CAPACITY = 1, 2
 ABI_VERSION = 7
 
 
@@ -93,6 +94,9 @@ SYMBOLS = {
     "scpose_events_area_bounds": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p, c_int64,
                                             c_void_p, c_void_p, c_size_t, c_void_p]),
     "scpose_events_bounds_midpoints": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "scpose_events_csv_workspace_bytes": (c_int32, [c_int64, POINTER(c_size_t)]),
+    "scpose_events_csv_parse": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "scpose_heatmap_accumulate": (c_int32, [c_void_p, c_void_p, c_float, c_int64, c_void_p]),
     "scpose_flip_merge": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
                                     c_void_p]),

@@ -147,6 +147,28 @@ extern "C" int32_t scpose_events_bounds_midpoints(const int64_t* t, const int64_
   return events_bounds_midpoints_launch(t, bounds, n_frames, mids, static_cast<hipStream_t>(stream));
 }
 
+extern "C" int32_t scpose_events_csv_workspace_bytes(int64_t n_bytes, size_t* bytes) {
+  SCP_REQUIRE(bytes, "events_csv_workspace_bytes: null argument");
+  SCP_REQUIRE(n_bytes >= 0, "events_csv_workspace_bytes: n_bytes=%lld", (long long)n_bytes);
+  *bytes = events_csv_workspace_bytes(n_bytes);
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_events_csv_parse(const uint8_t* data, int64_t n_bytes, int32_t delim_whitespace, int32_t swap_xy,
+                                           double t_divisor, int64_t* t, int32_t* x, int32_t* y, int8_t* p, int64_t capacity,
+                                           int64_t* count_status, void* workspace, size_t workspace_bytes, void* stream) {
+  SCP_REQUIRE(n_bytes >= 0 && capacity >= 0, "events_csv_parse: n_bytes=%lld capacity=%lld", (long long)n_bytes, (long long)capacity);
+  SCP_REQUIRE(t_divisor >= 0.0 && t_divisor <= 1e300, "events_csv_parse: t_divisor=%g (0: none, else a positive divisor)", t_divisor);
+  SCP_REQUIRE(count_status && (data || n_bytes == 0) && ((t && x && y && p) || capacity == 0), "events_csv_parse: null argument");
+  SCP_REQUIRE((reinterpret_cast<uintptr_t>(data) & 15) == 0, "events_csv_parse: data must be 16-byte aligned");
+  SCP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "events_csv_parse: workspace must be 16-byte aligned");
+  const size_t need = events_csv_workspace_bytes(n_bytes);
+  SCP_REQUIRE(workspace && workspace_bytes >= need, "events_csv_parse: workspace of %zu bytes needed (got %zu)", need,
+              workspace ? workspace_bytes : (size_t)0);
+  return events_csv_parse_launch(data, n_bytes, delim_whitespace != 0, swap_xy != 0, t_divisor, t, x, y, p, capacity, count_status,
+                                 static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
 extern "C" int32_t scpose_flip_merge(const float* a, const float* b, const int32_t* perm, int32_t n, int32_t j,
                                      int32_t h, int32_t w, int32_t shift, float* out, void* stream) {
   if (n == 0) return SCPOSE_OK;

@@ -254,6 +254,10 @@ int32_t events_area_bounds_launch(const int32_t* x, const int32_t* y, int64_t n,
                                   int64_t capacity, int64_t* count_status, uint8_t* workspace, hipStream_t stream);
 int32_t events_count_bounds_launch(int64_t N, int64_t F, int64_t* bounds, hipStream_t stream);
 int32_t events_bounds_midpoints_launch(const int64_t* t, const int64_t* bounds, int64_t F, double* mids, hipStream_t stream);
+// events_csv.hip: events.csv text -> (t, x, y, p)
+size_t events_csv_workspace_bytes(int64_t n_bytes);
+int32_t events_csv_parse_launch(const uint8_t* data, int64_t n_bytes, int ws_mode, int swap_xy, double t_div, int64_t* t, int32_t* x,
+                                int32_t* y, int8_t* p, int64_t capacity, int64_t* count_status, uint8_t* ws, hipStream_t stream);
 int32_t head_gather_launch(const void* taps, const float* bias, const float* prev, int N, int J, int H, int W,
                            int K, int S, int dtype, float* out, hipStream_t stream);
 int32_t heatmap_accumulate_launch(float* acc, const float* x, float div, size_t count, hipStream_t stream);

@@ -3,9 +3,11 @@
 The reference's entry script first runs v2e/convert_aedats.py: `e2v.py --dvs_exposure duration 10000 --dvs_vid_full_scale 2`
 on every scene's events.csv (t, x, y, p per line) histograms the events of each 10 000-tick window into a frame
 (v2e/v2ecore/renderer.py: render_events_to_frames), writes event-frames-distorted/<t>.bmp, and cv2.undistort turns every frame
-into event-frames/<t>.bmp.  Here the histogram, the gray mapping and the undistortion are HIP kernels (csrc/events.hip,
-ops.render_events); this module holds what stays on the host: the frame schedule (a handful of float64 additions), the CSV
-reader and the scene driver that the CLI v2e/convert_aedats.py calls."""
+into event-frames/<t>.bmp.  Here the CSV text is parsed (csrc/events_csv.hip, ops.parse_events_csv) and the histogram, the gray
+mapping and the undistortion are computed (csrc/events.hip, ops.render_events) by HIP kernels; this module holds what stays on
+the host: the frame schedule (a handful of float64 additions), the pandas reader the device parser falls back to for text
+outside its grammar (read_events_csv, also the oracle of the device parser), and the scene driver that the CLI
+v2e/convert_aedats.py calls."""
 import os
 
 import numpy as np
@@ -70,6 +72,25 @@ def read_events_csv(path, delim_whitespace=False, swap_xy=False, microseconds_ti
     elif milliseconds_timestamp:
         ev[:, 0] = ev[:, 0] / 1000.0
     return ev[:, 0].copy(), ev[:, 1].copy(), ev[:, 2].copy(), ev[:, 3].copy()
+
+
+def read_events_device(path, device=None, host_csv=False, **csv_flags):
+    """events.csv -> (t int64, x int32, y int32) device tensors, the stream ops.render_events takes.  The file's bytes are
+    uploaded in one piece and parsed on the device (ops.parse_events_csv); text outside that parser's grammar
+    (ops.UnsupportedCsv) and host_csv=True go through read_events_csv and one upload per column, as every file did before:
+    the columns are the same either way."""
+    import torch
+    from . import ops
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if not host_csv:
+        try:
+            t, x, y, _ = ops.parse_events_csv(path, device=dev, **csv_flags)
+            return t, x, y
+        except ops.UnsupportedCsv:
+            pass
+    t, x, y, _ = read_events_csv(path, **csv_flags)
+    return (torch.from_numpy(t).to(dev), torch.from_numpy(x.astype(np.int32)).to(dev),
+            torch.from_numpy(y.astype(np.int32)).to(dev))
 
 
 def write_bmp(path, frame):
@@ -138,24 +159,23 @@ def frame_times_text(dvs_vid, times):
 
 
 def render_scene(scene_dir, hw, K=None, dist=None, interval=10000.0, full_scale=2, write_distorted=True, device=None,
-                 chunk_frames=256, exposure=None, **csv_flags):
+                 chunk_frames=256, exposure=None, host_csv=False, **csv_flags):
     """scene_dir/events.csv -> scene_dir/event-frames/<t>.bmp (undistorted when K / dist are given) and, with
     write_distorted, scene_dir/event-frames-distorted/<t>.bmp: the directory contract of the reference's convert_aedats.py.
-    The stream is uploaded once and rendered on the device (ops.render_events); frames come back chunk_frames at a time.
+    The file is uploaded once, parsed and rendered on the device (read_events_device, ops.render_events); frames come back
+    chunk_frames at a time.  host_csv: read the file with the pandas reader instead (the device parser's fallback).
     exposure: None (DURATION over `interval`) or ops.render_events keyword arguments (exposure_kwargs) that replace it.
     Returns the list of frame names."""
     import torch
     from . import ops
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    t, x, y, p = read_events_csv(os.path.join(scene_dir, "events.csv"), **csv_flags)
+    t, x, y = read_events_device(os.path.join(scene_dir, "events.csv"), dev, host_csv=host_csv, **csv_flags)
     out_dir = os.path.join(scene_dir, "event-frames"); dis_dir = os.path.join(scene_dir, "event-frames-distorted")
     os.makedirs(out_dir, exist_ok=True)
     if write_distorted:
         os.makedirs(dis_dir, exist_ok=True)
     mode = dict(exposure) if exposure is not None else {"interval": interval}
-    frames, names = ops.render_events(torch.from_numpy(t).to(dev), torch.from_numpy(x.astype(np.int32)).to(dev),
-                                      torch.from_numpy(y.astype(np.int32)).to(dev), None, hw,
-                                      full_scale=full_scale, fold_polarity=True, K=K, dist=dist,
+    frames, names = ops.render_events(t, x, y, None, hw, full_scale=full_scale, fold_polarity=True, K=K, dist=dist,
                                       want_distorted=write_distorted, **mode)
     h, w = int(hw[0]), int(hw[1])
     und = frames["flat"].view(-1, h, w, 3)

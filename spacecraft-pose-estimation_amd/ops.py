@@ -346,6 +346,60 @@ def _render_events_counted(t, x, y, p, hw, mode, event_count, area_count, area_d
     return out, names
 
 
+class UnsupportedCsv(ValueError):
+    """parse_events_csv: the text is outside the grammar the device reader accepts (include/scpose.h:
+    scpose_events_csv_parse).  The host reader, event_render.read_events_csv, takes the reference's whole grammar."""
+
+
+def parse_events_csv(data, delim_whitespace=False, swap_xy=False, microseconds_timestamp=False, milliseconds_timestamp=False,
+                     device=None):
+    """events.csv text -> (t int64, x int32, y int32, p int8) device tensors, rows in file order: what
+    event_render.read_events_csv gives (the reference's pandas.read_csv call of v2e/e2v.py), parsed on the device
+    (csrc/events_csv.hip), in the dtypes render_events takes.  data: a uint8 device tensor holding the file's bytes, or bytes /
+    bytearray / a path, uploaded in one piece to `device` (default: the current one).  The flags are e2v.py's.  One small
+    read-back, [n_rows, status].  Raises UnsupportedCsv when the text is outside the accepted grammar (exponents, quotes, a wrong
+    field count, a decimal column with more than 15 digits, ...: include/scpose.h lists it); the host reader is the fallback.
+    Offsets are 64-bit, but files above 2^31 bytes have not been tested."""
+    if torch.is_tensor(data):
+        _need_cuda(data)
+        if data.dtype != torch.uint8:
+            raise ValueError("parse_events_csv: the bytes must be a uint8 tensor (got %s)" % data.dtype)
+        buf = data.contiguous().view(-1)
+    else:
+        if isinstance(data, (bytes, bytearray, memoryview)):
+            host = np.frombuffer(data, dtype=np.uint8)
+        else:
+            host = np.fromfile(data, dtype=np.uint8)
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        buf = torch.from_numpy(host.copy() if not host.flags.writeable else host).to(dev)
+    if buf.data_ptr() % 16:
+        buf = buf.clone()
+    dev = buf.device
+    n = int(buf.numel())
+    div = 1000000.0 if microseconds_timestamp else (1000.0 if milliseconds_timestamp else 0.0)
+    cap = (n + 1) // 8                                          # the shortest row, '1,2,3,4' and a line end, takes 8 bytes
+    lib = nat.lib()
+    ws = c_size_t()
+    nat.check(lib.scpose_events_csv_workspace_bytes(n, ctypes.byref(ws)), "events_csv_workspace_bytes")
+    with torch.cuda.device(dev):
+        t = torch.empty(cap, dtype=torch.int64, device=dev)
+        x = torch.empty(cap, dtype=torch.int32, device=dev)
+        y = torch.empty(cap, dtype=torch.int32, device=dev)
+        p = torch.empty(cap, dtype=torch.int8, device=dev)
+        cs = torch.empty(2, dtype=torch.int64, device=dev)
+        work = torch.empty(ws.value, dtype=torch.uint8, device=dev)
+        nat.check(lib.scpose_events_csv_parse(_ptr(buf), n, int(bool(delim_whitespace)), int(bool(swap_xy)), c_double(div), _ptr(t),
+                                              _ptr(x), _ptr(y), _ptr(p), cap, _ptr(cs), _ptr(work), ws.value, _stream()),
+                  "events_csv_parse")
+        rows, status = cs.tolist()                              # the one small read-back
+        if status == nat.CSV_UNSUPPORTED:
+            raise UnsupportedCsv("parse_events_csv: the text is outside the grammar the device reader accepts")
+        if status != 0:
+            raise nat.NativeError("parse_events_csv: events_csv_parse status %d" % status)
+        # the columns were sized for the shortest possible rows: give back right-sized ones
+        return t[:rows].clone(), x[:rows].clone(), y[:rows].clone(), p[:rows].clone()
+
+
 def warp_window(trans, out_wh, frame_hw):
     """[x0, y0, w, h]: a window of the frame that contains every pixel crop_warp reads for this affine (host side, NumPy).  The
     corners of the output grid go through the inverse map exactly as the kernel derives it; the fixed-point coordinates deviate

@@ -6,12 +6,14 @@ that holds events.csv (t, x, y, p per line) it writes
     <scene>/event-frames-distorted/<t>.bmp   the events of each 10 000-tick window as a gray frame (e2v.py --dvs_exposure
                                              duration 10000 --dvs_vid_full_scale 2)
     <scene>/event-frames/<t>.bmp             the same frame after cv2.undistort with the calibration file's camera
-as 24-bit BMP files; evaluate_pipeline.py then runs on the result unchanged.  Histogram, gray mapping and undistortion run
-on the device (csrc/events.hip); a process that already holds the events can skip the files altogether with
-ops.render_events, whose output ops.crop_warp accepts as is.
+as 24-bit BMP files; evaluate_pipeline.py then runs on the result unchanged.  The CSV text is parsed on the device
+(csrc/events_csv.hip), and histogram, gray mapping and undistortion run there too (csrc/events.hip); a process that already
+holds the file's bytes or the events can skip the files altogether with ops.parse_events_csv and ops.render_events, whose
+output ops.crop_warp accepts as is.
 
 Extensions (optional): --no_distorted skips event-frames-distorted/; the CSV flags of e2v.py (--delim_whitespace, --swap_xy,
---microseconds_timestamp, --milliseconds_timestamp).  Not reproduced: the AVI video and frame-times file e2v.py also
+--microseconds_timestamp, --milliseconds_timestamp); --host_csv reads events.csv with the pandas reader, which is also what a
+file outside the device parser's grammar (an exponent, a quoted field, ...) falls back to by itself.  Not reproduced: the AVI video and frame-times file e2v.py also
 writes, AEDAT parsing (aedat_to_csv.py)."""
 import argparse
 import json
@@ -34,6 +36,7 @@ def parse_args(argv=None):
     p.add_argument("--swap_xy", action="store_true", help="the second column of events.csv is y")
     p.add_argument("--microseconds_timestamp", action="store_true", help="divide the time stamps by 1e6 as e2v.py does")
     p.add_argument("--milliseconds_timestamp", action="store_true", help="divide the time stamps by 1e3 as e2v.py does")
+    p.add_argument("--host_csv", action="store_true", help="read events.csv with the pandas reader on the host instead of the device parser")
     return p.parse_args(argv)
 
 
@@ -53,7 +56,7 @@ def main(argv=None):
             names = er.render_scene(full, (args.image_height, args.image_width), K=K, dist=dist,
                                     write_distorted=not args.no_distorted, delim_whitespace=args.delim_whitespace,
                                     swap_xy=args.swap_xy, microseconds_timestamp=args.microseconds_timestamp,
-                                    milliseconds_timestamp=args.milliseconds_timestamp)
+                                    milliseconds_timestamp=args.milliseconds_timestamp, host_csv=args.host_csv)
             print("%s: %d frames" % (scene, len(names)))
 
 

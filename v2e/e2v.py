@@ -6,9 +6,10 @@ Same arguments and defaults as the reference script.  Every frame the reference'
                                                 an earlier one, as the reference's imwrite does (frames are written in order)
     <output_folder>/<dvs_vid stem>-frame_times.txt
 with all three exposure modes of --dvs_exposure: duration T, count N, area_count M D (event_render.parse_dvs_exposure).  The
-histogram, the gray mapping and the frame ends of the count modes run on the device (csrc/events.hip,
-csrc/events_exposure.hip).  No undistortion, as in e2v.py.  The AVI video is not written (there is no video encoder here);
---no_preview and --avi_frame_rate are accepted and ignored."""
+CSV parser, the histogram, the gray mapping and the frame ends of the count modes run on the device (csrc/events_csv.hip,
+csrc/events.hip, csrc/events_exposure.hip); --host_csv (an extension) reads the file with the pandas reader instead, which is
+also the fallback for text outside the device parser's grammar.  No undistortion, as in e2v.py.  The AVI video is not written
+(there is no video encoder here); --no_preview and --avi_frame_rate are accepted and ignored."""
 import argparse
 import os
 import sys
@@ -27,6 +28,8 @@ def e2v_args(parser):
                         help="divide the time stamps by 1e6 (int64, truncated) before rendering")
     parser.add_argument("--milliseconds_timestamp", action="store_true", default=False,
                         help="divide the time stamps by 1e3 (int64, truncated) before rendering")
+    parser.add_argument("--host_csv", action="store_true", default=False,
+                        help="read the CSV with the pandas reader on the host instead of the device parser")
     parser.add_argument("--avi_frame_rate", type=int, default=30, help="accepted and ignored: no AVI is written")
     parser.add_argument("--dvs_vid", type=str, default="dvs-video.avi",
                         help="name the frame-times file is derived from (<stem>-frame_times.txt); no AVI is written")
@@ -45,7 +48,6 @@ def e2v_args(parser):
 
 def main(argv=None):
     args = e2v_args(argparse.ArgumentParser(description="Event frames from an events CSV, on the device.")).parse_args(argv)
-    import numpy as np
     import torch
     import scpose  # noqa: F401
     from importlib import import_module
@@ -57,15 +59,14 @@ def main(argv=None):
           (args.dvs_vid, os.path.join(args.output_folder, "event-frames")), file=sys.stderr)
     out_dir = os.path.join(args.output_folder, "event-frames")
     os.makedirs(out_dir, exist_ok=True)
-    t, x, y, _ = er.read_events_csv(args.events_file, delim_whitespace=args.delim_whitespace, swap_xy=args.swap_xy,
-                                    microseconds_timestamp=args.microseconds_timestamp,
+    dev = torch.device("cuda", torch.cuda.current_device())
+    t, x, y = er.read_events_device(args.events_file, dev, host_csv=args.host_csv, delim_whitespace=args.delim_whitespace,
+                                    swap_xy=args.swap_xy, microseconds_timestamp=args.microseconds_timestamp,
                                     milliseconds_timestamp=args.milliseconds_timestamp)
     h, w = args.output_height, args.output_width
     times, names = [], []
     if len(t) > 0:
-        dev = torch.device("cuda", torch.cuda.current_device())
-        frames, names = ops.render_events(torch.from_numpy(t).to(dev), torch.from_numpy(x.astype(np.int32)).to(dev),
-                                          torch.from_numpy(y.astype(np.int32)).to(dev), None, (h, w),
+        frames, names = ops.render_events(t, x, y, None, (h, w),
                                           full_scale=args.dvs_vid_full_scale, fold_polarity=True, want_times=True, **kw)
         times = frames["times"]
         img = frames["flat"].view(-1, h, w, 3)
