@@ -113,8 +113,8 @@ struct ConvLaunch {
                                   // (buffer-addressed global traffic, conv_pipe_kernel.h: dma16_buf), else 0 (64-bit
                                   // addressing).  conv_pipe: out_bytes = size of in2 (K-concatenated second input).
   unsigned long long* dbg_buf;  // development build only (SCP_DBG_BUF): per-workgroup phase cycle sums (dbg & 8), else null
-  int32_t dbg;           // development build only (SCP_DBG): ablation bits 1 skip MFMA loop, 2 skip epilogue, 4 skip input DMA;
-                         // the shipped library's kernels never read either field
+  int32_t dbg;           // development build only (SCP_DBG; the shipped library's kernels read neither field): bits 1 skip MFMA loop, 2 skip epilogue, 4 skip input DMA, 8 phase stamps
+                         // bit 32 is the one bit the shipped library honours: the host prints the m32 tile choice
   int32_t cu_share;      // host only: CUs to size the layer for (0 = the whole chip)
 };
 
@@ -125,6 +125,10 @@ struct ConvConfig {
   int th, tw;          // output tile
   int cp;              // input planes (8 channels each) per K chunk
 };
+
+// A tiling of conv_launch_m32: th x tw output tile, nseg tiles per work item, nr (16x16x32 consumers: nb16) MFMA columns per wave,
+// ps = bytes of a staged halo plane, occ = kernel family (1 / 2 workgroups per CU, 3 = producer/consumer), cp = planes per K-chunk
+struct M32Tiling { int th = 0, tw = 0, nseg = 0, nr = 0, ps = 0, occ = 0, cp = 0, nb16 = 0; };
 
 struct PackedConv {
   int cin, cout, ks, stride, dtype;
@@ -142,8 +146,8 @@ struct PackedConv {
   float* d_b1 = nullptr;
   size_t w1_bytes = 0;
   int cout_pad1 = 0;
-  // tiling chosen by conv_launch_m32 for the last (N, Ho, Wo) seen (the search is a function of those and the layer only)
-  struct TileMemo { int n = -1, ho = 0, wo = 0, th = 0, tw = 0, nseg = 0, nr = 0, ps = 0, occ = 0, cp = 0, cus = 0, nb16 = 0; };
+  // tiling chosen by conv_launch_m32 for the last (N, Ho, Wo, CUs) seen (the search is a function of those and the layer only)
+  struct TileMemo { int n = -1, ho = 0, wo = 0, cus = 0; M32Tiling t; };
   mutable TileMemo m32_memo[2];   // [0] whole chip, [1] a share of it (concurrent lanes)
   // register-weight stride-2 kernel (conv_s2r.hip): weights [k-step][cout block][k-group][row][8], bias in MFMA row order
   void* d_ws2 = nullptr;

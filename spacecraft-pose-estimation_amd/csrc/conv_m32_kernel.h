@@ -167,7 +167,7 @@ __global__ __launch_bounds__(256, OCC) void conv_m32_kernel(const ConvLaunch p) 
       const bool ok = img >= 0 && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
       // buffer addressing (p.in_bytes != 0): the slot holds a 32-bit offset, BUF_OOB for padding pixels
       if (p.in_bytes) xoff[i] = ok ? (size_t)((uint32_t)(img * p.cin_planes * HW + iy * p.W + ix) * 16u) : (size_t)BUF_OOB;
-      else xoff[i] = ok ? ((size_t)(SCP_DBG(p, 64) ? 0 : img) * p.cin_planes * HW + (size_t)(iy * p.W + ix)) * 16 : ~(size_t)0;
+      else xoff[i] = ok ? ((size_t)img * p.cin_planes * HW + (size_t)(iy * p.W + ix)) * 16 : ~(size_t)0;
     }
   };
   const buf_rsrc_t rs_in = make_buf(p.in, p.in_bytes);
@@ -273,13 +273,9 @@ __global__ __launch_bounds__(256, OCC) void conv_m32_kernel(const ConvLaunch p) 
             }
       }
       // (2) DMA burst for the next stage
-      const unsigned long long ta = now();
-      unsigned long long tb = ta, tc = ta;
       if (have_next) {
         if (nc == 0) locate_halo(nit);
-        tb = now();
         issue_x(nc, xb ^ 1);
-        tc = now();
         if (!w_resident) issue_w(nit, nc, (wc + 1) & 1);
       }
       const unsigned long long t1 = now();
@@ -471,11 +467,7 @@ __global__ __launch_bounds__(256, OCC) void conv_m32_kernel(const ConvLaunch p) 
       }
       if SCP_DBG(p, 8) {
         const unsigned long long t6 = now();
-        if SCP_DBG(p, 256) {   // finer split of the front of the stage: [zero+residual][locate][X issue][W issue][MFMA][rest]
-          tph[0] += ta - t0; tph[1] += tb - ta; tph[2] += tc - tb; tph[3] += t1 - tc; tph[4] += t2 - t1; tph[5] += t6 - t2;
-        } else {
-          tph[0] += t1 - t0; tph[1] += t2 - t1; tph[2] += t3 - t2; tph[3] += t4 - t3; tph[4] += t5 - t4; tph[5] += t6 - t5;
-        }
+        tph[0] += t1 - t0; tph[1] += t2 - t1; tph[2] += t3 - t2; tph[3] += t4 - t3; tph[4] += t5 - t4; tph[5] += t6 - t5;
       }
       xb ^= 1;
     }
