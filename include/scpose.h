@@ -179,15 +179,14 @@ int32_t scpose_hrnet_graph_destroy(scpose_hrnet_graph_t g);
 
 /* Unit-level parity hook: runs the forward up to and including the op that produces the named intermediate tensor
  * and writes it as float32 N x C x h x w (converted from the 16-bit blocked layout).  Names follow the forward of
- * pose_hrnet.py:425-460: "stem1" (:426-428), "stem2" (:429-431), "layer1" (:432), "stage<S>.<M>.out0" = y_list[0]
+ * pose_hrnet.py:425-460: "stem2" (:429-431; the stem's first tap: conv1's output never leaves the fused stem kernel), "layer1" (:432), "stage<S>.<M>.out0" = y_list[0]
  * after module M of stage S (:247-265).  Every other tensor an op writes is offered too, named by the reference module
  * path that produces it: "layer1.<b>", "transition<k>.<i>" and hops "transition<k>.<i>.<j>", block outputs
  * "stage<S>.<M>.branches.<B>.<K>" and, where a block runs as separate launches, its intermediates "<block>.conv1" (and
  * "<block>.conv2" of a Bottleneck), fuse up paths "stage<S>.<M>.fuse_layers.<i>.<j>" (before upsampling), down hops
  * "stage<S>.<M>.fuse_layers.<i>.<j>.<k>", every fuse row "stage<S>.<M>.out<i>", and the 16-bit tap map of each hrnet_cms
  * head "<head>.tapmap".  With out == NULL only *channels / *out_h / *out_w are filled (shape query). */
-int32_t scpose_hrnet_tap_names(scpose_hrnet_t h, char* buf, int32_t cap);   /* comma-separated names this handle offers ("stem1"
-                                                                              exists only when the stem runs as two layers) */
+int32_t scpose_hrnet_tap_names(scpose_hrnet_t h, char* buf, int32_t cap);   /* comma-separated names this handle offers */
 int32_t scpose_hrnet_forward_tap(scpose_hrnet_t h, const void* in, int32_t in_fmt, int32_t n, int32_t height,
                                  int32_t width, const char* tap, float* out, int32_t* channels, int32_t* out_h,
                                  int32_t* out_w, void* workspace, size_t workspace_bytes, void* stream);

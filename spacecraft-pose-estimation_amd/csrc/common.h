@@ -77,8 +77,6 @@ inline FastDiv make_fastdiv(uint32_t d) {
 // [N][C/8][H][W][8] 16-bit elements.
 struct ConvLaunch {
   const void* in;      // blocked input  N x Cin x H x W
-  const void* in2;     // optional second input tensor supplying the planes >= split_planes (K-concatenated 1x1 conv), else null
-  int32_t split_planes;
   const void* wpk;     // packed weights (see pack_conv_weights)
   const float* bias;   // f32 [n_mblk*MT] (zero padded)
   const void* res;     // optional blocked residual, shape of out
@@ -111,7 +109,7 @@ struct ConvLaunch {
   FastDiv fd_npix, fd_tw, fd_hp, fd_halo_w, fd_tiles_img, fd_tiles_x, fd_nmblk;   // conv_m32: divisions by launch constants
   uint32_t in_bytes, out_bytes;   // sizes of the input / output (= residual) tensors when both are < 4 GiB
                                   // (buffer-addressed global traffic, conv_pipe_kernel.h: dma16_buf), else 0 (64-bit
-                                  // addressing).  conv_pipe: out_bytes = size of in2 (K-concatenated second input).
+                                  // addressing).  conv_pipe addresses only its input that way and leaves out_bytes 0.
   unsigned long long* dbg_buf;  // development build only (SCP_DBG_BUF): per-workgroup phase cycle sums (dbg & 8), else null
   int32_t dbg;           // development build only (SCP_DBG; the shipped library's kernels read neither field): bits 1 skip MFMA loop, 2 skip epilogue, 4 skip input DMA, 8 phase stamps
                          // bit 32 is the one bit the shipped library honours: the host prints the m32 tile choice
@@ -159,7 +157,7 @@ void conv_s2r_pack_bias(const float* bias, int cout, float* dst);
 int32_t conv_s2r_launch(const PackedConv& pc, const void* in, int N, int H, int W, int relu, void* out, hipStream_t stream);
 bool conv1x1_stream_eligible(const PackedConv& pc);
 int32_t conv1x1_stream_launch(const PackedConv& pc, const void* in, int N, int H, int W, const void* res, int relu,
-                              void* out, hipStream_t stream, const void* in2 = nullptr, int split_planes = 0);
+                              void* out, hipStream_t stream);
 
 // Pick (mrep, cp) for a layer independent of the spatial size; tiles are chosen per launch.
 void choose_mrep_cp(int cin, int cout, int ks, int stride, int* mrep, int* cp);
@@ -177,8 +175,7 @@ void conv_free(PackedConv* pc);
 // cu_share > 0: the caller runs other layers beside this one (concurrent lanes of the captured forward); a small 3x3 layer
 // then sizes its grid and tiles for that many CUs instead of the whole chip (same results: tiling never changes a pixel's sum)
 int32_t conv_launch(const PackedConv& pc, const void* in, int N, int H, int W, const void* res,
-                    int relu, int out_nchw_f32, void* out, hipStream_t stream,
-                    const void* in2 = nullptr, int split_planes = 0, int cu_share = 0);
+                    int relu, int out_nchw_f32, void* out, hipStream_t stream, int cu_share = 0);
 size_t conv_lds_bytes(const PackedConv& pc, int nrep, int th, int tw);
 int plane_stride_for(int stride, int halo_h, int halo_w);
 // software-pipelined persistent kernel (conv_pipe_kernel.h); nt = pixel tiles per work item
@@ -190,12 +187,6 @@ bool block_fusable(const PackedConv& c1, const PackedConv& c2);
 int32_t block_launch(const PackedConv& c1, const PackedConv& c2, const void* in, int N, int H, int W, void* out,
                      hipStream_t stream);
 int conv_device_cus();
-// branch chain (conv_chain.hip): the BasicBlocks of one low-resolution branch in one launch, a frame per workgroup, activations in LDS
-bool conv_chain_channels(int C);                 // channel counts with a chain kernel (the weights are packed at create time)
-bool conv_chain_supported(int C, int H, int W);  // ... and the map sizes it runs at (decided per forward)
-size_t conv_chain_pack(const float* w, int nconv, int C, int dtype, uint16_t* dst);   // nconv folded OIHW 3x3 weights back to back; bytes
-int32_t conv_chain_launch(const void* in, void* out, const void* wpk, const float* bias, int nconv, int N, int C, int H, int W,
-                          int dtype, uint32_t* sched, hipStream_t stream);
 unsigned long long* conv_dbg_buffer(hipStream_t stream);   // development instrumentation
 void conv_dbg_set_grid(int grid);
 // PackedConv::mrep value of the 48-row Cout block of the producer/consumer kernel's 3 x 8 form (conv_m32p_kernel.h, M16 = 3): one and
@@ -207,11 +198,7 @@ size_t pack_conv_weights_m32(const float* w, int cout, int cin, int ks, int mt, 
                              uint16_t* dst, int* nchunks, int* ksteps_full);
 int32_t conv_launch_m32(const PackedConv& pc, ConvLaunch& L, hipStream_t stream);   // SCPOSE_E_UNSUPPORTED-free: returns 1 if the shape has no good tiling (caller falls back)
 
-// ---- stem: 3 -> 64, 3x3 stride 2 from f32 NCHW or u8 NHWC ----------------------------------
-int32_t stem_launch(const void* in, int in_fmt, const float* w_folded /*dev [8][27][8]: channel group, tap, channel*/,
-                    const float* bias /*dev [64]*/, const float* mean_std /*dev [6] or null*/,
-                    int N, int H, int W, int dtype, void* out, hipStream_t stream);
-
+// ---- stem: 3 -> 64 -> 64, two 3x3 stride-2 convolutions from f32 NCHW or u8 NHWC -------------
 // fused stem (stem_fused.hip): conv1 + bn1 + relu + conv2 + bn2 + relu in one launch, both on MFMA
 void stem_fused_pack(const float* w1, const float* b1, const float* w2, const float* b2, int dtype, std::vector<uint16_t>* pw1,
                      std::vector<uint16_t>* pw2, std::vector<float>* pb1, std::vector<float>* pb2);

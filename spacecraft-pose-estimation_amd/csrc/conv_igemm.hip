@@ -4,7 +4,7 @@
 // Replaces every nn.Conv2d + eval BatchNorm2d (+ReLU, +residual add) of the reference
 // landmark_regression/lib/models/pose_hrnet.py (conv3x3 :22-25, BasicBlock :41-57,
 // Bottleneck :78-98, transition :343-368, fuse down path :216-237, fuse 1x1 :199-205,
-// final_layer :323-329) except the 3-channel stem conv (stem.hip).
+// final_layer :323-329) except the 3-channel stem conv (stem_fused.hip).
 //
 // GEMM view:  D[cout][pixel] = sum_k Wt[cout][k] * X[k][pixel],  k = (input plane, tap, 8 ch).
 //   * A operand = weights (M = Cout), B operand = activations (N = pixels).  With this
@@ -243,20 +243,18 @@ size_t conv_lds_bytes(const PackedConv& pc, int nrep, int th, int tw) {
 }
 
 int32_t conv_launch(const PackedConv& pc, const void* in, int N, int H, int W, const void* res,
-                    int relu, int out_nchw_f32, void* out, hipStream_t stream, const void* in2, int split_planes, int cu_share) {
-  SCP_REQUIRE(!in2 || (pc.variant == 0 && pc.ks == 1 && split_planes > 0 && split_planes % pc.cp == 0 && split_planes < pc.cin / 8),
-              "conv: a second input tensor needs a 1x1 layer whose K-chunks do not straddle the split (split=%d planes, cp=%d)", split_planes, pc.cp);
+                    int relu, int out_nchw_f32, void* out, hipStream_t stream, int cu_share) {
   SCP_REQUIRE(N > 0 && H > 0 && W > 0, "conv: bad shape N=%d H=%d W=%d", N, H, W);
   SCP_REQUIRE(out_nchw_f32 || pc.cout % 8 == 0, "conv: blocked output needs Cout%%8==0 (Cout=%d)", pc.cout);
   ConvLaunch L;
-  L.in = in; L.in2 = in2; L.split_planes = in2 ? split_planes : 0; L.wpk = pc.d_w; L.bias = pc.d_bias; L.res = res; L.out = out;
+  L.in = in; L.wpk = pc.d_w; L.bias = pc.d_bias; L.res = res; L.out = out;
   L.N = N; L.H = H; L.W = W;
   L.Ho = (H - 1) / pc.stride + 1;  // k=3,p=1 or k=1,p=0
   L.Wo = (W - 1) / pc.stride + 1;
   L.cin_planes = pc.cin / 8;
   L.cout = pc.cout;
   L.cu_share = cu_share;
-  if (pc.d_ws2 && !res && !in2 && !out_nchw_f32 && (size_t)N * L.cin_planes * H * W * 16 < 0xfffffff0ull &&
+  if (pc.d_ws2 && !res && !out_nchw_f32 && (size_t)N * L.cin_planes * H * W * 16 < 0xfffffff0ull &&
       (size_t)N * (pc.cout / 8) * L.Ho * L.Wo * 16 < 0xfffffff0ull)
     return conv_s2r_launch(pc, in, N, H, W, relu, out, stream);
   if (pc.variant == 1) {
@@ -267,8 +265,8 @@ int32_t conv_launch(const PackedConv& pc, const void* in, int N, int H, int W, c
   {   // 1x1 layers whose weights fit LDS: barrier-free streaming kernel (needs buffer-addressable tensors)
     static const char* e1 = dev_env("SCPOSE_K1_STREAM");
     const size_t ib = (size_t)N * L.cin_planes * H * W * 16, ob = (size_t)N * (pc.cout / 8) * H * W * 16;
-    if (pc.d_w1 && (!in2 || split_planes % 4 == 0) && !out_nchw_f32 && ib < 0xfffffff0ull && ob < 0xfffffff0ull && !(e1 && atoi(e1) == 0))
-      return conv1x1_stream_launch(pc, in, N, H, W, res, relu, out, stream, in2, split_planes);
+    if (pc.d_w1 && !out_nchw_f32 && ib < 0xfffffff0ull && ob < 0xfffffff0ull && !(e1 && atoi(e1) == 0))
+      return conv1x1_stream_launch(pc, in, N, H, W, res, relu, out, stream);
   }
   int nrep;
   choose_tile(pc.ks, pc.stride, L.Ho, L.Wo, &nrep, &L.th, &L.tw);
@@ -332,13 +330,12 @@ int32_t conv_launch(const PackedConv& pc, const void* in, int N, int H, int W, c
     }
     if (2 * conv_pipe_lds_bytes(pc, L.plane_stride, 1) <= 160 * 1024 && pc.mrep * nrep * 4 <= 128) occ = 2;
   }
-  {   // buffer-addressed input DMA when the input tensor(s) fit a 32-bit descriptor
+  {   // buffer-addressed input DMA when the input tensor fits a 32-bit descriptor
     static const char* e = dev_env("SCPOSE_M32_BUF");
-    const size_t plane = (size_t)N * H * W * 16;
-    const size_t ib = plane * (in2 ? split_planes : L.cin_planes), ib2 = in2 ? plane * (L.cin_planes - split_planes) : 0;
-    const bool fits = ib < 0xfffffff0ull && ib2 < 0xfffffff0ull && !(e && atoi(e) == 0);
+    const size_t ib = (size_t)N * H * W * 16 * L.cin_planes;
+    const bool fits = ib < 0xfffffff0ull && !(e && atoi(e) == 0);
     L.in_bytes = fits ? (uint32_t)ib : 0;
-    L.out_bytes = fits ? (uint32_t)ib2 : 0;
+    L.out_bytes = 0;   // conv_pipe writes its output through 64-bit pointers
   }
   L.cp = pc.cp; L.nchunks = pc.nchunks; L.ksteps_full = pc.ksteps_full;
   L.n_mblk = pc.n_mblk;

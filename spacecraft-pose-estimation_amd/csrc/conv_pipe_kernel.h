@@ -3,7 +3,7 @@
 // Replaces every nn.Conv2d + eval BatchNorm2d (+ReLU, +residual add) of the reference
 // landmark_regression/lib/models/pose_hrnet.py (conv3x3 :22-25, BasicBlock :41-57,
 // Bottleneck :78-98, transition :343-368, fuse down path :216-237, fuse 1x1 :199-205,
-// final_layer :323-329) except the 3-channel stem conv (stem.hip).
+// final_layer :323-329) except the 3-channel stem conv (stem_fused.hip).
 //
 // GEMM view:  D[cout][pixel] = sum_k Wt[cout][k] * X[k][pixel],  k = (input plane, tap, 8 ch).
 //   * A operand = weights (M = Cout), B operand = activations (N = pixels): an accumulator lane
@@ -200,15 +200,11 @@ __global__ __launch_bounds__(256 * G, (G == 2) ? 2 : OCC) void conv_pipe_kernel(
     if (img < 0 || SCP_DBG(p, 4)) return;
     const int planes = c == p.nchunks - 1 ? planes_last : p.cp;
     const int iy0 = oy0 * STRIDE - (KS / 2), ix0 = ox0 * STRIDE - (KS / 2);
-    // K-concatenated 1x1 layers read the chunks past split_planes from a second tensor (its own plane count)
-    const bool second = p.in2 && c * p.cp >= p.split_planes;
-    const int own_planes = p.in2 ? (second ? p.cin_planes - p.split_planes : p.split_planes) : p.cin_planes;
-    const char* inb = static_cast<const char*>(second ? p.in2 : p.in) +
-                      ((size_t)img * own_planes + (size_t)(c * p.cp - (second ? p.split_planes : 0))) * HW * 16;
+    const char* inb = static_cast<const char*>(p.in) + ((size_t)img * p.cin_planes + (size_t)(c * p.cp)) * HW * 16;
     char* xl = xl0 + (grp * 2 + xb) * p.lds_x;
     if (p.in_bytes) {   // buffer addressing (tensors < 4 GiB): image / chunk / plane displacement in an SGPR, padding out of range
-      const buf_rsrc_t rs = second ? make_buf(p.in2, p.out_bytes) : make_buf(p.in, p.in_bytes);   // out_bytes: size of in2 here
-      const uint32_t sbase = (uint32_t)((img * own_planes + (c * p.cp - (second ? p.split_planes : 0))) * HW) * 16u;
+      const buf_rsrc_t rs = make_buf(p.in, p.in_bytes);
+      const uint32_t sbase = (uint32_t)((img * p.cin_planes + c * p.cp) * HW) * 16u;
 #pragma unroll
       for (int i = 0; i < MAXP; ++i) {
         if (hy[i] >= 0) {

@@ -72,7 +72,7 @@ static bool fold(Weights& W, const std::string& conv, const std::string& bn, int
   return true;
 }
 
-enum OpKind { OP_STEM = 0, OP_CONV = 1, OP_FUSE = 2, OP_BLOCK = 3, OP_HEAD = 4, OP_STEM2 = 5, OP_BNECK = 6, OP_FDOWN = 8 };   // (9 is the profile signature of a branch chain: the OP_CONVs of a branch run as one launch, see scpose_hrnet::Chain)   // OP_FDOWN: fuse row 0 + first down hops of branch 0 (fuse_down.hip; 7 is the fused tail's profile signature)   // OP_STEM2: fused stem (stem_fused.hip); OP_BNECK: fused Bottleneck (bottleneck.hip)   // OP_BLOCK: fused BasicBlock (conv_block_kernel.h); OP_HEAD: head.hip
+enum OpKind { OP_CONV = 1, OP_FUSE = 2, OP_BLOCK = 3, OP_HEAD = 4, OP_STEM2 = 5, OP_BNECK = 6, OP_FDOWN = 8 };   // OP_FDOWN: fuse row 0 + first down hops of branch 0 (fuse_down.hip; 7 is the fused tail's profile signature)   // OP_STEM2: fused stem (stem_fused.hip); OP_BNECK: fused Bottleneck (bottleneck.hip)   // OP_BLOCK: fused BasicBlock (conv_block_kernel.h); OP_HEAD: head.hip
 
 struct TensorDesc {
   int C, ds;       // channels, log2 spatial downscale w.r.t. the network input
@@ -82,7 +82,6 @@ struct TensorDesc {
 struct Op {
   int kind;
   int in, out, res;  // tensor ids (-1 none; in == -2: network input; out == -2: heatmaps)
-  int in2;           // second input of a K-concatenated 1x1 conv (-1 none); stored +1 so that Op{} means none
   int conv;          // index into convs
   int conv2;         // OP_BLOCK: second convolution of the block
   int relu, out_f32;
@@ -111,8 +110,6 @@ struct scpose_hrnet {
   scpose_hrnet_desc desc;
   int device = 0;
   std::vector<scpose::PackedConv> convs;
-  float* d_stem_w = nullptr;   // folded, [8][27][8] (channel group, tap, channel in group)
-  float* d_stem_b = nullptr;   // [64]
   float* d_mean_std = nullptr; // [6]
   void* d_stemf_w1 = nullptr;  // fused stem (stem_fused.hip): packed conv1 / conv2 weights and biases
   void* d_stemf_w2 = nullptr;
@@ -120,11 +117,6 @@ struct scpose_hrnet {
   float* d_stemf_b2 = nullptr;
   struct Bneck { void* w1 = nullptr; void* w2 = nullptr; void* w3 = nullptr; float* bias = nullptr; int cin = 256; };   // fused Bottlenecks (bottleneck.hip)
   std::vector<Bneck> bnecks;
-  // branch chains (conv_chain.hip): ops[first_op .. first_op + nops) are the 3x3 convolutions of the BasicBlocks of one branch of a module;
-  // at map sizes the chain kernel supports they run as ONE launch at first_op and the others launch nothing (decided per forward)
-  struct Chain { int first_op = -1, nops = 0, C = 0; void* d_w = nullptr; float* d_b = nullptr; };
-  std::vector<Chain> chains;
-  std::vector<int> chain_at;    // per op: index into chains of the chain that STARTS there, else -1
   std::vector<scpose::FuseDownPacked> fdowns;   // fuse row 0 + first down hops of branch 0 (fuse_down.hip), one per module that qualifies
   float* d_head_bias = nullptr; // [4][16] folded biases of the hrnet_cms heads
   uint32_t* d_sched = nullptr;  // 16 zero-initialised words per op: dynamic tile queues of the persistent kernels (conv_device.h: tile_claim)
@@ -198,37 +190,6 @@ struct Builder {
     push(op);
     return op.out;
   }
-  // y = relu(conv_bn_a(xa) + conv_bn_b(xb)), both 1x1: ONE convolution over the concatenated input channels
-  // [xa; xb] with weights [Wa | Wb] and bias ba + bb.  Used for the first Bottleneck, whose residual is itself a
-  // 1x1 conv + BN of the block input (pose_hrnet.py:78-98, :374-391): the 256-channel residual tensor is then
-  // never written or read.  (The sum is formed in the fp32 accumulators, i.e. without the 16-bit rounding the
-  // stored residual would get.)
-  int conv_cat(int xa, const std::string& ca, const std::string& bna, int xb, const std::string& cb,
-               const std::string& bnb, int cout, bool relu, const std::string& name) {
-    if (status != SCPOSE_OK) return -1;
-    const int c1 = net->tensors[xa].C, c2 = net->tensors[xb].C;
-    std::vector<float> w1, b1, w2, b2;
-    if (!fold(*W, ca, bna, cout, c1, 1, false, &w1, &b1) || !fold(*W, cb, bnb, cout, c2, 1, false, &w2, &b2)) {
-      status = SCPOSE_E_MISSING; return -1;
-    }
-    std::vector<float> w((size_t)cout * (c1 + c2)), b(cout);
-    for (int o = 0; o < cout; ++o) {
-      for (int i = 0; i < c1; ++i) w[(size_t)o * (c1 + c2) + i] = w1[(size_t)o * c1 + i];
-      for (int i = 0; i < c2; ++i) w[(size_t)o * (c1 + c2) + c1 + i] = w2[(size_t)o * c2 + i];
-      b[o] = b1[o] + b2[o];
-    }
-    PackedConv pc;
-    const int32_t st = conv_upload(w.data(), b.data(), cout, c1 + c2, 1, 1, net->desc.dtype, &pc);
-    if (st != SCPOSE_OK) { status = st; return -1; }
-    if (pc.variant != 0 || (c1 / 8) % pc.cp != 0) { conv_free(&pc); return -2; }   // caller falls back to two convolutions
-    net->convs.push_back(pc);
-    Op op{};
-    op.kind = OP_CONV; op.in = xa; op.in2 = xb + 1; op.res = -1; op.conv = (int)net->convs.size() - 1;
-    op.relu = relu; op.out_f32 = 0;
-    op.out = new_tensor(cout, net->tensors[xa].ds, name);
-    push(op);
-    return op.out;
-  }
   // Bottleneck (layer1, pose_hrnet.py:78-98): one fused launch (bottleneck.hip).  Blocks 1-3 have an identity residual;
   // block 0 (64 input channels) projects its residual with `downsample` (1x1 conv + BN, :378-384), which rides in conv3.
   int bottleneck(int x, const std::string& p) {
@@ -262,8 +223,7 @@ struct Builder {
   // identity residual.  256 -> 64 -> 256 runs on the fused layer1 kernel, anything else as its three convolutions.
   int stage_bottleneck(int x, const std::string& p, int planes) {
     if (status != SCPOSE_OK) return -1;
-    static const char* bn_env = dev_env("SCPOSE_BNECK_FUSED");
-    if (planes == 64 && net->tensors[x].C == 256 && bottleneck_fusable(256, 64, 256) && !(bn_env && atoi(bn_env) == 0)) return bottleneck(x, p);
+    if (planes == 64 && net->tensors[x].C == 256 && bottleneck_fusable(256, 64, 256)) return bottleneck(x, p);
     int y = conv(x, p + ".conv1", p + ".bn1", planes, 1, 1, true);
     y = conv(y, p + ".conv2", p + ".bn2", planes, 3, 1, true);
     y = conv(y, p + ".conv3", p + ".bn3", 4 * planes, 1, 1, true, x);
@@ -288,41 +248,6 @@ struct Builder {
     op.out = t;
     push(op);
     return t;
-  }
-  // The ops pushed since first_op are the convolutions of `names.size() / 2` BasicBlocks of one branch (C -> C, 3x3, stride 1, each
-  // its own OP_CONV): pack them a second time for the branch-chain kernel (conv_chain.hip).  names: (conv, bn) pairs in op order.
-  void chain(size_t first_op, const std::vector<std::pair<std::string, std::string>>& names, int C) {
-    if (status != SCPOSE_OK || !conv_chain_channels(C)) return;
-    const size_t nops = net->ops.size() - first_op;
-    if (nops != names.size() || nops < 2 || nops % 2) return;
-    for (size_t k = 0; k < nops; ++k) {
-      const Op& op = net->ops[first_op + k];
-      if (op.kind != OP_CONV || op.in2 > 0 || op.out_f32) return;
-      const PackedConv& pc = net->convs[op.conv];
-      if (pc.ks != 3 || pc.stride != 1 || pc.cin != C || pc.cout != C || !op.relu) return;
-      if ((k & 1) ? (op.res != net->ops[first_op + k - 1].in) : (op.res != -1)) return;     // conv2's residual is its block's input
-      if (k > 0 && op.in != net->ops[first_op + k - 1].out) return;
-    }
-    std::vector<float> w((size_t)nops * C * C * 9), b((size_t)nops * C);
-    for (size_t k = 0; k < nops; ++k) {
-      std::vector<float> wk, bk;
-      if (!fold(*W, names[k].first, names[k].second, C, C, 3, false, &wk, &bk)) { status = SCPOSE_E_MISSING; return; }
-      memcpy(w.data() + k * C * C * 9, wk.data(), wk.size() * sizeof(float));
-      memcpy(b.data() + k * C, bk.data(), (size_t)C * sizeof(float));
-    }
-    std::vector<uint16_t> pk(conv_chain_pack(w.data(), (int)nops, C, net->desc.dtype, nullptr) / 2);
-    conv_chain_pack(w.data(), (int)nops, C, net->desc.dtype, pk.data());
-    scpose_hrnet::Chain ch;
-    ch.first_op = (int)first_op; ch.nops = (int)nops; ch.C = C;
-    if (hipMalloc(&ch.d_w, pk.size() * 2) != hipSuccess || hipMalloc(&ch.d_b, b.size() * sizeof(float)) != hipSuccess ||
-        hipMemcpy(ch.d_w, pk.data(), pk.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(ch.d_b, b.data(), b.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-      set_error("hrnet_create: uploading the branch-chain weights failed");
-      net->chains.push_back(ch);   // (hrnet_free releases whatever was allocated)
-      status = SCPOSE_E_HIP;
-      return;
-    }
-    net->chains.push_back(ch);
   }
   // x_b = Conv2d(32->J,1x1)(ConvTranspose2d(C->32,K,S,p1,op1)(y)) [+ bilinear_x2(prev)]  (hrnet_cms.py:353-368, :551-557)
   // folded into one transposed convolution C -> J: an MFMA 1x1 convolution to the tap map + the gather of head.hip.
@@ -427,25 +352,12 @@ int32_t hrnet_build(scpose_hrnet* net, Weights& W) {
   const scpose_hrnet_desc& d = net->desc;
   Builder B{net, &W};
 
-  // ---- stem conv1 (f32 VALU kernel, own weight format) ----
+  // ---- stem: conv1 + conv2 as one launch, the 64 x H/2 x W/2 tensor between them never reaches HBM (stem_fused.hip) ----
+  int x;
   {
-    std::vector<float> w, b;
-    if (!fold(W, "conv1", "bn1", 64, 3, 3, false, &w, &b)) return SCPOSE_E_MISSING;
-    SCP_CHECK_HIP(hipMalloc(&net->d_stem_w, w.size() * 4));
-    SCP_CHECK_HIP(hipMalloc(&net->d_stem_b, b.size() * 4));
     SCP_CHECK_HIP(hipMalloc(&net->d_mean_std, 6 * 4));
-    std::vector<float> wp(w.size());   // [64][27] -> [8 groups][27][8]: the stem kernel advances channel pairs with packed FMAs
-    for (int o = 0; o < 64; ++o)
-      for (int k = 0; k < 27; ++k) wp[((size_t)(o / 8) * 27 + k) * 8 + o % 8] = w[(size_t)o * 27 + k];
-    SCP_CHECK_HIP(hipMemcpy(net->d_stem_w, wp.data(), wp.size() * 4, hipMemcpyHostToDevice));
-    SCP_CHECK_HIP(hipMemcpy(net->d_stem_b, b.data(), b.size() * 4, hipMemcpyHostToDevice));
     float ms[6] = {d.mean[0], d.mean[1], d.mean[2], d.std[0], d.std[1], d.std[2]};
     SCP_CHECK_HIP(hipMemcpy(net->d_mean_std, ms, sizeof(ms), hipMemcpyHostToDevice));
-  }
-  int x;
-  static const char* stemf_env = dev_env("SCPOSE_STEM_FUSED");
-  if (!(stemf_env && atoi(stemf_env) == 0)) {
-    // conv1 + conv2 as one launch: the 64 x H/2 x W/2 tensor between them never reaches HBM (stem_fused.hip)
     std::vector<float> w1, b1, w2, b2;
     if (!fold(W, "conv1", "bn1", 64, 3, 3, false, &w1, &b1) || !fold(W, "conv2", "bn2", 64, 64, 3, false, &w2, &b2)) return SCPOSE_E_MISSING;
     std::vector<uint16_t> pw1, pw2;
@@ -464,41 +376,10 @@ int32_t hrnet_build(scpose_hrnet* net, Weights& W) {
     stem.out = B.new_tensor(64, 2, "stem2");
     B.push(stem);
     x = stem.out;
-  } else {
-    Op stem{};
-    stem.kind = OP_STEM; stem.in = -2; stem.res = -1; stem.conv = -1; stem.relu = 1;
-    stem.out = B.new_tensor(64, 1, "stem1");
-    B.push(stem);
-    x = stem.out;
-    x = B.conv(x, "conv2", "bn2", 64, 3, 2, true);
-    if (x >= 0) B.rename_tap(x, "stem2");
   }
 
   // ---- layer1: 4 Bottlenecks (64 -> 256) ----
-  for (int b = 0; b < 4; ++b) {
-    const std::string p = fmt("layer1.%d", b);
-    static const char* cat_env = dev_env("SCPOSE_CAT_DOWNSAMPLE");
-    const bool cat = b == 0 && !(cat_env && atoi(cat_env) == 0);
-    static const char* bn_env = dev_env("SCPOSE_BNECK_FUSED");
-    static const char* bn0_env = dev_env("SCPOSE_BNECK0_FUSED");
-    if (((b > 0 && net->tensors[x].C == 256) || (b == 0 && net->tensors[x].C == 64 && cat && !(bn0_env && atoi(bn0_env) == 0))) &&
-        !(bn_env && atoi(bn_env) == 0)) {   // one launch per Bottleneck
-      x = B.bottleneck(x, p);
-      continue;
-    }
-    int res = x;
-    if (b == 0 && !cat) res = B.conv(x, p + ".downsample.0", p + ".downsample.1", 256, 1, 1, false);
-    int y = B.conv(x, p + ".conv1", p + ".bn1", 64, 1, 1, true);
-    y = B.conv(y, p + ".conv2", p + ".bn2", 64, 3, 1, true);
-    int nx = -2;
-    if (cat) nx = B.conv_cat(y, p + ".conv3", p + ".bn3", x, p + ".downsample.0", p + ".downsample.1", 256, true, p);
-    if (nx == -2) {   // not concatenated (disabled or the packing does not allow the split)
-      if (b == 0 && cat) res = B.conv(x, p + ".downsample.0", p + ".downsample.1", 256, 1, 1, false);
-      nx = B.conv(y, p + ".conv3", p + ".bn3", 256, 1, 1, true, res);
-      if (nx >= 0) B.rename_tap(nx, p);
-    }
-    x = nx;
-  }
+  for (int b = 0; b < 4; ++b) x = B.bottleneck(x, fmt("layer1.%d", b));
 
   net->taps.emplace_back("layer1", x);   // the same tensor as "layer1.3" (kept: the oracle's forward(taps=) names it so)
   std::vector<int> ylist{x};
@@ -535,14 +416,10 @@ int32_t hrnet_build(scpose_hrnet* net, Weights& W) {
       for (int b = 0; b < nb; ++b) {
         B.lane = b;
         int t = xs[b];
-        const size_t branch_first_op = net->ops.size();
-        std::vector<std::pair<std::string, std::string>> branch_names;
         for (int k = 0; k < d.num_blocks[si][b]; ++k) {
           const std::string p = fmt("%s.branches.%d.%d", mp.c_str(), b, k);
           t = bneck_stage ? B.stage_bottleneck(t, p, d.num_channels[si][b]) : B.basic_block(t, p, cur[b]);
-          branch_names.emplace_back(p + ".conv1", p + ".bn1"); branch_names.emplace_back(p + ".conv2", p + ".bn2");
         }
-        if (!bneck_stage) B.chain(branch_first_op, branch_names, cur[b]);
         xs[b] = t;
       }
       B.parallel_end();
@@ -675,32 +552,15 @@ int32_t hrnet_build(scpose_hrnet* net, Weights& W) {
   }
   SCP_CHECK_HIP(hipMalloc(&net->d_sched, net->ops.size() * 16 * sizeof(uint32_t)));
   SCP_CHECK_HIP(hipMemset(net->d_sched, 0, net->ops.size() * 16 * sizeof(uint32_t)));
-  net->chain_at.assign(net->ops.size(), -1);
-  for (size_t c = 0; c < net->chains.size(); ++c) net->chain_at[net->chains[c].first_op] = (int)c;
 
   // liveness
   for (size_t i = 0; i < net->ops.size(); ++i) {
     const Op& op = net->ops[i];
     auto use = [&](int t) { if (t >= 0) net->tensors[t].last_use = (int)i; };
-    use(net->ops[i].in2 - 1);
     use(op.in); use(op.res);
     for (int k = 0; k < op.nterms; ++k) use(op.term[k]);
   }
   return SCPOSE_OK;
-}
-
-// does a branch chain start at op oi, and does its kernel run at this input size?
-static bool hrnet_chain_active(const scpose_hrnet* net, int oi, int h, int w) {
-  if (oi < 0 || (size_t)oi >= net->chain_at.size() || net->chain_at[oi] < 0) return false;
-  const scpose_hrnet::Chain& ch = net->chains[net->chain_at[oi]];
-  const TensorDesc& ti = net->tensors[net->ops[oi].in];
-  return conv_chain_supported(ch.C, h >> ti.ds, w >> ti.ds);
-}
-// ... or is op oi one of the later convolutions of such a chain (it launches nothing)?
-static bool hrnet_chain_member(const scpose_hrnet* net, int oi, int h, int w) {
-  for (const scpose_hrnet::Chain& ch : net->chains)
-    if (oi > ch.first_op && oi < ch.first_op + ch.nops) return hrnet_chain_active(net, ch.first_op, h, w);
-  return false;
 }
 
 static size_t tensor_bytes(const TensorDesc& t, int n, int h, int w) {
@@ -755,7 +615,6 @@ size_t hrnet_plan(scpose_hrnet* net, int n, int h, int w, int mode = 0) {
   P.off.assign(net->tensors.size(), 0);
   std::vector<char> released(net->tensors.size(), 0);
   std::vector<int> pending;   // mode 1: tensors whose last reader ran in the current epoch
-  int chain_out = -1;         // output tensor of the branch chain being walked (allocated at the chain's first op)
   int cur_epoch = net->ops.empty() ? 0 : net->ops[0].epoch;
   for (size_t i = 0; i < net->ops.size(); ++i) {
     const Op& op = net->ops[i];
@@ -764,14 +623,7 @@ size_t hrnet_plan(scpose_hrnet* net, int n, int h, int w, int mode = 0) {
       pending.clear();
       cur_epoch = op.epoch;
     }
-    // A branch chain (conv_chain.hip) launched at its first op writes the LAST op's output tensor, frame by frame, while other
-    // workgroups still read the chain's input: that output is born here, beside the (still live) input, not at the last op
-    if (hrnet_chain_active(net, (int)i, h, w)) {
-      const int t_out = net->ops[i + net->chains[net->chain_at[i]].nops - 1].out;
-      P.off[t_out] = alloc(tensor_bytes(net->tensors[t_out], n, h, w));
-      chain_out = t_out;
-    }
-    if (op.out >= 0 && op.out != chain_out) P.off[op.out] = alloc(tensor_bytes(net->tensors[op.out], n, h, w));
+    if (op.out >= 0) P.off[op.out] = alloc(tensor_bytes(net->tensors[op.out], n, h, w));
     for (int k = 0; k < op.nouts; ++k) P.off[op.outs[k]] = alloc(tensor_bytes(net->tensors[op.outs[k]], n, h, w));
     auto done = [&](int t) {
       if (t >= 0 && net->tensors[t].last_use == (int)i && !released[t]) {
@@ -780,7 +632,7 @@ size_t hrnet_plan(scpose_hrnet* net, int n, int h, int w, int mode = 0) {
         else release(P.off[t], tensor_bytes(net->tensors[t], n, h, w));
       }
     };
-    done(op.in); done(op.res); done(op.in2 - 1);
+    done(op.in); done(op.res);
     for (int k = 0; k < op.nterms; ++k) done(op.term[k]);
     // an output nobody reads (cannot happen in a well-formed net) is simply never reused
   }
@@ -837,7 +689,6 @@ int32_t hrnet_forward(scpose_hrnet* net, const void* in, int in_fmt, int n, int 
   hipStream_t const st0 = st;
   int cur_epoch = -1, par_index = -1;
   unsigned open_lanes = 0;   // side lanes forked in the current epoch
-  int chain_end = 0;         // ops below this index belong to a branch chain that has been launched
   auto join_lanes = [&]() -> int32_t {
     for (int l = 1; l < 4; ++l)
       if (open_lanes & (1u << l)) {
@@ -870,16 +721,7 @@ int32_t hrnet_forward(scpose_hrnet* net, const void* in, int in_fmt, int n, int 
     if (profile) SCP_CHECK_HIP(hipEventRecord(net->events[opi], st));
     ++opi;
     int32_t rc = SCPOSE_OK;
-    if ((int)oi < chain_end) {
-      // nothing: a convolution inside a branch chain that was launched at the chain's first op
-      if (stop_tensor >= 0 && op.out == stop_tensor && (int)oi + 1 < chain_end) { set_error("hrnet_forward: tensor %d lies inside a branch chain", stop_tensor); return SCPOSE_E_INVALID; }
-    } else if (hrnet_chain_active(net, (int)oi, h, w)) {
-      const scpose_hrnet::Chain& ch = net->chains[net->chain_at[oi]];
-      const TensorDesc& ti = net->tensors[op.in];
-      chain_end = ch.first_op + ch.nops;
-      rc = conv_chain_launch(ptr(op.in), ptr(net->ops[chain_end - 1].out), ch.d_w, ch.d_b, ch.nops, n, ch.C, h >> ti.ds, w >> ti.ds,
-                             net->desc.dtype, net->d_sched + 16 * oi, st);
-    } else if (fused_tail && (int)oi == net->headf.fuse_op) {
+    if (fused_tail && (int)oi == net->headf.fuse_op) {
       // nothing: its sum is formed in registers by the next op
     } else if (fused_tail && (int)oi == net->headf.conv_op) {
       const Op& fo = net->ops[net->headf.fuse_op];
@@ -890,9 +732,6 @@ int32_t hrnet_forward(scpose_hrnet* net, const void* in, int in_fmt, int n, int 
                              net->headf.d_w, net->headf.d_b, heatmaps, dec ? part_v : nullptr,
                              dec ? part_i : nullptr, dec ? dec->center : nullptr, dec ? dec->scale : nullptr,
                              dec ? dec->post_process : 0, dec ? dec->preds : nullptr, st);
-    } else if (op.kind == OP_STEM) {
-      rc = stem_launch(in, in_fmt, net->d_stem_w, net->d_stem_b, net->d_mean_std, n, h, w,
-                       net->desc.dtype, ptr(op.out), st);
     } else if (op.kind == OP_STEM2) {
       rc = stem_fused_launch(in, in_fmt, net->d_stemf_w1, net->d_stemf_w2, net->d_stemf_b1, net->d_stemf_b2, net->d_mean_std,
                              n, h, w, net->desc.dtype, ptr(op.out), net->d_sched + 16 * oi, st);
@@ -900,8 +739,7 @@ int32_t hrnet_forward(scpose_hrnet* net, const void* in, int in_fmt, int n, int 
       const TensorDesc& ti = net->tensors[op.in];
       void* out = op.out == -2 ? static_cast<void*>(heatmaps) : ptr(op.out);
       rc = conv_launch(net->convs[op.conv], ptr(op.in), n, h >> ti.ds, w >> ti.ds, ptr(op.res),
-                       op.relu, op.out_f32, out, st, op.in2 > 0 ? ptr(op.in2 - 1) : nullptr,
-                       op.in2 > 0 ? net->tensors[op.in].C / 8 : 0, open_lanes ? conv_device_cus() / 2 : 0);
+                       op.relu, op.out_f32, out, st, open_lanes ? conv_device_cus() / 2 : 0);
     } else if (op.kind == OP_HEAD) {
       const TensorDesc& ti = net->tensors[op.in];
       float* out = op.out == -2 ? heatmaps : static_cast<float*>(ptr(op.out));
@@ -968,22 +806,6 @@ static void op_work(const scpose_hrnet* net, const Op& op, int h, int w, double*
     *by = J * ho * wo * 4;
     for (int k = 0; k < fo.nterms; ++k) *by += to.C * (ho / (1 << fo.shift[k])) * (wo / (1 << fo.shift[k])) * 2;
     sig[0] = 7; sig[1] = fo.nterms; sig[2] = to.C; sig[3] = (int)J;
-  } else if (!unfused && hrnet_chain_active(net, (int)(&op - net->ops.data()), h, w)) {
-    // branch chain (conv_chain.hip): every convolution of the branch in this one launch (kind 9); it reads the branch input once and
-    // writes the branch output once
-    const scpose_hrnet::Chain& ch = net->chains[net->chain_at[&op - net->ops.data()]];
-    const TensorDesc& ti = net->tensors[op.in];
-    const double hi = h >> ti.ds, wi = w >> ti.ds;
-    *f = ch.nops * 2.0 * ch.C * ch.C * 9 * hi * wi;
-    *by = 2.0 * ch.C * hi * wi * 2;
-    sig[0] = 9; sig[1] = ch.nops; sig[2] = ch.C; sig[3] = ch.C;
-  } else if (!unfused && hrnet_chain_member(net, (int)(&op - net->ops.data()), h, w)) {
-    // launched nothing: accounted under the chain's first op
-    sig[0] = 9; sig[1] = 0; sig[2] = net->convs[op.conv].cin; sig[3] = net->convs[op.conv].cout;
-  } else if (op.kind == OP_STEM) {
-    *f = 2.0 * 27 * 64 * (h / 2) * (w / 2);
-    *by = (double)64 * (h / 2) * (w / 2) * 2 + 3.0 * h * w;   // u8 in (f32 in: 4x) + 16-bit out
-    sig[1] = 32; sig[2] = 3; sig[3] = 64;
   } else if (op.kind == OP_STEM2) {
     // both stem convolutions; bytes: the launch reads the image and writes the H/4 x W/4 result (unfused accounting:
     // + the H/2 x W/2 tensor written once and read once)
@@ -997,7 +819,6 @@ static void op_work(const scpose_hrnet* net, const Op& op, int h, int w, double*
     const double ho = pc.stride == 2 ? hi / 2 : hi, wo = pc.stride == 2 ? wi / 2 : wi;
     *f = 2.0 * pc.cin * pc.cout * pc.ks * pc.ks * ho * wo;
     *by = pc.cin * hi * wi * 2 + pc.cout * ho * wo * (op.out_f32 ? 4 : 2) + (op.res >= 0 ? pc.cout * ho * wo * 2 : 0);
-    if (op.in2 > 0 && unfused) *by += 2.0 * pc.cout * ho * wo * 2;   // the unfused pair writes the residual tensor once and reads it once; the K-concatenated launch does neither
     sig[1] = pc.ks * 10 + pc.stride; sig[2] = pc.cin; sig[3] = pc.cout;
   } else if (op.kind == OP_BLOCK) {
     // flops of the two convolutions; bytes: the fused launch reads x once and writes the block output once (the
@@ -1047,12 +868,10 @@ void hrnet_stats(scpose_hrnet* net, int h, int w, int* launches, double* flops, 
   for (const Op& op : net->ops) {
     double of, ob; int32_t sig[4];
     op_work(net, op, h, w, &of, &ob, sig, true);   // whole-net figure in SURVEY.md 8(d)'s accounting (422 MB for W48 384^2)
-    if (op.kind == OP_STEM || op.kind == OP_STEM2) ob -= 3.0 * h * w;   // network input is not an inter-layer activation
+    if (op.kind == OP_STEM2) ob -= 3.0 * h * w;   // network input is not an inter-layer activation
     f += of; by += ob;
   }
-  int skipped = hrnet_tail_fused(net, 1, h, w) ? 1 : 0;   // the fused tail absorbs the last fuse row
-  for (const scpose_hrnet::Chain& ch : net->chains)
-    if (hrnet_chain_active(net, ch.first_op, h, w)) skipped += ch.nops - 1;   // a branch chain is one launch
+  const int skipped = hrnet_tail_fused(net, 1, h, w) ? 1 : 0;   // the fused tail absorbs the last fuse row
   if (launches) *launches = (int)net->ops.size() - skipped;
   if (flops) *flops = f;
   if (bytes) *bytes = by;
@@ -1060,8 +879,6 @@ void hrnet_stats(scpose_hrnet* net, int h, int w, int* launches, double* flops, 
 
 void hrnet_free(scpose_hrnet* net) {
   for (auto& c : net->convs) conv_free(&c);
-  if (net->d_stem_w) (void)hipFree(net->d_stem_w);
-  if (net->d_stem_b) (void)hipFree(net->d_stem_b);
   if (net->d_mean_std) (void)hipFree(net->d_mean_std);
   for (auto& bn : net->bnecks) {
     if (bn.w1) (void)hipFree(bn.w1);
@@ -1070,7 +887,6 @@ void hrnet_free(scpose_hrnet* net) {
     if (bn.bias) (void)hipFree(bn.bias);
   }
   for (auto& fd : net->fdowns) fuse_down_free(&fd);
-  for (auto& ch : net->chains) { if (ch.d_w) (void)hipFree(ch.d_w); if (ch.d_b) (void)hipFree(ch.d_b); }
   if (net->d_stemf_w1) (void)hipFree(net->d_stemf_w1);
   if (net->d_stemf_w2) (void)hipFree(net->d_stemf_w2);
   if (net->d_stemf_b1) (void)hipFree(net->d_stemf_b1);

@@ -731,7 +731,7 @@ class HrnetEngine:
         return buf.value.decode().split(",")
 
     def forward_tap(self, x, tap):
-        """Intermediate tensor `tap` ("stem1", "stem2", "layer1", "stage3.1.out0", ...) of the forward of x as float32
+        """Intermediate tensor `tap` ("stem2", "layer1", "stage3.1.out0", ...) of the forward of x as float32
         (N, C, h, w): the forward is run up to the op that produces it (unit-level parity against the oracle's taps)."""
         _need_cuda(x)
         x = x.contiguous()

@@ -71,7 +71,15 @@ def table(path, filters=()):
     plain = subprocess.check_output([filt if os.path.exists(filt) else "c++filt"], input="\n".join(names), text=True).splitlines()
     res = {}
     for mangled, name in zip(names, plain):
-        name = re.sub(r"^void |\(.*\)$", "", name)
+        name = re.sub(r"^void ", "", name)
+        if name.endswith(")"):   # drop the argument list: the parenthesis that closes at the end ("(anonymous namespace)" stays)
+            depth, i = 0, len(name)
+            while i > 0:
+                i -= 1
+                depth += (name[i] == ")") - (name[i] == "(")
+                if depth == 0:
+                    break
+            name = name[:i]
         if not filters or any(f in name for f in filters):
             res[name] = rows[mangled]
     return res
