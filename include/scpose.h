@@ -345,6 +345,53 @@ int32_t scpose_events_csv_parse(const uint8_t* data, int64_t n_bytes, int32_t de
                                 int64_t* t, int32_t* x, int32_t* y, int8_t* p, int64_t capacity, int64_t* count_status,
                                 void* workspace, size_t workspace_bytes, void* stream);
 
+/* (ABI 7, additive) DVS emulator core on the device (csrc/dvs_emulator.hip): time-stamped grayscale uint8 frames -> an event
+ * stream, in the columns scpose_events_frame_bounds / scpose_events_render take.  Restates EventEmulator._init / generate_events
+ * of the reference's v2e/v2ecore/emulator.py (with lin_log, rescale_intensity_frame, low_pass_filter, subtract_leak_current,
+ * compute_event_map of emulator_utils.py) bit for bit in float32; shot noise and leak jitter, which draw random numbers every
+ * frame, are not part of it.  The per-pixel quantities the reference draws once (thresholds, noise-rate array) are inputs.
+ *
+ * The state (base_log_frame, lp_log_frame0 / 1, timestamp_mem, t_previous and two planes of scratch) lives in a caller-owned
+ * device buffer of scpose_dvs_state_bytes(h, w) bytes, 256-byte aligned.  scpose_dvs_init is the reference's first frame: it
+ * only initialises the state.  scpose_dvs_emulate then takes n_frames >= 0 further frames in order and appends their events;
+ * a sequence fed in several calls gives bitwise the events of one call.  Per sub-iteration i of a frame the events are all ON
+ * pixels in row-major order, then all OFF pixels in row-major order (the reference shuffles each such group, whose stamps are
+ * equal).  No allocation, no synchronisation, no floating-point atomic; two runs are bitwise equal.
+ *   params        h, w; pos_thres / neg_thres (> 0) used where the matching *_map (device f32 h x w, or null) is null;
+ *                 noise_rate_map device f32 h x w or null (1 everywhere), used when leak_rate_hz > 0; cutoff_hz, leak_rate_hz,
+ *                 refractory_period_s >= 0 (0: off); lin_log_table device f32 [256], the reference's lin_log of 0 ... 255
+ *                 (float64 formula, rounded to 1e-8, then float32); max_iters in [1, 4096]: the most sub-iterations of one
+ *                 frame the workspace is sized for, 2 * h * w * max_iters < 2^31
+ *   frames        device u8 n_frames x h x w;  t  device f64 [n_frames], seconds, each later than the one before (and than
+ *                 the state's), >= 0 and below 2^32 us for the integer column
+ *   t_s,t,x,y,p   device f32 / i64 / i32 / i32 / i8, capacity rows each: the reference's float32 stamp, the same in
+ *                 microseconds by its h5 rule uint32(float32(t_s) * 1e6), the pixel, and the polarity: ON (the reference's
+ *                 +1) is 1, OFF (its -1) is 0
+ *   count_status  device i64 [2] <- [n_events, status].  n_events is the number the frames produce even where it exceeds
+ *                 capacity; rows at and past capacity are never written.  status is a set of bits:
+ *                   SCPOSE_DVS_CAPACITY  n_events > capacity: the first `capacity` rows are valid, the state has advanced
+ *                   SCPOSE_DVS_ITERS     a frame needs more than max_iters sub-iterations: that frame and all later ones were
+ *                                        not emulated and the state is unusable until the next scpose_dvs_init
+ *                   SCPOSE_DVS_TIME      a stamp does not increase (the reference raises ValueError): likewise
+ *   workspace     caller-owned, 256-byte aligned, scpose_dvs_workspace_bytes(h, w, n_frames, max_iters) */
+enum { SCPOSE_DVS_CAPACITY = 1, SCPOSE_DVS_ITERS = 2, SCPOSE_DVS_TIME = 4 };
+typedef struct {
+  int32_t h, w;
+  float pos_thres, neg_thres;
+  const float* pos_thres_map;
+  const float* neg_thres_map;
+  const float* noise_rate_map;
+  const float* lin_log_table;
+  double cutoff_hz, leak_rate_hz, refractory_period_s;
+  int32_t max_iters;
+} scpose_dvs_params;
+int32_t scpose_dvs_state_bytes(int32_t h, int32_t w, size_t* bytes);
+int32_t scpose_dvs_workspace_bytes(int32_t h, int32_t w, int32_t n_frames, int32_t max_iters, size_t* bytes);
+int32_t scpose_dvs_init(void* state, const uint8_t* frame0, double t0, const scpose_dvs_params* params, void* stream);
+int32_t scpose_dvs_emulate(void* state, const uint8_t* frames, const double* t, int32_t n_frames, const scpose_dvs_params* params,
+                           float* t_s, int64_t* t_us, int32_t* x, int32_t* y, int8_t* p, int64_t capacity, int64_t* count_status,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
 /* Flip test (cfg.TEST.FLIP_TEST, lib/core/function.py:347-366): out = (a + flip_back(b)) * 0.5 where b
  * is the forward of the x-flipped input; flip_back (lib/utils/transforms.py:15-29) mirrors b in x and
  * swaps the joints of each flip pair; shift != 0 applies the TEST.SHIFT_HEATMAP column shift (:361-363).

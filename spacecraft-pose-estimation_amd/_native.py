@@ -22,6 +22,7 @@ if os.environ.get("SCPOSE_DEV") == "1":
 DT_BF16, DT_F16 = 0, 1
 IN_F32_NCHW, IN_U8_NHWC = 0, 1
 CSV_UNSUPPORTED, CSV_CAPACITY = 1, 2
+DVS_CAPACITY, DVS_ITERS, DVS_TIME = 1, 2, 4
 ABI_VERSION = 7
 
 
@@ -39,6 +40,23 @@ class HrnetDesc(ctypes.Structure):
         ("std", c_float * 3),
         ("head", c_int32),
         ("block", c_int32 * 3),
+    ]
+
+
+class DvsParams(ctypes.Structure):
+    _fields_ = [
+        ("h", c_int32),
+        ("w", c_int32),
+        ("pos_thres", c_float),
+        ("neg_thres", c_float),
+        ("pos_thres_map", c_void_p),
+        ("neg_thres_map", c_void_p),
+        ("noise_rate_map", c_void_p),
+        ("lin_log_table", c_void_p),
+        ("cutoff_hz", c_double),
+        ("leak_rate_hz", c_double),
+        ("refractory_period_s", c_double),
+        ("max_iters", c_int32),
     ]
 
 
@@ -97,6 +115,11 @@ SYMBOLS = {
     "scpose_events_csv_workspace_bytes": (c_int32, [c_int64, POINTER(c_size_t)]),
     "scpose_events_csv_parse": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "scpose_dvs_state_bytes": (c_int32, [c_int32, c_int32, POINTER(c_size_t)]),
+    "scpose_dvs_workspace_bytes": (c_int32, [c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
+    "scpose_dvs_init": (c_int32, [c_void_p, c_void_p, c_double, POINTER(DvsParams), c_void_p]),
+    "scpose_dvs_emulate": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, POINTER(DvsParams), c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "scpose_heatmap_accumulate": (c_int32, [c_void_p, c_void_p, c_float, c_int64, c_void_p]),
     "scpose_flip_merge": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
                                     c_void_p]),

@@ -169,6 +169,65 @@ extern "C" int32_t scpose_events_csv_parse(const uint8_t* data, int64_t n_bytes,
                                  static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
 }
 
+static int32_t dvs_check_params(const scpose_dvs_params* p, const char* who) {
+  SCP_REQUIRE(p, "%s: null params", who);
+  SCP_REQUIRE(p->h > 0 && p->w > 0 && (int64_t)p->h * p->w <= (1 << 24), "%s: bad shape h=%d w=%d", who, p->h, p->w);
+  SCP_REQUIRE((p->pos_thres_map || p->pos_thres > 0.f) && (p->neg_thres_map || p->neg_thres > 0.f),
+              "%s: thresholds must be > 0 (pos_thres=%g neg_thres=%g)", who, (double)p->pos_thres, (double)p->neg_thres);
+  SCP_REQUIRE(p->cutoff_hz >= 0.0 && p->leak_rate_hz >= 0.0 && p->refractory_period_s >= 0.0 && p->cutoff_hz <= 1e300 &&
+                  p->leak_rate_hz <= 1e300 && p->refractory_period_s <= 1e300,
+              "%s: cutoff_hz=%g leak_rate_hz=%g refractory_period_s=%g must be finite and >= 0", who, p->cutoff_hz, p->leak_rate_hz,
+              p->refractory_period_s);
+  SCP_REQUIRE(p->lin_log_table, "%s: null lin_log_table", who);
+  SCP_REQUIRE(p->max_iters >= 1 && p->max_iters <= 4096 && 2 * (int64_t)p->h * p->w * p->max_iters < ((int64_t)1 << 31),
+              "%s: max_iters=%d (1 ... 4096, and 2 * h * w * max_iters < 2^31)", who, p->max_iters);
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_dvs_state_bytes(int32_t h, int32_t w, size_t* bytes) {
+  SCP_REQUIRE(bytes, "dvs_state_bytes: null argument");
+  SCP_REQUIRE(h > 0 && w > 0 && (int64_t)h * w <= (1 << 24), "dvs_state_bytes: bad shape h=%d w=%d", h, w);
+  *bytes = dvs_state_bytes(h, w);
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_dvs_workspace_bytes(int32_t h, int32_t w, int32_t n_frames, int32_t max_iters, size_t* bytes) {
+  SCP_REQUIRE(bytes, "dvs_workspace_bytes: null argument");
+  SCP_REQUIRE(h > 0 && w > 0 && (int64_t)h * w <= (1 << 24) && n_frames >= 0, "dvs_workspace_bytes: bad shape h=%d w=%d n_frames=%d", h,
+              w, n_frames);
+  SCP_REQUIRE(max_iters >= 1 && max_iters <= 4096 && 2 * (int64_t)h * w * max_iters < ((int64_t)1 << 31),
+              "dvs_workspace_bytes: max_iters=%d (1 ... 4096, and 2 * h * w * max_iters < 2^31)", max_iters);
+  *bytes = dvs_workspace_bytes(h, w, n_frames, max_iters);
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_dvs_init(void* state, const uint8_t* frame0, double t0, const scpose_dvs_params* params, void* stream) {
+  const int32_t rc = dvs_check_params(params, "dvs_init");
+  if (rc != SCPOSE_OK) return rc;
+  SCP_REQUIRE(state && frame0, "dvs_init: null argument");
+  SCP_REQUIRE((reinterpret_cast<uintptr_t>(state) & 255) == 0, "dvs_init: state must be 256-byte aligned");
+  SCP_REQUIRE(t0 == t0 && t0 >= -1e300 && t0 <= 1e300, "dvs_init: t0=%g", t0);
+  return dvs_init_launch(state, frame0, t0, params->h, params->w, params->lin_log_table, params->refractory_period_s,
+                         static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t scpose_dvs_emulate(void* state, const uint8_t* frames, const double* t, int32_t n_frames,
+                                      const scpose_dvs_params* params, float* t_s, int64_t* t_us, int32_t* x, int32_t* y, int8_t* p,
+                                      int64_t capacity, int64_t* count_status, void* workspace, size_t workspace_bytes, void* stream) {
+  const int32_t rc = dvs_check_params(params, "dvs_emulate");
+  if (rc != SCPOSE_OK) return rc;
+  SCP_REQUIRE(n_frames >= 0 && capacity >= 0, "dvs_emulate: n_frames=%d capacity=%lld", n_frames, (long long)capacity);
+  SCP_REQUIRE(state && count_status && ((frames && t) || n_frames == 0) && ((t_s && t_us && x && y && p) || capacity == 0),
+              "dvs_emulate: null argument");
+  SCP_REQUIRE((reinterpret_cast<uintptr_t>(state) & 255) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
+              "dvs_emulate: state and workspace must be 256-byte aligned");
+  const size_t need = dvs_workspace_bytes(params->h, params->w, n_frames, params->max_iters);
+  SCP_REQUIRE(workspace && workspace_bytes >= need, "dvs_emulate: workspace of %zu bytes needed (got %zu)", need,
+              workspace ? workspace_bytes : (size_t)0);
+  return dvs_emulate_launch(state, frames, t, n_frames, *params, t_s, t_us, x, y, p, capacity, count_status,
+                            static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
 extern "C" int32_t scpose_flip_merge(const float* a, const float* b, const int32_t* perm, int32_t n, int32_t j,
                                      int32_t h, int32_t w, int32_t shift, float* out, void* stream) {
   if (n == 0) return SCPOSE_OK;

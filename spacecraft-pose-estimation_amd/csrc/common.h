@@ -249,6 +249,14 @@ int32_t events_bounds_midpoints_launch(const int64_t* t, const int64_t* bounds, 
 size_t events_csv_workspace_bytes(int64_t n_bytes);
 int32_t events_csv_parse_launch(const uint8_t* data, int64_t n_bytes, int ws_mode, int swap_xy, double t_div, int64_t* t, int32_t* x,
                                 int32_t* y, int8_t* p, int64_t capacity, int64_t* count_status, uint8_t* ws, hipStream_t stream);
+// dvs_emulator.hip: intensity frames -> event stream (v2e/v2ecore/emulator.py: EventEmulator.generate_events)
+size_t dvs_state_bytes(int h, int w);
+size_t dvs_workspace_bytes(int h, int w, int frames, int max_iters);
+int32_t dvs_init_launch(void* state, const uint8_t* frame0, double t0, int h, int w, const float* lut, double refractory_period_s,
+                        hipStream_t stream);
+int32_t dvs_emulate_launch(void* state, const uint8_t* frames, const double* t, int n_frames, const scpose_dvs_params& prm, float* t_s,
+                           int64_t* t_us, int32_t* x, int32_t* y, int8_t* pol, int64_t capacity, int64_t* counts, uint8_t* ws,
+                           hipStream_t stream);
 int32_t head_gather_launch(const void* taps, const float* bias, const float* prev, int N, int J, int H, int W,
                            int K, int S, int dtype, float* out, hipStream_t stream);
 int32_t heatmap_accumulate_launch(float* acc, const float* x, float div, size_t count, hipStream_t stream);

@@ -400,6 +400,130 @@ def parse_events_csv(data, delim_whitespace=False, swap_xy=False, microseconds_t
         return t[:rows].clone(), x[:rows].clone(), y[:rows].clone(), p[:rows].clone()
 
 
+class DvsEmulator:
+    """Device DVS emulator (csrc/dvs_emulator.hip): see dvs_emulator().  The state lives in device memory between calls."""
+
+    def __init__(self, h, w, device=None, **params):
+        from . import dvs_emulator as de
+        self._p = de.validate(h, w, **params)
+        self.h, self.w = self._p["h"], self._p["w"]
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if self.device.type != "cuda":
+            raise nat.NativeError("dvs_emulator needs a ROCm device (got %s); there is no CPU path" % self.device)
+        lib = nat.lib()
+        sb = c_size_t()
+        nat.check(lib.scpose_dvs_state_bytes(self.h, self.w, ctypes.byref(sb)), "dvs_state_bytes")
+        up = lambda a: torch.from_numpy(a).to(self.device) if a is not None else None
+        self._maps = [up(self._p[k]) for k in ("pos_map", "neg_map", "noise_map")]
+        self._lut = up(de.lin_log_table())
+        self._state = torch.zeros(sb.value, dtype=torch.uint8, device=self.device)
+        self._c = nat.DvsParams(self.h, self.w, self._p["pos"], self._p["neg"], self._maps[0].data_ptr() if self._maps[0] is not None else None,
+                                self._maps[1].data_ptr() if self._maps[1] is not None else None,
+                                self._maps[2].data_ptr() if self._maps[2] is not None else None, self._lut.data_ptr(),
+                                self._p["cutoff_hz"], self._p["leak_rate_hz"], self._p["refractory_period_s"], self._p["max_iters"])
+        self._t_prev = None
+        self._per_frame = 0.25                 # events per pixel and frame seen so far: sizes the next call's columns
+        self.last_status = 0
+
+    def reset(self):
+        """The next emulate() call initialises the state from its first frame again."""
+        self._t_prev = None
+
+    def state(self):
+        """dict of the four state planes (base, lp0, lp1, tmem) as (h, w) float32 device tensors: copies, for inspection."""
+        hw = self.h * self.w
+        pl = (hw * 4 + 255) // 256 * 256
+        return {k: self._state[256 + i * pl: 256 + i * pl + hw * 4].view(torch.float32).view(self.h, self.w).clone()
+                for i, k in enumerate(("base", "lp0", "lp1", "tmem"))}
+
+    def emulate(self, frames, t, capacity=None):
+        """frames uint8 (F, h, w) and t float64 (F,) seconds: device tensors, or host arrays that are uploaded.  Returns
+        (t int64 us, x int32, y int32, p int8, t_s float32) device tensors: the events of these frames in order, p == 1 for ON.
+        The first call (and the first after reset()) takes its first frame as the reference's frame 0, which only initialises
+        the state.  Stamps that do not increase raise ValueError before anything runs.  capacity: rows to provide for; by
+        default sized from the event rate seen so far, and the call is repeated from a saved state when that was too small.  One
+        small read-back per attempt, [n_events, status]."""
+        from . import dvs_emulator as de
+        if torch.is_tensor(frames):
+            fr = frames.to(self.device)
+        else:
+            fr = torch.from_numpy(np.ascontiguousarray(np.asarray(frames))).to(self.device)
+        if fr.dtype != torch.uint8 or fr.dim() != 3 or tuple(fr.shape[1:]) != (self.h, self.w):
+            raise ValueError("dvs_emulator: frames must be uint8 of shape (F, %d, %d) (got %s %s)" % (self.h, self.w, fr.dtype, tuple(fr.shape)))
+        fr = fr.contiguous()
+        th = de.check_times(t.detach().cpu().numpy() if torch.is_tensor(t) else t, self._t_prev)
+        if th.shape[0] != fr.shape[0]:
+            raise ValueError("dvs_emulator: %d frames but %d stamps" % (fr.shape[0], th.shape[0]))
+        lib = nat.lib()
+        dev = self.device
+        with torch.cuda.device(dev):
+            if fr.shape[0] and self._t_prev is None:
+                nat.check(lib.scpose_dvs_init(_ptr(self._state), _ptr(fr), c_double(float(th[0])), ctypes.byref(self._c), _stream()), "dvs_init")
+                self._t_prev = float(th[0])
+                fr, th = fr[1:], th[1:]
+            f = int(fr.shape[0])
+            empty = lambda dt: torch.empty(0, dtype=dt, device=dev)
+            if f == 0:
+                return empty(torch.int64), empty(torch.int32), empty(torch.int32), empty(torch.int8), empty(torch.float32)
+            t_d = (t.to(dev, torch.float64)[-f:] if torch.is_tensor(t) else torch.from_numpy(th).to(dev)).contiguous()
+            ws = c_size_t()
+            nat.check(lib.scpose_dvs_workspace_bytes(self.h, self.w, f, self._p["max_iters"], ctypes.byref(ws)), "dvs_workspace_bytes")
+            work = torch.empty(ws.value, dtype=torch.uint8, device=dev)
+            cs = torch.empty(2, dtype=torch.int64, device=dev)
+            fixed = capacity is not None
+            cap = int(capacity) if fixed else max(4096, int(self._per_frame * 1.25 * f * self.h * self.w) + 1024)
+            saved = None if fixed else self._state.clone()
+            while True:
+                cols = (torch.empty(cap, dtype=torch.float32, device=dev), torch.empty(cap, dtype=torch.int64, device=dev),
+                        torch.empty(cap, dtype=torch.int32, device=dev), torch.empty(cap, dtype=torch.int32, device=dev),
+                        torch.empty(cap, dtype=torch.int8, device=dev))
+                nat.check(lib.scpose_dvs_emulate(_ptr(self._state), _ptr(fr), _ptr(t_d), f, ctypes.byref(self._c), _ptr(cols[0]), _ptr(cols[1]),
+                                                 _ptr(cols[2]), _ptr(cols[3]), _ptr(cols[4]), cap, _ptr(cs), _ptr(work), ws.value, _stream()),
+                          "dvs_emulate")
+                n, status = cs.tolist()                             # the one small read-back
+                self.last_status = status
+                if status & nat.DVS_TIME:
+                    raise ValueError("dvs_emulator: a frame time is not later than its predecessor")
+                if status & nat.DVS_ITERS:
+                    self._t_prev = None
+                    raise nat.NativeError("dvs_emulator: a frame needs more than max_iters=%d sub-iterations; the state was reset -- "
+                                          "construct the emulator with a larger max_iters" % self._p["max_iters"])
+                if status & nat.DVS_CAPACITY and not fixed:
+                    self._state.copy_(saved)
+                    cap = n
+                    continue
+                break
+            self._t_prev = float(th[-1])
+            if status & nat.DVS_CAPACITY:
+                raise DvsCapacity("dvs_emulator: %d events do not fit the capacity of %d rows" % (n, cap), n, cols)
+            self._per_frame = max(self._per_frame, n / float(f * self.h * self.w))
+            return cols[1][:n], cols[2][:n], cols[3][:n], cols[4][:n], cols[0][:n]
+
+
+class DvsCapacity(nat.NativeError):
+    """emulate(capacity=...) produced more events than the capacity: .n_events is the full count, .columns the (t_s, t, x, y, p)
+    buffers, whose first `capacity` rows are valid.  The state has advanced past the frames."""
+
+    def __init__(self, msg, n_events, columns):
+        super().__init__(msg)
+        self.n_events, self.columns = n_events, columns
+
+
+def dvs_emulator(h, w, pos_thres=0.2, neg_thres=0.2, cutoff_hz=0, leak_rate_hz=0, noise_rate_array=None, refractory_period_s=0,
+                 shot_noise_rate_hz=0, leak_jitter_fraction=0, max_iters=1024, device=None):
+    """The reference's DVS emulator core (v2e/v2ecore/emulator.py: EventEmulator.generate_events) on the device: intensity frames
+    -> the event stream render_events takes.  pos_thres / neg_thres: scalars or (h, w) float32 arrays (dvs_emulator.
+    draw_pixel_arrays draws them the way the reference does for sigma_thres > 0); noise_rate_array likewise, used with
+    leak_rate_hz > 0.  shot_noise_rate_hz and leak_jitter_fraction must be 0: both draw random numbers every frame.  max_iters:
+    the most sub-iterations (events of one polarity at one pixel) one frame may need.  Returns a DvsEmulator:
+    .emulate(frames, t) -> (t, x, y, p, t_s), .reset().  Events of one sub-iteration come out as all ON pixels in row-major
+    order, then all OFF pixels (the reference shuffles each such group of equal stamps); p is 1 for ON (the reference's +1) and 0
+    for OFF (its -1)."""
+    return DvsEmulator(h, w, device=device, pos_thres=pos_thres, neg_thres=neg_thres, cutoff_hz=cutoff_hz, leak_rate_hz=leak_rate_hz,
+                       noise_rate_array=noise_rate_array, refractory_period_s=refractory_period_s, shot_noise_rate_hz=shot_noise_rate_hz,
+                       leak_jitter_fraction=leak_jitter_fraction, max_iters=max_iters)
+
+
 def warp_window(trans, out_wh, frame_hw):
     """[x0, y0, w, h]: a window of the frame that contains every pixel crop_warp reads for this affine (host side, NumPy).  The
     corners of the output grid go through the inverse map exactly as the kernel derives it; the fixed-point coordinates deviate
