@@ -345,6 +345,49 @@ int32_t scpose_events_csv_parse(const uint8_t* data, int64_t n_bytes, int32_t de
                                 int64_t* t, int32_t* x, int32_t* y, int8_t* p, int64_t capacity, int64_t* count_status,
                                 void* workspace, size_t workspace_bytes, void* stream);
 
+/* Event files from the device (csrc/events_write.hip): the four columns -> the bytes of a text / CSV file or of AEDAT-2.0
+ * records, the way out that mirrors scpose_events_csv_parse.
+ *
+ * Text: a row is `t SEP a SEP b SEP p '\n'`, (a, b) = (x, y), or (y, x) with swap_xy != 0 (the reader's flag, so that
+ * parse(format(cols, swap), swap) == cols); every value as C's "%d" prints it; `"%d %d %d %d\n" % row` of v2e/v2e.py:write_text
+ * byte for byte.  The bytes lie inside the grammar scpose_events_csv_parse accepts.  Two calls, as scpose_events_count_frames +
+ * scpose_events_render: measure, read [n_bytes, status] back once, size the output, emit.
+ *   t, x, y, p   device i64 / i32 / i32 / i8, n rows each (n == 0: may be NULL)
+ *   sep          ' ' (32) or ',' (44)
+ *   measure      count_status device i64 [2] <- [n_bytes, 0]; n_bytes is 64-bit, a row takes 8 .. 50 bytes.  Leaves the tile
+ *                offsets in the workspace, which emit reads: the same columns, n and workspace go to both calls
+ *   emit         out device u8, 16-byte aligned, `capacity` bytes; count_status <- [n_bytes, status], status 0 or
+ *                SCPOSE_TEXT_CAPACITY when capacity < n_bytes: nothing is stored at or past `capacity`, the bytes below it are
+ *                the prefix of the text
+ *   workspace    caller-owned, 16-byte aligned, scpose_events_text_workspace_bytes(n)
+ *   tiling       tile_rows: rows per workgroup; scan_rows: rows per step of the offset scan (sizes at which tests look)
+ *
+ * AEDAT-2.0 (jAER): per event two big-endian 32-bit words, address = xf << 12 | yf << 22 | p << 11 computed in uint32 with
+ * xf = w - 1 - x, yf = h - 1 - y, then (int32) t in microseconds: the records of the reference's v2ecore/output/aedat2_output.py
+ * (AEDat2Output.appendEvents), which flips both axes for every size it takes.
+ *   h, w         h 1 .. 1024 (the 10 bits above bit 22), w 1 .. 1280 (the reference's widest sensor; from x = 1024 on the x field
+ *                shares bit 22 with y, in the reference's files as here)
+ *   out          device u8, 8-byte aligned, 8 * n bytes
+ *   count_status device i64 [3] <- [n, status, lead].  status bits: SCPOSE_AEDAT2_RANGE (some x outside [0, w), y outside [0, h)
+ *                or p outside {0, 1}), SCPOSE_AEDAT2_TIME (some t outside [0, 2^31): the reference's cast is undefined there);
+ *                with either set the records are unspecified.  lead: how many leading records start with the byte '#' (0x23:
+ *                yf in 140 .. 143); the reference drops exactly those from the first non-empty write to a file, and so does
+ *                the host writer (event_write.write_events_aedat2)
+ * Argument errors (null pointers with n > 0, n < 0, another separator, h outside 1 .. 1024 or w outside 1 .. 1280, a workspace that is too small)
+ * return -1 with a message before anything is launched.  No allocation, no synchronisation, no floating point; two calls on
+ * the same columns give bitwise equal bytes. */
+enum { SCPOSE_TEXT_CAPACITY = 1 };
+enum { SCPOSE_AEDAT2_RANGE = 1, SCPOSE_AEDAT2_TIME = 2 };
+int32_t scpose_events_text_tiling(int32_t* tile_rows, int32_t* scan_rows);
+int32_t scpose_events_text_workspace_bytes(int64_t n, size_t* bytes);
+int32_t scpose_events_text_measure(const int64_t* t, const int32_t* x, const int32_t* y, const int8_t* p, int64_t n,
+                                   int64_t* count_status, void* workspace, size_t workspace_bytes, void* stream);
+int32_t scpose_events_text_emit(const int64_t* t, const int32_t* x, const int32_t* y, const int8_t* p, int64_t n, int32_t sep,
+                                int32_t swap_xy, uint8_t* out, int64_t capacity, int64_t* count_status, void* workspace,
+                                size_t workspace_bytes, void* stream);
+int32_t scpose_events_aedat2_pack(const int64_t* t, const int32_t* x, const int32_t* y, const int8_t* p, int64_t n, int32_t h,
+                                  int32_t w, uint8_t* out, int64_t* count_status, void* stream);
+
 /* (ABI 7, additive) DVS emulator core on the device (csrc/dvs_emulator.hip): time-stamped grayscale uint8 frames -> an event
  * stream, in the columns scpose_events_frame_bounds / scpose_events_render take.  Restates EventEmulator._init / generate_events
  * of the reference's v2e/v2ecore/emulator.py (with lin_log, rescale_intensity_frame, low_pass_filter, subtract_leak_current,

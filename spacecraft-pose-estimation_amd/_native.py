@@ -23,6 +23,8 @@ DT_BF16, DT_F16 = 0, 1
 IN_F32_NCHW, IN_U8_NHWC = 0, 1
 CSV_UNSUPPORTED, CSV_CAPACITY = 1, 2
 DVS_CAPACITY, DVS_ITERS, DVS_TIME = 1, 2, 4
+TEXT_CAPACITY = 1
+AEDAT2_RANGE, AEDAT2_TIME = 1, 2
 ABI_VERSION = 7
 
 
@@ -115,6 +117,13 @@ SYMBOLS = {
     "scpose_events_csv_workspace_bytes": (c_int32, [c_int64, POINTER(c_size_t)]),
     "scpose_events_csv_parse": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "scpose_events_text_tiling": (c_int32, [POINTER(c_int32), POINTER(c_int32)]),
+    "scpose_events_text_workspace_bytes": (c_int32, [c_int64, POINTER(c_size_t)]),
+    "scpose_events_text_measure": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "scpose_events_text_emit": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64,
+                                          c_void_p, c_void_p, c_size_t, c_void_p]),
+    "scpose_events_aedat2_pack": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p,
+                                            c_void_p]),
     "scpose_dvs_state_bytes": (c_int32, [c_int32, c_int32, POINTER(c_size_t)]),
     "scpose_dvs_workspace_bytes": (c_int32, [c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
     "scpose_dvs_init": (c_int32, [c_void_p, c_void_p, c_double, POINTER(DvsParams), c_void_p]),

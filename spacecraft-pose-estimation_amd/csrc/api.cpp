@@ -169,6 +169,64 @@ extern "C" int32_t scpose_events_csv_parse(const uint8_t* data, int64_t n_bytes,
                                  static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
 }
 
+static const int64_t kMaxWriteEvents = (int64_t)1 << 38;      // one workgroup per 256 events, the grid below 2^31
+
+static int32_t text_args_ok(const char* who, const void* t, const void* x, const void* y, const void* p, int64_t n,
+                            const int64_t* count_status, const void* workspace, size_t workspace_bytes) {
+  SCP_REQUIRE(n >= 0 && n <= kMaxWriteEvents, "%s: n=%lld (0 .. 2^38)", who, (long long)n);
+  SCP_REQUIRE(count_status && ((t && x && y && p) || n == 0), "%s: null argument", who);
+  const size_t need = events_text_workspace_bytes(n);
+  SCP_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace of %zu bytes needed (got %zu)", who, need,
+              workspace ? workspace_bytes : (size_t)0);
+  SCP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: workspace must be 16-byte aligned", who);
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_events_text_tiling(int32_t* tile_rows, int32_t* scan_rows) {
+  SCP_REQUIRE(tile_rows && scan_rows, "events_text_tiling: null argument");
+  *tile_rows = events_text_tile_rows();
+  *scan_rows = events_text_scan_rows();
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_events_text_workspace_bytes(int64_t n, size_t* bytes) {
+  SCP_REQUIRE(bytes, "events_text_workspace_bytes: null argument");
+  SCP_REQUIRE(n >= 0 && n <= kMaxWriteEvents, "events_text_workspace_bytes: n=%lld (0 .. 2^38)", (long long)n);
+  *bytes = events_text_workspace_bytes(n);
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_events_text_measure(const int64_t* t, const int32_t* x, const int32_t* y, const int8_t* p, int64_t n,
+                                              int64_t* count_status, void* workspace, size_t workspace_bytes, void* stream) {
+  const int32_t rc = text_args_ok("events_text_measure", t, x, y, p, n, count_status, workspace, workspace_bytes);
+  if (rc != SCPOSE_OK) return rc;
+  return events_text_measure_launch(t, x, y, p, n, count_status, static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t scpose_events_text_emit(const int64_t* t, const int32_t* x, const int32_t* y, const int8_t* p, int64_t n,
+                                           int32_t sep, int32_t swap_xy, uint8_t* out, int64_t capacity, int64_t* count_status,
+                                           void* workspace, size_t workspace_bytes, void* stream) {
+  SCP_REQUIRE(sep == ' ' || sep == ',', "events_text_emit: sep=%d: the separator is ' ' (32) or ',' (44)", sep);
+  SCP_REQUIRE(capacity >= 0, "events_text_emit: capacity=%lld", (long long)capacity);
+  const int32_t rc = text_args_ok("events_text_emit", t, x, y, p, n, count_status, workspace, workspace_bytes);
+  if (rc != SCPOSE_OK) return rc;
+  SCP_REQUIRE(out || capacity == 0, "events_text_emit: null argument");
+  SCP_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0, "events_text_emit: out must be 16-byte aligned");
+  return events_text_emit_launch(t, x, y, p, n, sep, swap_xy != 0, out, capacity, count_status, static_cast<uint8_t*>(workspace),
+                                 static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t scpose_events_aedat2_pack(const int64_t* t, const int32_t* x, const int32_t* y, const int8_t* p, int64_t n,
+                                             int32_t h, int32_t w, uint8_t* out, int64_t* count_status, void* stream) {
+  // y has the 10 bits above bit 22; x starts at bit 12, and the reference's widest sensor (1280) already reaches into bit 22
+  SCP_REQUIRE(h >= 1 && h <= 1024 && w >= 1 && w <= 1280, "events_aedat2_pack: frame %dx%d (HxW) not supported: H 1 .. 1024, "
+              "W 1 .. 1280", h, w);
+  SCP_REQUIRE(n >= 0 && n <= kMaxWriteEvents, "events_aedat2_pack: n=%lld (0 .. 2^38)", (long long)n);
+  SCP_REQUIRE(count_status && ((t && x && y && p && out) || n == 0), "events_aedat2_pack: null argument");
+  SCP_REQUIRE((reinterpret_cast<uintptr_t>(out) & 7) == 0, "events_aedat2_pack: out must be 8-byte aligned");
+  return events_aedat2_pack_launch(t, x, y, p, n, h, w, out, count_status, static_cast<hipStream_t>(stream));
+}
+
 static int32_t dvs_check_params(const scpose_dvs_params* p, const char* who) {
   SCP_REQUIRE(p, "%s: null params", who);
   SCP_REQUIRE(p->h > 0 && p->w > 0 && (int64_t)p->h * p->w <= (1 << 24), "%s: bad shape h=%d w=%d", who, p->h, p->w);

@@ -249,6 +249,16 @@ int32_t events_bounds_midpoints_launch(const int64_t* t, const int64_t* bounds, 
 size_t events_csv_workspace_bytes(int64_t n_bytes);
 int32_t events_csv_parse_launch(const uint8_t* data, int64_t n_bytes, int ws_mode, int swap_xy, double t_div, int64_t* t, int32_t* x,
                                 int32_t* y, int8_t* p, int64_t capacity, int64_t* count_status, uint8_t* ws, hipStream_t stream);
+// events_write.hip: (t, x, y, p) -> event text / AEDAT-2.0 records
+int events_text_tile_rows();
+int events_text_scan_rows();
+size_t events_text_workspace_bytes(int64_t n);
+int32_t events_text_measure_launch(const int64_t* t, const int32_t* x, const int32_t* y, const int8_t* p, int64_t n,
+                                   int64_t* count_status, uint8_t* ws, hipStream_t stream);
+int32_t events_text_emit_launch(const int64_t* t, const int32_t* x, const int32_t* y, const int8_t* p, int64_t n, int sep, int swap_xy,
+                                uint8_t* out, int64_t capacity, int64_t* count_status, uint8_t* ws, hipStream_t stream);
+int32_t events_aedat2_pack_launch(const int64_t* t, const int32_t* x, const int32_t* y, const int8_t* p, int64_t n, int h, int w,
+                                  uint8_t* out, int64_t* count_status, hipStream_t stream);
 // dvs_emulator.hip: intensity frames -> event stream (v2e/v2ecore/emulator.py: EventEmulator.generate_events)
 size_t dvs_state_bytes(int h, int w);
 size_t dvs_workspace_bytes(int h, int w, int frames, int max_iters);

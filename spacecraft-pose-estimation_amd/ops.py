@@ -400,6 +400,79 @@ def parse_events_csv(data, delim_whitespace=False, swap_xy=False, microseconds_t
         return t[:rows].clone(), x[:rows].clone(), y[:rows].clone(), p[:rows].clone()
 
 
+def events_text_tiling():
+    """(rows per workgroup, rows per step of the offset scan) of the text formatter (csrc/events_write.hip)."""
+    a, b = c_int32(), c_int32()
+    nat.check(nat.lib().scpose_events_text_tiling(ctypes.byref(a), ctypes.byref(b)), "events_text_tiling")
+    return a.value, b.value
+
+
+def _event_columns(who, t, x, y, p):
+    """The four columns as contiguous device tensors of the dtypes the kernels read; their device and row count."""
+    _need_cuda(t, x, y, p)
+    for name, c, dt in (("t", t, torch.int64), ("x", x, torch.int32), ("y", y, torch.int32), ("p", p, torch.int8)):
+        if c.dtype != dt or c.dim() != 1:
+            raise ValueError("%s: %s must be a 1-d %s tensor (got %s %s)" % (who, name, dt, c.dtype, tuple(c.shape)))
+    n = int(t.numel())
+    if not (x.numel() == n and y.numel() == n and p.numel() == n):
+        raise ValueError("%s: the columns differ in length: %s" % (who, [int(c.numel()) for c in (t, x, y, p)]))
+    if not (x.device == t.device and y.device == t.device and p.device == t.device):
+        raise ValueError("%s: the columns live on different devices" % who)
+    return t.contiguous(), x.contiguous(), y.contiguous(), p.contiguous(), t.device, n
+
+
+def _sep_byte(sep):
+    b = sep.encode() if isinstance(sep, str) else bytes(sep)
+    if b not in (b" ", b","):
+        raise ValueError("format_events_text: sep must be ' ' or ',' (got %r)" % (sep,))
+    return b[0]
+
+
+def format_events_text(t, x, y, p, sep=" ", swap_xy=False):
+    """(t int64, x int32, y int32, p int8) device tensors -> a uint8 device tensor holding the rows as text, one
+    `t SEP x SEP y SEP p` line per event with every value printed as "%d" (csrc/events_write.hip): the inverse of
+    parse_events_csv, and byte for byte what `"%d %d %d %d\\n" % row` writes.  sep: ' ' or ','.  swap_xy: write y before x (the
+    reader's flag).  The tensor has exactly the text's length; one small read-back, [n_bytes, status], sizes it."""
+    sb = _sep_byte(sep)
+    t, x, y, p, dev, n = _event_columns("format_events_text", t, x, y, p)
+    lib = nat.lib()
+    ws = c_size_t()
+    nat.check(lib.scpose_events_text_workspace_bytes(n, ctypes.byref(ws)), "events_text_workspace_bytes")
+    with torch.cuda.device(dev):
+        work = torch.empty(ws.value, dtype=torch.uint8, device=dev)
+        cs = torch.empty(2, dtype=torch.int64, device=dev)
+        nat.check(lib.scpose_events_text_measure(_ptr(t), _ptr(x), _ptr(y), _ptr(p), n, _ptr(cs), _ptr(work), ws.value, _stream()),
+                  "events_text_measure")
+        n_bytes = int(cs.tolist()[0])                           # the one small read-back
+        out = torch.empty(n_bytes, dtype=torch.uint8, device=dev)
+        # capacity == n_bytes: the status word of emit cannot be set, and is not read back
+        nat.check(lib.scpose_events_text_emit(_ptr(t), _ptr(x), _ptr(y), _ptr(p), n, sb, int(bool(swap_xy)), _ptr(out), n_bytes,
+                                              _ptr(cs), _ptr(work), ws.value, _stream()), "events_text_emit")
+    return out
+
+
+def pack_events_aedat2(t, x, y, p, hw):
+    """(t int64 microseconds, x int32, y int32, p int8 in {0, 1}) device tensors -> (uint8 device tensor of 8 * n bytes, lead):
+    the AEDAT-2.0 records of the events for a sensor of hw = (height, width), two big-endian 32-bit words per event as the
+    reference's AEDat2Output.appendEvents packs them (both axes flipped), and the number of leading records whose first byte is
+    '#', which a writer drops at the start of a file (event_write.write_events_aedat2 does).  Raises ValueError when a
+    coordinate or polarity is out of range or a time stamp is outside [0, 2^31).  One small read-back, [n, status, lead]."""
+    h, w = int(hw[0]), int(hw[1])
+    t, x, y, p, dev, n = _event_columns("pack_events_aedat2", t, x, y, p)
+    lib = nat.lib()
+    with torch.cuda.device(dev):
+        out = torch.empty(8 * n, dtype=torch.uint8, device=dev)
+        cs = torch.empty(3, dtype=torch.int64, device=dev)
+        nat.check(lib.scpose_events_aedat2_pack(_ptr(t), _ptr(x), _ptr(y), _ptr(p), n, h, w, _ptr(out), _ptr(cs), _stream()),
+                  "events_aedat2_pack")
+        _, status, lead = cs.tolist()                           # the one small read-back
+    if status & nat.AEDAT2_RANGE:
+        raise ValueError("pack_events_aedat2: an event lies outside the %d x %d sensor, or a polarity is neither 0 nor 1" % (w, h))
+    if status & nat.AEDAT2_TIME:
+        raise ValueError("pack_events_aedat2: a time stamp is outside [0, 2^31) microseconds, which AEDAT-2.0 cannot hold")
+    return out, int(lead)
+
+
 class DvsEmulator:
     """Device DVS emulator (csrc/dvs_emulator.hip): see dvs_emulator().  The state lives in device memory between calls."""
 

@@ -1,0 +1,69 @@
+#!/usr/bin/env python3
+"""events_convert: an event text / CSV file into another event file, on the device.
+
+    python v2e/events_convert.py --events_file IN [--delim_whitespace] [--swap_xy] --output OUT [--width W --height H]
+
+IN is read by ops.parse_events_csv (csrc/events_csv.hip; --delim_whitespace and --swap_xy are e2v.py's flags of the same
+names) and the four columns go straight to one of the device writers (event_write), chosen by OUT's extension, without a host
+copy of the columns:
+    .csv     `t,x,y,p` lines without a header: what the reference's aedat_to_csv.py writes (to_csv(index=False, header=False))
+             and convert_aedats.py reads
+    .txt     `t x y p` lines without a header: the --delim_whitespace grammar
+    .aedat   AEDAT-2.0 for jAER; needs --width and --height, one of 346x260, 692x520, 1280x720, 640x480, 240x180, and time
+             stamps in microseconds
+The text forms write x before y whatever --swap_xy says: the flag describes IN.
+"""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+FORMATS = (".csv", ".txt", ".aedat")
+
+
+def convert_args(parser):
+    parser.add_argument("--events_file", type=str, required=True, help="event text file: t, x, y, p per line, '#' comments")
+    parser.add_argument("--delim_whitespace", action="store_true", default=False, help="fields are separated by blanks, not commas")
+    parser.add_argument("--swap_xy", action="store_true", default=False, help="the second column of the input is y, the third x")
+    parser.add_argument("--output", type=str, required=True, help="file to write; the extension picks the format: %s" % ", ".join(FORMATS))
+    parser.add_argument("--width", type=int, default=None, help="sensor width in pixels (.aedat only)")
+    parser.add_argument("--height", type=int, default=None, help="sensor height in pixels (.aedat only)")
+    return parser
+
+
+def main(argv=None):
+    args = convert_args(argparse.ArgumentParser(description="Convert an event text file on the device.")).parse_args(argv)
+    ext = os.path.splitext(args.output)[1].lower()
+    if ext not in FORMATS:
+        sys.exit("events_convert: --output %s: the extension must be one of %s" % (args.output, ", ".join(FORMATS)))
+    if ext == ".aedat" and (args.width is None or args.height is None):
+        sys.exit("events_convert: an .aedat output needs --width and --height")
+    if not os.path.isfile(args.events_file):
+        sys.exit("events_convert: --events_file %s is not a file" % args.events_file)
+    import scpose  # noqa: F401
+    from importlib import import_module
+    ew = import_module("spacecraft-pose-estimation_amd.event_write")
+    if ext == ".aedat":
+        try:
+            ew.check_aedat2_size((args.height, args.width))
+        except ValueError as e:
+            sys.exit("events_convert: %s" % e)
+    ops = import_module("spacecraft-pose-estimation_amd.ops")
+    t, x, y, p = ops.parse_events_csv(args.events_file, delim_whitespace=args.delim_whitespace, swap_xy=args.swap_xy)
+    if ext == ".aedat":
+        try:
+            n = ew.write_events_aedat2(args.output, t, x, y, p, (args.height, args.width))
+        except ValueError as e:
+            sys.exit("events_convert: %s" % e)
+        print("events_convert: %d events -> %d AEDAT-2.0 records in %s" % (int(t.numel()), n, args.output))
+    else:
+        n = ew.write_events_text(args.output, t, x, y, p, sep="," if ext == ".csv" else " ")
+        print("events_convert: %d events -> %d bytes in %s" % (int(t.numel()), n, args.output))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """v2e: DVS events from intensity frames, the emulator core of the reference's v2e/v2e.py on the MI355X HIP path.
 
-    python v2e/v2e.py --input DIR --input_frame_rate 100 --dvs_params clean --output_folder OUT --dvs_text events
+    python v2e/v2e.py --input DIR --input_frame_rate 100 --dvs_params clean --output_folder OUT --dvs_text events [--events_aedat2 events]
 
 reads the image files of DIR in name order (PIL; grayscale as is, RGB reduced with OpenCV's 8-bit BGR2GRAY weights
 (4899 R + 9617 G + 1868 B + 8192) >> 14, which is what the reference's cv2.imread + cvtColor gives), stamps frame k with
@@ -10,10 +10,14 @@ k / input_frame_rate seconds, runs the emulator on the device (csrc/dvs_emulator
 microseconds (the reference's h5 rule uint32(float32(t_s) * 1e6)), p = 1 for ON and 0 for OFF.  That is the grammar both
 ops.parse_events_csv(..., delim_whitespace=True) and the reference's e2v.py reader (pandas, comment='#') take.  Two deviations
 from the reference's DVSTextOutput, which writes float seconds and the constant polarity 1: integer microseconds survive the
-readers' cast to int64, and the real polarity is written.
+readers' cast to int64, and the real polarity is written.  The text is formatted on the device and streamed to the file
+(event_write.write_events_text); write_text below states the same bytes in Python.  --events_aedat2 NAME adds
+<output_folder>/<NAME>.aedat, the AEDAT-2.0 file the reference's AEDat2Output writes for jAER (same records, a header without
+date and user lines), for the reference's five sensor sizes.
 
-Only the emulator core exists here.  SloMo interpolation, video input / output, the h5 and AEDAT2 writers, shot noise and leak
-jitter do not: their arguments are refused by name, not ignored.  --disable_slomo is accepted (it asks for what happens anyway).
+Only the emulator core and these two writers exist here.  SloMo interpolation, video input / output, the h5 writer, the
+reference's --dvs_aedat2 and --ddd_output, shot noise and leak jitter do not: their arguments are refused by name, not ignored.
+--disable_slomo is accepted (it asks for what happens anyway).
 """
 import argparse
 import os
@@ -30,8 +34,10 @@ REFUSED = {
     "video files are neither read nor written here (give a directory of image files with --input)":
         ("--start_time", "--stop_time", "--dvs_vid", "--dvs_vid_full_scale", "--dvs_exposure", "--avi_frame_rate", "--crop",
          "--synthetic_input", "--skip_video_output"),
-    "the h5 and AEDAT2 writers are not part of this emulator (use --dvs_text)":
-        ("--dvs_h5", "--dvs_aedat2", "--ddd_output"),
+    "the h5 writer is not part of this emulator (use --dvs_text)":
+        ("--dvs_h5", "--ddd_output"),
+    "the AEDAT-2.0 file is written by --events_aedat2 NAME here":
+        ("--dvs_aedat2",),
     "the DVS model state display is not part of this emulator":
         ("--show_dvs_model_state", "--no_preview"),
 }
@@ -55,6 +61,9 @@ def v2e_args(parser):
     parser.add_argument("--disable_slomo", action="store_true", default=False, help="accepted: SloMo never runs here")
     parser.add_argument("--output_folder", "-o", type=str, default=".", help="where the event text file goes")
     parser.add_argument("--dvs_text", type=str, required=True, help="name of the event text file ('.txt' is added when missing)")
+    parser.add_argument("--events_aedat2", type=str, default=None,
+                        help="name of an AEDAT-2.0 file for jAER ('.aedat' is added when the name has no extension); frames of "
+                             "346x260, 692x520, 1280x720, 640x480 or 240x180 only")
     return parser
 
 
@@ -112,9 +121,14 @@ def model_params(args):
     return p
 
 
+TEXT_HEADER = "#!events.txt\n# DVS events from the device emulator\n# format: time (integer microseconds), x, y, polarity (0=off, 1=on)\n"
+
+
 def write_text(path, t, x, y, p):
+    """The event text file stated in Python, from host columns: the bytes event_write.write_events_text(path, ..., sep=" ",
+    header=TEXT_HEADER) makes on the device.  main() does not come through here; tests compare the two."""
     with open(path, "w") as f:
-        f.write("#!events.txt\n# DVS events from the device emulator\n# format: time (integer microseconds), x, y, polarity (0=off, 1=on)\n")
+        f.write(TEXT_HEADER)
         for row in zip(t.tolist(), x.tolist(), y.tolist(), p.tolist()):
             f.write("%d %d %d %d\n" % row)
 
@@ -131,9 +145,15 @@ def main(argv=None):
     import scpose  # noqa: F401
     from importlib import import_module
     de = import_module("spacecraft-pose-estimation_amd.dvs_emulator")
+    ew = import_module("spacecraft-pose-estimation_amd.event_write")
     p = model_params(args)
     frames = read_frames(args.input)
     f, h, w = frames.shape
+    if args.events_aedat2 is not None:
+        try:
+            ew.check_aedat2_size((h, w))
+        except ValueError as e:
+            sys.exit("v2e: --events_aedat2: %s" % e)
     de.validate(h, w, cutoff_hz=p["cutoff_hz"], leak_rate_hz=p["leak_rate_hz"], refractory_period_s=p["refractory_period_s"],
                 shot_noise_rate_hz=p["shot_noise_rate_hz"], leak_jitter_fraction=p["leak_jitter_fraction"], max_iters=args.max_iters)
     pos, neg, noise = de.draw_pixel_arrays(h, w, p["pos_thres"], p["neg_thres"], p["sigma_thres"], p["noise_rate_cov_decades"],
@@ -145,8 +165,12 @@ def main(argv=None):
     os.makedirs(args.output_folder, exist_ok=True)
     name = args.dvs_text if args.dvs_text.endswith(".txt") else args.dvs_text + ".txt"
     path = os.path.join(args.output_folder, name)
-    write_text(path, t.cpu().numpy(), x.cpu().numpy(), y.cpu().numpy(), pol.cpu().numpy())
+    ew.write_events_text(path, t, x, y, pol, sep=" ", header=TEXT_HEADER.encode())
     print("v2e: %d frames of %d x %d -> %d events (%d ON) in %s" % (f, w, h, int(t.numel()), int(pol.sum().item()), path))
+    if args.events_aedat2 is not None:
+        name = args.events_aedat2 if os.path.splitext(args.events_aedat2)[1] else args.events_aedat2 + ".aedat"
+        path = os.path.join(args.output_folder, name)
+        print("v2e: %d AEDAT-2.0 records in %s" % (ew.write_events_aedat2(path, t, x, y, pol, (h, w)), path))
     return 0
 
 
