@@ -72,6 +72,21 @@ inline FastDiv make_fastdiv(uint32_t d) {
   return f;
 }
 
+// Carves one caller-owned workspace into consecutive 256-byte aligned regions.  base == nullptr only adds the sizes up: a
+// *_workspace_bytes entry point and its launch run the same carving function, so the two cannot disagree.
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+struct Carve {
+  uint8_t* base;
+  size_t off = 0;
+  template <class T>
+  T* take(size_t count) {
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += align256(count * sizeof(T));
+    return p;
+  }
+  size_t bytes() const { return off; }
+};
+
 // ---- 3x3 / 1x1 implicit-GEMM convolution ---------------------------------------------------
 // Device-side description of one convolution launch.  All tensors are "blocked":
 // [N][C/8][H][W][8] 16-bit elements.

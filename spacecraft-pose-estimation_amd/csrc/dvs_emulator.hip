@@ -13,30 +13,28 @@
 //                   state, and writes the tile's count of every group g = 2 * i + (0 ON, 1 OFF) into the group-major table
 //                   table[g * tiles + tile].  Pixels are tiled in row-major order, so an exclusive scan of that table is the
 //                   offset of the tile's first event of group g in the reference's unshuffled order
-//   scan_*          exclusive int32 scan of the first 2 * num_iters * tiles entries (the length is read on the device); the
-//                   one-block middle pass also advances the running event count of the call and raises the status bits
+//   scan_*          scan_device.h's exclusive sum scan of the first 2 * num_iters * tiles entries.  That length is only known on
+//                   the device: the launch covers 2 * max_iters * tiles entries and the workgroups past the length return at
+//                   once.  The one-workgroup middle pass also advances the call's running event count and raises the status bits
 //   scatter_kernel  the same walk again, now writing timestamp_mem and base; an event's rank inside its tile comes from the
 //                   ballot of its group, so the output order is a fixed function of the input
 // No floating-point atomic, no global atomic other than the integer maximum; two runs are bitwise equal.
 #include "common.h"
+#include "scan_device.h"
 
 namespace scpose {
 
 namespace {
 
 constexpr int kThreads = 256;
+static_assert(kThreads == kScanThreads, "the scan bodies of scan_device.h run in the workgroups of this file");
 constexpr int kWave = 64;
-constexpr int kScanItems = 16;
-constexpr int kScanTile = kThreads * kScanItems;
 
 struct DvsHeader {        // first 256 bytes of the state
   double t_prev;
   int32_t initialised;
   int32_t pad;
 };
-constexpr size_t kHeaderBytes = 256;
-
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct StateView {
   DvsHeader* hdr;
@@ -44,21 +42,18 @@ struct StateView {
   int32_t *on, *off;
 };
 
-inline size_t plane_bytes(int h, int w) { return align256((size_t)h * w * 4); }
-
-inline StateView state_view(void* state, int h, int w) {
-  uint8_t* p = static_cast<uint8_t*>(state);
-  const size_t pl = plane_bytes(h, w);
-  StateView v;
-  v.hdr = reinterpret_cast<DvsHeader*>(p);
-  p += kHeaderBytes;
-  v.base = reinterpret_cast<float*>(p); p += pl;
-  v.lp0 = reinterpret_cast<float*>(p); p += pl;
-  v.lp1 = reinterpret_cast<float*>(p); p += pl;
-  v.tmem = reinterpret_cast<float*>(p); p += pl;
-  v.on = reinterpret_cast<int32_t*>(p); p += pl;
-  v.off = reinterpret_cast<int32_t*>(p);
-  return v;
+// the state: a 256-byte header and six 256-byte aligned planes (ops.DvsEmulator.state() reads the first four)
+inline size_t state_view(void* state, int h, int w, StateView* v) {
+  const size_t hw = (size_t)h * w;
+  Carve c{static_cast<uint8_t*>(state)};
+  v->hdr = c.take<DvsHeader>(1);
+  v->base = c.take<float>(hw);
+  v->lp0 = c.take<float>(hw);
+  v->lp1 = c.take<float>(hw);
+  v->tmem = c.take<float>(hw);
+  v->on = c.take<int32_t>(hw);
+  v->off = c.take<int32_t>(hw);
+  return c.bytes();
 }
 
 struct Workspace {
@@ -72,14 +67,13 @@ struct Workspace {
 inline Workspace workspace_view(uint8_t* ws, int h, int w, int frames, int max_iters) {
   const int64_t tiles = ((int64_t)h * w + kWave - 1) / kWave;
   const int64_t len = 2 * (int64_t)max_iters * tiles;
-  const int64_t nb = (len + kScanTile - 1) / kScanTile;
+  Carve c{ws};
   Workspace v;
-  size_t o = 0;
-  v.nit = reinterpret_cast<int32_t*>(ws + o); o += align256((size_t)(frames > 0 ? frames : 1) * 4);
-  v.fbase = reinterpret_cast<int64_t*>(ws + o); o += align256((size_t)(frames + 1) * 8);
-  v.table = reinterpret_cast<int32_t*>(ws + o); o += align256((size_t)len * 4);
-  v.aggr = reinterpret_cast<int32_t*>(ws + o); o += align256((size_t)nb * 4);
-  v.bytes = o;
+  v.nit = c.take<int32_t>(frames > 0 ? frames : 1);
+  v.fbase = c.take<int64_t>(frames + 1);
+  v.table = c.take<int32_t>(len);
+  v.aggr = c.take<int32_t>((len + kScanTile - 1) / kScanTile);
+  v.bytes = c.bytes();
   return v;
 }
 
@@ -243,22 +237,8 @@ __global__ __launch_bounds__(kThreads) void count_kernel(StateView s, DevParams 
   }
 }
 
-// ---- exclusive int32 sum scan of table[0 .. 2 * nit[f] * tiles), in place; the length is only known on the device
-__device__ int32_t block_inclusive_sum(int32_t v, int32_t* sm) {
-  const int tid = threadIdx.x;
-  sm[tid] = v;
-  __syncthreads();
-  for (int off = 1; off < kThreads; off <<= 1) {
-    const int32_t a = tid >= off ? sm[tid - off] : 0;
-    __syncthreads();
-    sm[tid] += a;
-    __syncthreads();
-  }
-  const int32_t r = sm[tid];
-  __syncthreads();
-  return r;
-}
-
+// ---- exclusive int32 sum scan of table[0 .. 2 * nit[f] * tiles), in place.  Every workgroup reads the length on the device; one
+// whose tile starts at or past it returns before any barrier, all of its threads alike
 __device__ __forceinline__ int64_t scan_len(const int32_t* nit, int f, int tiles, int max_iters, const int64_t* counts) {
   const int n = nit[f];
   if (n > max_iters || (counts[1] & (SCPOSE_DVS_ITERS | SCPOSE_DVS_TIME))) return 0;
@@ -270,15 +250,8 @@ __global__ __launch_bounds__(kThreads) void scan_reduce_kernel(const int32_t* __
                                                                int32_t* __restrict__ aggr) {
   __shared__ int32_t sm[kThreads];
   const int64_t len = scan_len(nit, f, tiles, max_iters, counts);
-  const int64_t base = (int64_t)blockIdx.x * kScanTile;
-  if (base >= len) return;
-  int32_t acc = 0;
-  for (int k = 0; k < kScanItems; ++k) {
-    const int64_t j = base + k * kThreads + threadIdx.x;
-    if (j < len) acc += table[j];
-  }
-  const int32_t tot = block_inclusive_sum(acc, sm);
-  if (threadIdx.x == kThreads - 1) aggr[blockIdx.x] = tot;
+  if ((int64_t)blockIdx.x * kScanTile >= len) return;
+  scan_tile_reduce<0, false>(table, len, aggr, sm);
 }
 
 // one workgroup: aggr[b] <- sum of aggr[0 .. b - 1]; then the call's running event count and the status bits
@@ -287,23 +260,10 @@ __global__ __launch_bounds__(kThreads) void scan_aggr_kernel(int32_t* __restrict
                                                              int64_t* __restrict__ counts) {
   __shared__ int32_t sm[kThreads];
   const int64_t len = scan_len(nit, f, tiles, max_iters, counts);
-  const int64_t nb = (len + kScanTile - 1) / kScanTile;
-  int32_t carry = 0;
-  for (int64_t b0 = 0; b0 < nb; b0 += kThreads) {
-    const int64_t b = b0 + threadIdx.x;
-    const int32_t v = b < nb ? aggr[b] : 0;
-    const int32_t inc = block_inclusive_sum(v, sm);
-    sm[threadIdx.x] = inc;
-    __syncthreads();
-    const int32_t before = threadIdx.x == 0 ? carry : carry + sm[threadIdx.x - 1];
-    const int32_t total = sm[kThreads - 1];
-    __syncthreads();
-    if (b < nb) aggr[b] = before;
-    carry += total;
-  }
+  const int32_t events = scan_aggregates<0>(aggr, (len + kScanTile - 1) / kScanTile, sm);
   __syncthreads();                                         // every thread has read the status word before it changes
   if (threadIdx.x == 0) {
-    const int64_t after = fbase[f] + carry;
+    const int64_t after = fbase[f] + events;
     fbase[f + 1] = after;
     int64_t status = counts[1];
     if (nit[f] > max_iters) status |= SCPOSE_DVS_ITERS;
@@ -313,32 +273,13 @@ __global__ __launch_bounds__(kThreads) void scan_aggr_kernel(int32_t* __restrict
   }
 }
 
-__global__ __launch_bounds__(kThreads) void scan_apply_kernel(int32_t* __restrict__ table, const int32_t* __restrict__ nit, int f,
-                                                              int tiles, int max_iters, const int64_t* __restrict__ counts,
+__global__ __launch_bounds__(kThreads) void scan_apply_kernel(int32_t* table, const int32_t* __restrict__ nit, int f, int tiles,
+                                                              int max_iters, const int64_t* __restrict__ counts,
                                                               const int32_t* __restrict__ aggr) {
   __shared__ int32_t sm[kThreads];
   const int64_t len = scan_len(nit, f, tiles, max_iters, counts);
-  const int64_t first = (int64_t)blockIdx.x * kScanTile;
-  if (first >= len) return;
-  const int64_t base = first + (int64_t)threadIdx.x * kScanItems;
-  int32_t v[kScanItems];
-  int32_t acc = 0;
-#pragma unroll
-  for (int k = 0; k < kScanItems; ++k) {
-    const int64_t j = base + k;
-    v[k] = j < len ? table[j] : 0;
-    acc += v[k];
-  }
-  const int32_t inc = block_inclusive_sum(acc, sm);
-  sm[threadIdx.x] = inc;
-  __syncthreads();
-  int32_t run = aggr[blockIdx.x] + (threadIdx.x == 0 ? 0 : sm[threadIdx.x - 1]);
-#pragma unroll
-  for (int k = 0; k < kScanItems; ++k) {
-    const int64_t j = base + k;
-    if (j < len) table[j] = run;
-    run += v[k];
-  }
+  if ((int64_t)blockIdx.x * kScanTile >= len) return;
+  scan_tile_apply<0, false, true>(table, table, len, aggr, sm);
 }
 
 struct OutColumns {
@@ -407,13 +348,17 @@ __global__ void finish_kernel(DvsHeader* hdr, const double* __restrict__ t, int 
 
 }  // namespace
 
-size_t dvs_state_bytes(int h, int w) { return kHeaderBytes + 6 * plane_bytes(h, w); }
+size_t dvs_state_bytes(int h, int w) {
+  StateView v;
+  return state_view(nullptr, h, w, &v);
+}
 
 size_t dvs_workspace_bytes(int h, int w, int frames, int max_iters) { return workspace_view(nullptr, h, w, frames, max_iters).bytes; }
 
 int32_t dvs_init_launch(void* state, const uint8_t* frame0, double t0, int h, int w, const float* lut, double refractory_period_s,
                         hipStream_t stream) {
-  const StateView s = state_view(state, h, w);
+  StateView s;
+  state_view(state, h, w, &s);
   const int hw = h * w;
   hipLaunchKernelGGL(init_kernel, dim3((hw + kThreads - 1) / kThreads), dim3(kThreads), 0, stream, s.hdr, s.base, s.lp0, s.lp1, s.tmem,
                      frame0, lut, hw, t0, (float)refractory_period_s);
@@ -425,7 +370,8 @@ int32_t dvs_emulate_launch(void* state, const uint8_t* frames, const double* t, 
                            int64_t* t_us, int32_t* x, int32_t* y, int8_t* pol, int64_t capacity, int64_t* counts, uint8_t* ws,
                            hipStream_t stream) {
   const int h = prm.h, w = prm.w, hw = h * w;
-  const StateView s = state_view(state, h, w);
+  StateView s;
+  state_view(state, h, w, &s);
   const Workspace wk = workspace_view(ws, h, w, n_frames, prm.max_iters);
   DevParams p{};
   p.hw = hw; p.w = w;

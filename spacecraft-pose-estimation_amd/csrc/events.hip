@@ -53,6 +53,15 @@ __global__ __launch_bounds__(256) void events_frame_bounds_kernel(const int64_t*
 
 struct U32x3 { uint32_t a, b, c; };
 
+// four gray pixels as the 12 bytes of four RGB pixels with equal channels: one store
+__device__ __forceinline__ U32x3 gray4_to_rgb(uint32_t g0, uint32_t g1, uint32_t g2, uint32_t g3) {
+  U32x3 o;
+  o.a = g0 * 0x010101u | (g1 << 24);
+  o.b = g1 * 0x0101u | (g2 << 16) | (g2 << 24);
+  o.c = g2 | (g3 * 0x01010100u);
+  return o;
+}
+
 template <bool FOLD>
 __global__ __launch_bounds__(kEvThreads) void events_accumulate_kernel(
     const int32_t* __restrict__ ex, const int32_t* __restrict__ ey, const void* __restrict__ ep, int p_bytes,
@@ -119,13 +128,7 @@ __global__ __launch_bounds__(kEvThreads) void events_accumulate_kernel(
       const int4 c = *reinterpret_cast<const int4*>(cnt + i);
       const uint32_t g0 = gray(c.x), g1 = gray(c.y), g2 = gray(c.z), g3 = gray(c.w);
       if (plane) *reinterpret_cast<uint32_t*>(plane + pix0 + i) = g0 | (g1 << 8) | (g2 << 16) | (g3 << 24);
-      if (rgb) {
-        U32x3 o;
-        o.a = g0 * 0x010101u | (g1 << 24);
-        o.b = g1 * 0x0101u | (g2 << 16) | (g2 << 24);
-        o.c = g2 | (g3 * 0x01010100u);
-        *reinterpret_cast<U32x3*>(rgb + (pix0 + i) * 3) = o;
-      }
+      if (rgb) *reinterpret_cast<U32x3*>(rgb + (pix0 + i) * 3) = gray4_to_rgb(g0, g1, g2, g3);
     }
   } else {
     for (int i = tid; i < npx; i += kEvThreads) {
@@ -182,11 +185,7 @@ __global__ __launch_bounds__(256) void events_undistort_kernel(const uint8_t* __
     }
     uint8_t* o = out + ((size_t)f * npix + pix) * 3;
     if (PX == 4) {
-      U32x3 w;
-      w.a = g[0] * 0x010101u | (g[1] << 24);
-      w.b = g[1] * 0x0101u | (g[2] << 16) | (g[2] << 24);
-      w.c = g[2] | (g[3] * 0x01010100u);
-      *reinterpret_cast<U32x3*>(o) = w;
+      *reinterpret_cast<U32x3*>(o) = gray4_to_rgb(g[0], g[1], g[2], g[3]);
     } else {
       o[0] = (uint8_t)g[0]; o[1] = (uint8_t)g[0]; o[2] = (uint8_t)g[0];
     }

@@ -10,7 +10,7 @@
 //               every line end.  A line is a ROW when its first byte that is not a space / tab is none of '\n', '\r', '#'.
 //   csv_count_kernel   a tile of 4096 bytes (+ 256 bytes of halo) goes through LDS; the thread that owns a line end classifies
 //                      the line that starts after it; rows per tile
-//   csv_scan_kernel    exclusive int64 scan of the tile counts (one workgroup), the total
+//   csv_scan_kernel    scan_device.h's tile-count scan: int64 offsets of the tiles (one workgroup), the total
 //   csv_parse_kernel   the same classification, an in-tile exclusive scan of the per-thread row counts, then the owner of a row
 //                      walks its line -- from LDS while it stays inside tile + halo, from global memory past that -- splits
 //                      the four fields, converts and stores the row at its final index: file order, no compaction pass, no
@@ -24,12 +24,14 @@
 // Everything is integer work on fixed positions (the optional time-stamp division is one IEEE float64 division per row): two
 // runs on the same bytes are bitwise equal.
 #include "common.h"
+#include "scan_device.h"
 
 namespace scpose {
 
 namespace {
 
 constexpr int kThreads = 256;
+static_assert(kThreads == kScanThreads, "the scan bodies of scan_device.h run in the workgroups of this file");
 constexpr int kPerThread = 16;
 constexpr int kTile = kThreads * kPerThread;   // 4096 bytes of text per workgroup
 constexpr int kHalo = 256;                     // bytes after the tile kept in LDS: a line that starts in the tile ends there
@@ -41,7 +43,6 @@ constexpr int kLongShift = 8;                  // bit (8 + c): a field of more t
 constexpr int kMaxFloatDigits = 15;
 constexpr int64_t kMaxLine = 65536;            // one thread walks a line: a longer walk (blanks, digits) stops and is unsupported
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 inline int64_t tiles_of(int64_t n) { return n > 0 ? (n + kTile - 1) / kTile : 1; }
 
 // tile + halo -> LDS, 16 bytes per load; bytes at and past n read as '\n'
@@ -118,21 +119,6 @@ __device__ __forceinline__ uint32_t thread_rows(const Reader& rd, const uint8_t*
   return mask;
 }
 
-__device__ int32_t block_inclusive_sum(int32_t v, int32_t* s) {      // 256 threads, Hillis-Steele in LDS
-  const int tid = threadIdx.x;
-  s[tid] = v;
-  __syncthreads();
-  for (int off = 1; off < kThreads; off <<= 1) {
-    const int32_t a = tid >= off ? s[tid - off] : 0;
-    __syncthreads();
-    s[tid] += a;
-    __syncthreads();
-  }
-  const int32_t r = s[tid];
-  __syncthreads();
-  return r;
-}
-
 __global__ __launch_bounds__(kThreads) void csv_count_kernel(const uint8_t* __restrict__ data, int64_t n, int ws_mode,
                                                              int32_t* __restrict__ tile_rows) {
   __shared__ __attribute__((aligned(16))) uint8_t s[kStage];
@@ -142,7 +128,7 @@ __global__ __launch_bounds__(kThreads) void csv_count_kernel(const uint8_t* __re
   const Reader rd{s, data, base, n};
   uint32_t flags = 0;
   const int32_t rows = __popc(thread_rows(rd, s, base, ws_mode != 0, flags));
-  const int32_t inc = block_inclusive_sum(rows, sc);
+  const int32_t inc = block_inclusive_scan<0>(rows, sc);
   if (threadIdx.x == kThreads - 1) tile_rows[blockIdx.x] = inc;
 }
 
@@ -150,19 +136,8 @@ __global__ __launch_bounds__(kThreads) void csv_count_kernel(const uint8_t* __re
 __global__ __launch_bounds__(kThreads) void csv_scan_kernel(const int32_t* __restrict__ tile_rows, int64_t nb,
                                                             int64_t* __restrict__ tile_off, int64_t* __restrict__ total) {
   __shared__ int32_t sc[kThreads];
-  int64_t carry = 0;
-  for (int64_t b0 = 0; b0 < nb; b0 += kThreads) {
-    const int64_t b = b0 + threadIdx.x;
-    const int32_t v = b < nb ? tile_rows[b] : 0;
-    const int32_t inc = block_inclusive_sum(v, sc);       // at most 256 * 4097: fits int32
-    sc[threadIdx.x] = inc;
-    __syncthreads();
-    const int32_t chunk = sc[kThreads - 1];
-    __syncthreads();
-    if (b < nb) tile_off[b] = carry + inc - v;
-    carry += chunk;
-  }
-  if (threadIdx.x == 0) total[0] = carry;
+  const int64_t rows = scan_tile_counts(tile_rows, nb, tile_off, sc);      // a step sums at most 256 * 4097: fits int32
+  if (threadIdx.x == 0) total[0] = rows;
 }
 
 // one field: [+-]? digits [. digits] | [+-]? . digits.  p is left on the first byte after it.  The value is the integer part
@@ -213,7 +188,7 @@ __global__ __launch_bounds__(kThreads) void csv_parse_kernel(const uint8_t* __re
   uint32_t flags = 0;
   uint32_t mask = thread_rows(rd, s, base, ws, flags);
   const int32_t rows = __popc(mask);
-  int64_t row = tile_off[blockIdx.x] + block_inclusive_sum(rows, sc) - rows;
+  int64_t row = tile_off[blockIdx.x] + block_inclusive_scan<0>(rows, sc) - rows;
   const int64_t mine = base + (int64_t)threadIdx.x * kPerThread;
   while (mask) {
     const int bit = __ffs(mask) - 1;
@@ -271,32 +246,33 @@ __global__ void csv_finish_kernel(const int64_t* __restrict__ total, const uint3
 
 struct CsvPlan {
   int64_t nb;
-  size_t off_rows, off_off, off_words, bytes;
+  int32_t* tile_rows;
+  int64_t *tile_off, *total;                    // total: 256 bytes, the int64 total and the uint32 flags
+  size_t bytes;
 };
 
-CsvPlan csv_plan(int64_t n_bytes) {
+CsvPlan csv_plan(int64_t n_bytes, uint8_t* wsp) {
   CsvPlan p{};
   p.nb = tiles_of(n_bytes);
-  size_t o = 0;
-  p.off_rows = o; o += align256((size_t)p.nb * 4);
-  p.off_off = o; o += align256((size_t)p.nb * 8);
-  p.off_words = o; o += 256;                    // int64 total, uint32 flags
-  p.bytes = o;
+  Carve c{wsp};
+  p.tile_rows = c.take<int32_t>(p.nb);
+  p.tile_off = c.take<int64_t>(p.nb);
+  p.total = c.take<int64_t>(32);
+  p.bytes = c.bytes();
   return p;
 }
 
 }  // namespace
 
-size_t events_csv_workspace_bytes(int64_t n_bytes) { return csv_plan(n_bytes).bytes; }
+size_t events_csv_workspace_bytes(int64_t n_bytes) { return csv_plan(n_bytes, nullptr).bytes; }
 
 int32_t events_csv_parse_launch(const uint8_t* data, int64_t n_bytes, int ws_mode, int swap_xy, double t_div, int64_t* t, int32_t* x,
                                 int32_t* y, int8_t* p, int64_t capacity, int64_t* count_status, uint8_t* wsp, hipStream_t stream) {
-  const CsvPlan pl = csv_plan(n_bytes);
-  int32_t* tile_rows = reinterpret_cast<int32_t*>(wsp + pl.off_rows);
-  int64_t* tile_off = reinterpret_cast<int64_t*>(wsp + pl.off_off);
-  int64_t* total = reinterpret_cast<int64_t*>(wsp + pl.off_words);
-  uint32_t* flags = reinterpret_cast<uint32_t*>(wsp + pl.off_words + 8);
-  SCP_CHECK_HIP(hipMemsetAsync(wsp + pl.off_words, 0, 256, stream));
+  const CsvPlan pl = csv_plan(n_bytes, wsp);
+  int32_t* tile_rows = pl.tile_rows;
+  int64_t *tile_off = pl.tile_off, *total = pl.total;
+  uint32_t* flags = reinterpret_cast<uint32_t*>(total + 1);
+  SCP_CHECK_HIP(hipMemsetAsync(total, 0, 256, stream));
   hipLaunchKernelGGL(csv_count_kernel, dim3((unsigned)pl.nb), dim3(kThreads), 0, stream, data, n_bytes, ws_mode, tile_rows);
   hipLaunchKernelGGL(csv_scan_kernel, dim3(1), dim3(kThreads), 0, stream, tile_rows, pl.nb, tile_off, total);
   hipLaunchKernelGGL(csv_parse_kernel, dim3((unsigned)pl.nb), dim3(kThreads), 0, stream, data, n_bytes, ws_mode, t_div, tile_off,

@@ -13,10 +13,10 @@
 //   area_id_kernel      per event its area (Python floor division and negative wraparound on the (1 + W // D) x (1 + H // D)
 //                       grid); a coordinate off that grid sets the status word (a plain store of 1: no order to race on)
 //   rs_*                stable LSD radix sort of (area, index), 8 bits per pass: per-tile digit counts in LDS, one exclusive
-//                       scan of the (digit, tile) table, a scatter whose in-tile ranks come from ballots -- stable, no global
-//                       atomic, so the permutation is the same on every run
+//                       sum scan (scan_device.h) of the digit-major (digit, tile) table, a scatter whose in-tile ranks come from
+//                       ballots -- stable, no global atomic, so the permutation is the same on every run
 //   area_g_kernel       g from the sorted order: the M-th occurrence of area(j) is M - 1 places further in j's run
-//   scan_* (min, REV)   next[s] = suffix minimum of g, clamped to n - 1 (an absorbing node)
+//   scan_* (min, REV)   next[s] = suffix minimum of g, clamped to n - 1 (an absorbing node): the same device-wide scan
 //   area_double_kernel  J_l = next^(2^l): L doubling passes, 2^L > the frame-count bound (n - 2) / (M - 1)
 //   area_count_kernel   one thread: F = the number of chain steps from 0 that stay below n - 1, found with the tables top
 //                       down (and the chain's nodes every 2^L steps, when L had to be capped)
@@ -24,108 +24,45 @@
 // Every output is an integer and every step is a fixed function of the input: two runs are bitwise equal.
 // tests/event_exposure_restated.py restates both the serial loop and this suffix-minimum form.
 #include "common.h"
-
-#include <climits>
+#include "scan_device.h"
 
 namespace scpose {
 
 namespace {
 
 constexpr int kThreads = 256;
+static_assert(kThreads == kScanThreads, "the scan bodies of scan_device.h run in the workgroups of this file");
 constexpr int kTileItems = 16;
-constexpr int kTile = kThreads * kTileItems;   // 4096 elements per tile of the radix sort and of the scans
+constexpr int kTile = kThreads * kTileItems;   // 4096 elements per tile of the radix sort
 constexpr int kRadix = 256;
 constexpr int kMaxLevels = 31;
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // ------------------------------------------------------------------------------------------------ device-wide int32 scan
-// element j of the scanned sequence is in[REV ? len - 1 - j : j]; OP 0: sum, 1: min
-template <int OP>
-__device__ __forceinline__ int32_t sc_op(int32_t a, int32_t b) { return OP == 0 ? a + b : (a < b ? a : b); }
-template <int OP>
-__device__ __forceinline__ int32_t sc_id() { return OP == 0 ? 0 : INT_MAX; }
-
-template <int OP>
-__device__ int32_t block_inclusive_scan(int32_t v, int32_t* s) {      // 256 threads, Hillis-Steele in LDS
-  const int tid = threadIdx.x;
-  s[tid] = v;
-  __syncthreads();
-  for (int off = 1; off < kThreads; off <<= 1) {
-    const int32_t a = tid >= off ? s[tid - off] : sc_id<OP>();
-    __syncthreads();
-    s[tid] = sc_op<OP>(s[tid], a);
-    __syncthreads();
-  }
-  const int32_t r = s[tid];
-  __syncthreads();
-  return r;
-}
-
+// scan_device.h's three passes over a length the host knows
 template <int OP, bool REV>
 __global__ __launch_bounds__(kThreads) void scan_reduce_kernel(const int32_t* __restrict__ in, int64_t len,
                                                                int32_t* __restrict__ aggr) {
   __shared__ int32_t s[kThreads];
-  const int64_t base = (int64_t)blockIdx.x * kTile;
-  int32_t acc = sc_id<OP>();
-  for (int k = 0; k < kTileItems; ++k) {
-    const int64_t j = base + k * kThreads + threadIdx.x;
-    if (j < len) acc = sc_op<OP>(acc, in[REV ? len - 1 - j : j]);
-  }
-  const int32_t tot = block_inclusive_scan<OP>(acc, s);
-  if (threadIdx.x == kThreads - 1) aggr[blockIdx.x] = tot;
+  scan_tile_reduce<OP, REV>(in, len, aggr, s);
 }
 
-// one workgroup: aggr[b] <- op(aggr[0 .. b - 1]) (identity for b = 0)
 template <int OP>
 __global__ __launch_bounds__(kThreads) void scan_aggr_kernel(int32_t* __restrict__ aggr, int64_t nb) {
   __shared__ int32_t s[kThreads];
-  int32_t carry = sc_id<OP>();
-  for (int64_t b0 = 0; b0 < nb; b0 += kThreads) {
-    const int64_t b = b0 + threadIdx.x;
-    const int32_t v = b < nb ? aggr[b] : sc_id<OP>();
-    const int32_t inc = block_inclusive_scan<OP>(v, s);
-    s[threadIdx.x] = inc;
-    __syncthreads();
-    const int32_t before = threadIdx.x == 0 ? carry : sc_op<OP>(carry, s[threadIdx.x - 1]);
-    const int32_t total = s[kThreads - 1];
-    __syncthreads();
-    if (b < nb) aggr[b] = before;
-    carry = sc_op<OP>(carry, total);
-  }
+  scan_aggregates<OP>(aggr, nb, s);
 }
 
-// out[j] = op over the sequence up to j (inclusive; EXCL: up to j - 1); out may alias in
 template <int OP, bool REV, bool EXCL>
 __global__ __launch_bounds__(kThreads) void scan_apply_kernel(const int32_t* in, int32_t* out, int64_t len,
                                                               const int32_t* __restrict__ aggr) {
   __shared__ int32_t s[kThreads];
-  const int64_t base = (int64_t)blockIdx.x * kTile + (int64_t)threadIdx.x * kTileItems;
-  int32_t v[kTileItems];
-  int32_t acc = sc_id<OP>();
-#pragma unroll
-  for (int k = 0; k < kTileItems; ++k) {
-    const int64_t j = base + k;
-    v[k] = j < len ? in[REV ? len - 1 - j : j] : sc_id<OP>();
-    acc = sc_op<OP>(acc, v[k]);
-  }
-  const int32_t inc = block_inclusive_scan<OP>(acc, s);
-  s[threadIdx.x] = inc;
-  __syncthreads();
-  int32_t run = sc_op<OP>(aggr[blockIdx.x], threadIdx.x == 0 ? sc_id<OP>() : s[threadIdx.x - 1]);   // everything before this thread
-#pragma unroll
-  for (int k = 0; k < kTileItems; ++k) {
-    const int64_t j = base + k;
-    const int32_t after = sc_op<OP>(run, v[k]);
-    if (j < len) out[REV ? len - 1 - j : j] = EXCL ? run : after;
-    run = after;
-  }
+  scan_tile_apply<OP, REV, EXCL>(in, out, len, aggr, s);
 }
 
 template <int OP, bool REV, bool EXCL>
 int32_t scan_launch(const int32_t* in, int32_t* out, int64_t len, int32_t* aggr, hipStream_t stream) {
   if (len == 0) return SCPOSE_OK;
-  const int64_t nb = (len + kTile - 1) / kTile;
+  const int64_t nb = (len + kScanTile - 1) / kScanTile;
   hipLaunchKernelGGL((scan_reduce_kernel<OP, REV>), dim3((unsigned)nb), dim3(kThreads), 0, stream, in, len, aggr);
   hipLaunchKernelGGL((scan_aggr_kernel<OP>), dim3(1), dim3(kThreads), 0, stream, aggr, nb);
   hipLaunchKernelGGL((scan_apply_kernel<OP, REV, EXCL>), dim3((unsigned)nb), dim3(kThreads), 0, stream, in, out, len, aggr);
@@ -300,14 +237,16 @@ unsigned grid_for(int64_t items) {
 }
 
 struct AreaPlan {
-  int64_t n, nt, aggr_len, tops_cap;
+  int64_t nt, tops_cap;
   int nw, nh, passes, L;
-  size_t off_k0, off_k1, off_v0, off_v1, off_hist, off_aggr, off_tables, off_tops, bytes;
+  uint32_t *k0, *k1;                       // sort keys, ping and pong
+  int32_t *v0, *v1, *hist, *aggr, *tables, *tops;
+  size_t bytes;
 };
 
-AreaPlan area_plan(int64_t n, int64_t M, int D, int h, int w) {
+// ws == nullptr: the sizes only
+AreaPlan area_plan(int64_t n, int64_t M, int D, int h, int w, uint8_t* ws) {
   AreaPlan p{};
-  p.n = n;
   p.nw = 1 + w / D;
   p.nh = 1 + h / D;
   const int64_t areas = (int64_t)p.nw * p.nh;
@@ -316,7 +255,6 @@ AreaPlan area_plan(int64_t n, int64_t M, int D, int h, int w) {
   p.passes = (bits + 7) / 8;
   p.nt = (n + kTile - 1) / kTile;
   const int64_t scan_len = n > (int64_t)kRadix * p.nt ? n : (int64_t)kRadix * p.nt;
-  p.aggr_len = (scan_len + kTile - 1) / kTile + 1;
   const int64_t fcap = n >= 2 ? (n - 2) / (M - 1) : 0;
   int L = 0;
   while (L < kMaxLevels && ((int64_t)1 << L) <= fcap) ++L;        // 2^L > every possible frame count: no top walk
@@ -324,35 +262,28 @@ AreaPlan area_plan(int64_t n, int64_t M, int D, int h, int w) {
   while (L > 8 && (double)(L + 1) * 4.0 * (double)n > 34359738368.0) --L;
   p.L = L;
   p.tops_cap = (fcap >> L) + 2;
-  size_t o = 0;
-  const size_t col = align256((size_t)n * 4);
-  p.off_k0 = o; o += col;
-  p.off_k1 = o; o += col;
-  p.off_v0 = o; o += col;
-  p.off_v1 = o; o += col;
-  p.off_hist = o; o += align256((size_t)kRadix * p.nt * 4);
-  p.off_aggr = o; o += align256((size_t)p.aggr_len * 4);
-  p.off_tables = o; o += align256((size_t)(L + 1) * n * 4);
-  p.off_tops = o; o += align256((size_t)p.tops_cap * 4);
-  p.bytes = o;
+  Carve c{ws};
+  p.k0 = c.take<uint32_t>(n);
+  p.k1 = c.take<uint32_t>(n);
+  p.v0 = c.take<int32_t>(n);
+  p.v1 = c.take<int32_t>(n);
+  p.hist = c.take<int32_t>(kRadix * p.nt);
+  p.aggr = c.take<int32_t>((scan_len + kScanTile - 1) / kScanTile + 1);
+  p.tables = c.take<int32_t>((L + 1) * n);
+  p.tops = c.take<int32_t>(p.tops_cap);
+  p.bytes = c.bytes();
   return p;
 }
 
 }  // namespace
 
-size_t events_area_workspace_bytes(int64_t n, int64_t M, int D, int h, int w) { return area_plan(n, M, D, h, w).bytes; }
+size_t events_area_workspace_bytes(int64_t n, int64_t M, int D, int h, int w) { return area_plan(n, M, D, h, w, nullptr).bytes; }
 
 int32_t events_area_bounds_launch(const int32_t* x, const int32_t* y, int64_t n, int64_t M, int D, int h, int w, int64_t* bounds,
                                   int64_t capacity, int64_t* count_status, uint8_t* ws, hipStream_t stream) {
-  const AreaPlan p = area_plan(n, M, D, h, w);
-  uint32_t* k0 = reinterpret_cast<uint32_t*>(ws + p.off_k0);
-  uint32_t* k1 = reinterpret_cast<uint32_t*>(ws + p.off_k1);
-  int32_t* v0 = reinterpret_cast<int32_t*>(ws + p.off_v0);
-  int32_t* v1 = reinterpret_cast<int32_t*>(ws + p.off_v1);
-  int32_t* hist = reinterpret_cast<int32_t*>(ws + p.off_hist);
-  int32_t* aggr = reinterpret_cast<int32_t*>(ws + p.off_aggr);
-  int32_t* tables = reinterpret_cast<int32_t*>(ws + p.off_tables);
-  int32_t* tops = reinterpret_cast<int32_t*>(ws + p.off_tops);
+  const AreaPlan p = area_plan(n, M, D, h, w, ws);
+  uint32_t *k0 = p.k0, *k1 = p.k1;
+  int32_t *v0 = p.v0, *v1 = p.v1, *hist = p.hist, *aggr = p.aggr, *tables = p.tables, *tops = p.tops;
   SCP_CHECK_HIP(hipMemsetAsync(count_status, 0, 2 * sizeof(int64_t), stream));
   if (n > 0)
     hipLaunchKernelGGL(area_id_kernel, dim3(grid_for(n)), dim3(kThreads), 0, stream, x, y, n, D, p.nw, p.nh, k0, count_status);

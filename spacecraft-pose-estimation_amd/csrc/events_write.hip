@@ -4,7 +4,8 @@
 // for negatives, no '+', no leading zeros), SEP one byte.  That is what `"%d %d %d %d\n" % row` of v2e/v2e.py:write_text gives,
 // and it lies inside the grammar csv_parse_kernel accepts, so parse(format(cols)) == cols.  A row takes 8 ... 50 bytes.
 //   text_len_kernel    a tile of 256 rows per workgroup, one row per thread: the row's length, the tile's byte sum
-//   text_scan_kernel   exclusive int64 scan of the tile sums (one workgroup, 256 tiles per step), [n_bytes, 0] -> count_status
+//   text_scan_kernel   scan_device.h's tile-count scan: int64 offsets of the tiles (one workgroup, 256 tiles per step),
+//                      [n_bytes, 0] -> count_status
 //   text_emit_kernel   the same lengths, an in-tile exclusive scan, then every thread renders its row into LDS at its in-tile
 //                      offset.  The LDS image is shifted by (tile offset mod 16), so that after one barrier 16-byte pieces of
 //                      LDS are 16-byte aligned pieces of the file: the workgroup streams them out with one 16-byte store per
@@ -19,17 +20,18 @@
 // integer atomicMin: both are independent of the order.
 // Integer work on fixed positions only: two runs on the same columns are bitwise equal.
 #include "common.h"
+#include "scan_device.h"
 
 namespace scpose {
 
 namespace {
 
 constexpr int kThreads = 256;
+static_assert(kThreads == kScanThreads, "the scan bodies of scan_device.h run in the workgroups of this file");
 constexpr int kTileRows = kThreads;                  // one row per thread
 constexpr int kMaxRow = 50;                          // 20 + 11 + 11 + 4 digits and signs, 3 separators, '\n'
 constexpr int kStage = kTileRows * kMaxRow + 16;     // the tile's text, shifted by up to 15 bytes
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 inline int64_t tiles_of(int64_t n) { return (n + kTileRows - 1) / kTileRows; }
 
 __device__ __forceinline__ int digits_u32(uint32_t v) {
@@ -128,27 +130,12 @@ __device__ __forceinline__ Row load_row(const int64_t* __restrict__ t, const int
   return r;
 }
 
-__device__ int32_t block_inclusive_sum(int32_t v, int32_t* s) {      // 256 threads, Hillis-Steele in LDS
-  const int tid = threadIdx.x;
-  s[tid] = v;
-  __syncthreads();
-  for (int off = 1; off < kThreads; off <<= 1) {
-    const int32_t a = tid >= off ? s[tid - off] : 0;
-    __syncthreads();
-    s[tid] += a;
-    __syncthreads();
-  }
-  const int32_t r = s[tid];
-  __syncthreads();
-  return r;
-}
-
 __global__ __launch_bounds__(kThreads) void text_len_kernel(const int64_t* __restrict__ t, const int32_t* __restrict__ a,
                                                             const int32_t* __restrict__ b, const int8_t* __restrict__ p, int64_t n,
                                                             int32_t* __restrict__ tile_bytes) {
   __shared__ int32_t sc[kThreads];
   const Row r = load_row(t, a, b, p, (int64_t)blockIdx.x * kTileRows + threadIdx.x, n);
-  const int32_t inc = block_inclusive_sum(r.len, sc);
+  const int32_t inc = block_inclusive_scan<0>(r.len, sc);
   if (threadIdx.x == kThreads - 1) tile_bytes[blockIdx.x] = inc;
 }
 
@@ -157,21 +144,10 @@ __global__ __launch_bounds__(kThreads) void text_scan_kernel(const int32_t* __re
                                                              int64_t* __restrict__ tile_off, int64_t* __restrict__ total,
                                                              int64_t* __restrict__ count_status) {
   __shared__ int32_t sc[kThreads];
-  int64_t carry = 0;
-  for (int64_t b0 = 0; b0 < nb; b0 += kThreads) {
-    const int64_t b = b0 + threadIdx.x;
-    const int32_t v = b < nb ? tile_bytes[b] : 0;
-    const int32_t inc = block_inclusive_sum(v, sc);         // at most 256 * 256 * 50: fits int32
-    sc[threadIdx.x] = inc;
-    __syncthreads();
-    const int32_t chunk = sc[kThreads - 1];
-    __syncthreads();
-    if (b < nb) tile_off[b] = carry + inc - v;
-    carry += chunk;
-  }
+  const int64_t bytes = scan_tile_counts(tile_bytes, nb, tile_off, sc);    // a step sums at most 256 * 256 * 50: fits int32
   if (threadIdx.x == 0) {
-    total[0] = carry;
-    count_status[0] = carry;
+    total[0] = bytes;
+    count_status[0] = bytes;
     count_status[1] = 0;
   }
 }
@@ -188,7 +164,7 @@ __global__ __launch_bounds__(kThreads) void text_emit_kernel(const int64_t* __re
     count_status[1] = total[0] > capacity ? SCPOSE_TEXT_CAPACITY : 0;
   }
   const Row r = load_row(t, a, b, p, (int64_t)blockIdx.x * kTileRows + threadIdx.x, n);
-  const int32_t inc = block_inclusive_sum(r.len, sc);
+  const int32_t inc = block_inclusive_scan<0>(r.len, sc);
   sc[threadIdx.x] = inc;
   const int64_t base = tile_off[blockIdx.x];
   const int shift = (int)(base & 15);
@@ -275,47 +251,45 @@ __global__ __launch_bounds__(kThreads) void aedat2_pack_kernel(const int64_t* __
 
 struct TextPlan {
   int64_t nb;
-  size_t off_bytes, off_off, off_words, bytes;
+  int64_t* tile_off;
+  int32_t* tile_bytes;
+  int64_t* total;                                    // 256 bytes
+  size_t bytes;
 };
 
-TextPlan text_plan(int64_t n) {
+TextPlan text_plan(int64_t n, uint8_t* wsp) {
   TextPlan p{};
   p.nb = tiles_of(n);
-  size_t o = 0;
-  p.off_off = o; o += align256((size_t)p.nb * 8);
-  p.off_bytes = o; o += align256((size_t)p.nb * 4);
-  p.off_words = o; o += 256;                         // int64 total
-  p.bytes = o;
+  Carve c{wsp};
+  p.tile_off = c.take<int64_t>(p.nb);
+  p.tile_bytes = c.take<int32_t>(p.nb);
+  p.total = c.take<int64_t>(32);
+  p.bytes = c.bytes();
   return p;
 }
 
 }  // namespace
 
 int events_text_tile_rows() { return kTileRows; }
-int events_text_scan_rows() { return kTileRows * kThreads; }
-size_t events_text_workspace_bytes(int64_t n) { return text_plan(n).bytes; }
+int events_text_scan_rows() { return kTileRows * kScanThreads; }
+size_t events_text_workspace_bytes(int64_t n) { return text_plan(n, nullptr).bytes; }
 
 int32_t events_text_measure_launch(const int64_t* t, const int32_t* x, const int32_t* y, const int8_t* p, int64_t n,
                                    int64_t* count_status, uint8_t* wsp, hipStream_t stream) {
-  const TextPlan pl = text_plan(n);
-  int64_t* tile_off = reinterpret_cast<int64_t*>(wsp + pl.off_off);
-  int32_t* tile_bytes = reinterpret_cast<int32_t*>(wsp + pl.off_bytes);
-  int64_t* total = reinterpret_cast<int64_t*>(wsp + pl.off_words);
+  const TextPlan pl = text_plan(n, wsp);
   if (pl.nb > 0)
-    hipLaunchKernelGGL(text_len_kernel, dim3((unsigned)pl.nb), dim3(kThreads), 0, stream, t, x, y, p, n, tile_bytes);
-  hipLaunchKernelGGL(text_scan_kernel, dim3(1), dim3(kThreads), 0, stream, tile_bytes, pl.nb, tile_off, total, count_status);
+    hipLaunchKernelGGL(text_len_kernel, dim3((unsigned)pl.nb), dim3(kThreads), 0, stream, t, x, y, p, n, pl.tile_bytes);
+  hipLaunchKernelGGL(text_scan_kernel, dim3(1), dim3(kThreads), 0, stream, pl.tile_bytes, pl.nb, pl.tile_off, pl.total, count_status);
   SCP_CHECK_HIP(hipGetLastError());
   return SCPOSE_OK;
 }
 
 int32_t events_text_emit_launch(const int64_t* t, const int32_t* x, const int32_t* y, const int8_t* p, int64_t n, int sep, int swap_xy,
                                 uint8_t* out, int64_t capacity, int64_t* count_status, uint8_t* wsp, hipStream_t stream) {
-  const TextPlan pl = text_plan(n);
-  const int64_t* tile_off = reinterpret_cast<const int64_t*>(wsp + pl.off_off);
-  const int64_t* total = reinterpret_cast<const int64_t*>(wsp + pl.off_words);
+  const TextPlan pl = text_plan(n, wsp);
   // n == 0: one workgroup without rows still writes count_status
   hipLaunchKernelGGL(text_emit_kernel, dim3((unsigned)(pl.nb > 0 ? pl.nb : 1)), dim3(kThreads), 0, stream, t, swap_xy ? y : x,
-                     swap_xy ? x : y, p, n, (uint32_t)sep, tile_off, total, out, capacity, count_status);
+                     swap_xy ? x : y, p, n, (uint32_t)sep, pl.tile_off, pl.total, out, capacity, count_status);
   SCP_CHECK_HIP(hipGetLastError());
   return SCPOSE_OK;
 }

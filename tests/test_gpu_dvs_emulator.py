@@ -81,6 +81,46 @@ def test_device_equals_restatement(gpu_ops, name, hw):
         assert float(np.min(case["pos_thres"])) == np.float32(0.01)
 
 
+SCAN_TILE = 4096                         # table entries per workgroup of the device-wide scan (csrc/scan_device.h)
+SCAN_SHAPES = {"two_scan_blocks": (16, 16, 1), "carry_loop": (240, 256, 256)}     # h, w, scan blocks the longest table must exceed
+
+
+def scan_case(h, w, f=3):
+    """A moving background at threshold 0.2 and one pixel at pos_thres 0.01 that steps 0 -> 255 in frame 1: that frame needs
+    ln(255) / 0.01 sub-iterations while the events stay few; in frame 2 the pixel rests and the table is short again."""
+    frames = R.moving_frames(8, f, h, w)
+    y, x = h // 2, w // 3
+    frames[0, y, x] = 0
+    frames[1:, y, x] = 255
+    pos = np.full((h, w), 0.2, np.float32)
+    pos[y, x] = 0.01
+    return dict(frames=frames, t=0.5 + 0.01 * np.arange(f), pos_thres=pos, neg_thres=0.2)
+
+
+@pytest.mark.parametrize("name", sorted(SCAN_SHAPES))
+def test_scan_past_one_block_equals_restatement(gpu_ops, name):
+    """The scanned table has 2 * num_iters * ceil(h * w / 64) entries.  two_scan_blocks: more than one scan tile, the last one
+    partial (the aggregate pass).  carry_loop: more than 256 scan tiles (the carry loop of the one-workgroup middle pass), followed
+    by a frame with a shorter table (blocks past the device-side length return early, over aggregates the long frame left)."""
+    h, w, blocks = SCAN_SHAPES[name]
+    case = scan_case(h, w)
+    e = R.RestatedEmulator(**R.case_params(case))
+    ref_cols = R.columns(e.emulate(case["frames"], case["t"]))
+    ref_state = e.state()
+    tiles = (h * w + 63) // 64
+    lens = [2 * n * tiles for n in e.num_iters]
+    assert max(e.num_iters) <= 1024                                  # max_iters stays at its default
+    assert max(lens) > blocks * SCAN_TILE, (e.num_iters, tiles)
+    if name == "two_scan_blocks":
+        assert max(lens) % SCAN_TILE != 0
+    else:
+        assert lens.index(max(lens)) < len(lens) - 1 and lens[-1] < max(lens), lens
+    cols, state, _ = run_device(gpu_ops, case, h, w)
+    assert_same(cols, ref_cols, name)
+    for k in ("base", "lp0", "lp1", "tmem"):
+        assert np.array_equal(bits(state[k]), bits(ref_state[k])), "%s: state %s differs" % (name, k)
+
+
 def test_device_equals_reference_rows(gpu_ops):
     g = np.load(GOLDEN)
     for name in g["cases"]:
