@@ -388,6 +388,44 @@ int32_t scpose_events_text_emit(const int64_t* t, const int32_t* x, const int32_
 int32_t scpose_events_aedat2_pack(const int64_t* t, const int32_t* x, const int32_t* y, const int8_t* p, int64_t n, int32_t h,
                                   int32_t w, uint8_t* out, int64_t* count_status, void* stream);
 
+/* (ABI 7, additive) AEDAT-2.0 records on the device (csrc/events_aedat2_read.hip): the bytes after a file's '#' header -> the four
+ * columns scpose_events_frame_bounds / scpose_events_render take, kept events in file order.  The inverse of
+ * scpose_events_aedat2_pack, and a reader of jAER's DAVIS recordings.  A record is two big-endian uint32 words, (address, time stamp).
+ *   records      device u8, 8-byte aligned, 8 * n_records bytes (n_records == 0: the data pointers may be NULL)
+ *   layout       SCPOSE_AEDAT2_LAYOUT_DAVIS: jAER's DAVIS word.  Bit 31 set: an APS / IMU sample, dropped and counted in n_other.
+ *                Bit 31 clear and bit 10 set: a special event, dropped and counted in n_special.  Otherwise a polarity event: p =
+ *                bit 11, x field = bits 12-21, y field = bits 22-30.  h 1 .. 512, w 1 .. 1024.
+ *                SCPOSE_AEDAT2_LAYOUT_V2E: what AEDat2Output of the reference and scpose_events_aedat2_pack write.  Every record is
+ *                a polarity event; the y field is bits 22-31 (the writer's 692x520 sets bit 31 for its flipped y >= 512, which jAER
+ *                itself would misread).  h 1 .. 1024, w 1 .. 1024: the 1280-wide size is refused, because from x = 1024 on the
+ *                writer ORs bit 10 of x into bit 0 of y and the word cannot be inverted.
+ *   flip_x/y     != 0: x = w - 1 - x field, y = h - 1 - y field, what both writers do (unpack(pack(cols)) == cols); 0: the field
+ *   range        a polarity event whose x field is outside [0, w) or y field outside [0, h) sets status bit
+ *                SCPOSE_AEDAT2_READ_RANGE; the columns are then unspecified -- never a different answer silently
+ *   unwrap       with u_i the time stamp word of record i as uint32, over ALL records, dropped ones included:
+ *                0: t = (int64)(int32)u.  != 0: t_i = u_i + 2^32 * wraps_i, wraps_i = #{ j in 1 .. i : u_{j-1} > u_j and
+ *                u_{j-1} - u_j > 2^31 }.  A signed roll-over (0x7fffffff -> 0x80000000) is an increase and needs nothing, a full
+ *                32-bit roll-over adds 2^32, a smaller step back is not a wrap.
+ *   t_divisor    0: none; 1e3 / 1e6: t <- (int64)((double)t / t_divisor) afterwards, as scpose_events_csv_parse
+ *   t, x, y, p   device i64 / i32 / i32 / i8, capacity rows each; n_records rows always suffice
+ *   count_status device i64 [6] <- [n_events, status, n_other, n_special, n_wraps, n_backward].  n_wraps: the wraps of the whole
+ *                stream (counted whatever unwrap says).  n_backward: kept events whose final t is below the previous kept event's:
+ *                the renderer needs a sorted stream, the caller decides.  SCPOSE_AEDAT2_READ_CAPACITY: more kept events than
+ *                capacity; nothing is stored at or past `capacity` and n_events = 0.  Read count_status back once.
+ *   workspace    caller-owned, 16-byte aligned, scpose_events_aedat2_unpack_workspace_bytes(n_records) (never 0)
+ * Argument errors (a null pointer with n_records > 0, a null count_status or workspace, n_records < 0, capacity < 0, an unknown
+ * layout, h or w outside the layout's range -- "not supported" --, a divisor other than 0, 1e3, 1e6, a misaligned buffer, a workspace
+ * that is too small) return -1 with a message before anything is launched.  Three launches, a tile of 4096 records per workgroup:
+ * count, scan, scatter; 16 bytes read and at most 17 written per record.  No allocation, no synchronisation, no atomics on the
+ * columns, no floating point except the divisor; two calls on the same bytes give bitwise equal outputs. */
+enum { SCPOSE_AEDAT2_LAYOUT_DAVIS = 0, SCPOSE_AEDAT2_LAYOUT_V2E = 1 };
+enum { SCPOSE_AEDAT2_READ_RANGE = 1, SCPOSE_AEDAT2_READ_CAPACITY = 2 };
+int32_t scpose_events_aedat2_unpack_workspace_bytes(int64_t n_records, size_t* bytes);
+int32_t scpose_events_aedat2_unpack(const uint8_t* records, int64_t n_records, int32_t h, int32_t w, int32_t layout,
+                                    int32_t flip_x, int32_t flip_y, int32_t unwrap, double t_divisor,
+                                    int64_t* t, int32_t* x, int32_t* y, int8_t* p, int64_t capacity,
+                                    int64_t* count_status, void* workspace, size_t workspace_bytes, void* stream);
+
 /* (ABI 7, additive) DVS emulator core on the device (csrc/dvs_emulator.hip): time-stamped grayscale uint8 frames -> an event
  * stream, in the columns scpose_events_frame_bounds / scpose_events_render take.  Restates EventEmulator._init / generate_events
  * of the reference's v2e/v2ecore/emulator.py (with lin_log, rescale_intensity_frame, low_pass_filter, subtract_leak_current,

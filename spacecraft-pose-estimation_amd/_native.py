@@ -25,6 +25,8 @@ CSV_UNSUPPORTED, CSV_CAPACITY = 1, 2
 DVS_CAPACITY, DVS_ITERS, DVS_TIME = 1, 2, 4
 TEXT_CAPACITY = 1
 AEDAT2_RANGE, AEDAT2_TIME = 1, 2
+AEDAT2_LAYOUT_DAVIS, AEDAT2_LAYOUT_V2E = 0, 1
+AEDAT2_READ_RANGE, AEDAT2_READ_CAPACITY = 1, 2
 ABI_VERSION = 7
 
 
@@ -124,6 +126,10 @@ SYMBOLS = {
                                           c_void_p, c_void_p, c_size_t, c_void_p]),
     "scpose_events_aedat2_pack": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p,
                                             c_void_p]),
+    "scpose_events_aedat2_unpack_workspace_bytes": (c_int32, [c_int64, POINTER(c_size_t)]),
+    "scpose_events_aedat2_unpack": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_double,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_size_t,
+                                              c_void_p]),
     "scpose_dvs_state_bytes": (c_int32, [c_int32, c_int32, POINTER(c_size_t)]),
     "scpose_dvs_workspace_bytes": (c_int32, [c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
     "scpose_dvs_init": (c_int32, [c_void_p, c_void_p, c_double, POINTER(DvsParams), c_void_p]),

@@ -227,6 +227,43 @@ extern "C" int32_t scpose_events_aedat2_pack(const int64_t* t, const int32_t* x,
   return events_aedat2_pack_launch(t, x, y, p, n, h, w, out, count_status, static_cast<hipStream_t>(stream));
 }
 
+static const int64_t kMaxReadRecords = (int64_t)1 << 38;      // 2 TiB of records; the tile index is negated in an int32
+
+extern "C" int32_t scpose_events_aedat2_unpack_workspace_bytes(int64_t n_records, size_t* bytes) {
+  SCP_REQUIRE(bytes, "events_aedat2_unpack_workspace_bytes: null argument");
+  SCP_REQUIRE(n_records >= 0 && n_records <= kMaxReadRecords, "events_aedat2_unpack_workspace_bytes: n_records=%lld (0 .. 2^38)",
+              (long long)n_records);
+  *bytes = events_aedat2_unpack_workspace_bytes(n_records);
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_events_aedat2_unpack(const uint8_t* records, int64_t n_records, int32_t h, int32_t w, int32_t layout,
+                                               int32_t flip_x, int32_t flip_y, int32_t unwrap, double t_divisor, int64_t* t, int32_t* x,
+                                               int32_t* y, int8_t* p, int64_t capacity, int64_t* count_status, void* workspace,
+                                               size_t workspace_bytes, void* stream) {
+  SCP_REQUIRE(layout == SCPOSE_AEDAT2_LAYOUT_DAVIS || layout == SCPOSE_AEDAT2_LAYOUT_V2E,
+              "events_aedat2_unpack: layout=%d: the layouts are 0 (DAVIS) and 1 (V2E)", layout);
+  // x has the 10 bits from bit 12; y the 9 bits from bit 22 below the DAVIS type bit, or all 10 as the V2E writer uses them
+  const int32_t max_h = layout == SCPOSE_AEDAT2_LAYOUT_DAVIS ? 512 : 1024;
+  SCP_REQUIRE(h >= 1 && h <= max_h && w >= 1 && w <= 1024,
+              "events_aedat2_unpack: frame %dx%d (HxW) not supported under the %s layout: H 1 .. %d, W 1 .. 1024%s", h, w,
+              layout == SCPOSE_AEDAT2_LAYOUT_DAVIS ? "DAVIS" : "V2E", max_h,
+              w > 1024 && w <= 1280 ? " (the 1280x720 writer ORs bit 10 of x into bit 0 of y: the word cannot be inverted)" : "");
+  SCP_REQUIRE(n_records >= 0 && n_records <= kMaxReadRecords, "events_aedat2_unpack: n_records=%lld (0 .. 2^38)", (long long)n_records);
+  SCP_REQUIRE(capacity >= 0, "events_aedat2_unpack: capacity=%lld", (long long)capacity);
+  SCP_REQUIRE(t_divisor == 0.0 || t_divisor == 1e3 || t_divisor == 1e6, "events_aedat2_unpack: t_divisor=%g (0: none, 1e3 or 1e6)",
+              t_divisor);
+  SCP_REQUIRE(count_status && (n_records == 0 || (records && ((t && x && y && p) || capacity == 0))),
+              "events_aedat2_unpack: null argument");
+  SCP_REQUIRE((reinterpret_cast<uintptr_t>(records) & 7) == 0, "events_aedat2_unpack: records must be 8-byte aligned");
+  const size_t need = events_aedat2_unpack_workspace_bytes(n_records);
+  SCP_REQUIRE(workspace && workspace_bytes >= need, "events_aedat2_unpack: workspace of %zu bytes needed (got %zu)", need,
+              workspace ? workspace_bytes : (size_t)0);
+  SCP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "events_aedat2_unpack: workspace must be 16-byte aligned");
+  return events_aedat2_unpack_launch(records, n_records, h, w, layout, flip_x != 0, flip_y != 0, unwrap != 0, t_divisor, t, x, y, p,
+                                     capacity, count_status, static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
 static int32_t dvs_check_params(const scpose_dvs_params* p, const char* who) {
   SCP_REQUIRE(p, "%s: null params", who);
   SCP_REQUIRE(p->h > 0 && p->w > 0 && (int64_t)p->h * p->w <= (1 << 24), "%s: bad shape h=%d w=%d", who, p->h, p->w);

@@ -274,6 +274,11 @@ int32_t events_text_emit_launch(const int64_t* t, const int32_t* x, const int32_
                                 uint8_t* out, int64_t capacity, int64_t* count_status, uint8_t* ws, hipStream_t stream);
 int32_t events_aedat2_pack_launch(const int64_t* t, const int32_t* x, const int32_t* y, const int8_t* p, int64_t n, int h, int w,
                                   uint8_t* out, int64_t* count_status, hipStream_t stream);
+// events_aedat2_read.hip: AEDAT-2.0 records -> (t, x, y, p)
+size_t events_aedat2_unpack_workspace_bytes(int64_t n);
+int32_t events_aedat2_unpack_launch(const uint8_t* records, int64_t n, int h, int w, int layout, int flip_x, int flip_y, int unwrap,
+                                    double t_div, int64_t* t, int32_t* x, int32_t* y, int8_t* p, int64_t capacity, int64_t* count_status,
+                                    uint8_t* ws, hipStream_t stream);
 // dvs_emulator.hip: intensity frames -> event stream (v2e/v2ecore/emulator.py: EventEmulator.generate_events)
 size_t dvs_state_bytes(int h, int w);
 size_t dvs_workspace_bytes(int h, int w, int frames, int max_iters);

@@ -74,14 +74,34 @@ def read_events_csv(path, delim_whitespace=False, swap_xy=False, microseconds_ti
     return ev[:, 0].copy(), ev[:, 1].copy(), ev[:, 2].copy(), ev[:, 3].copy()
 
 
-def read_events_device(path, device=None, host_csv=False, **csv_flags):
+def read_events_device(path, device=None, host_csv=False, hw=None, aedat_layout="davis", aedat_flip_x=True, aedat_flip_y=True,
+                       **csv_flags):
     """events.csv -> (t int64, x int32, y int32) device tensors, the stream ops.render_events takes.  The file's bytes are
     uploaded in one piece and parsed on the device (ops.parse_events_csv); text outside that parser's grammar
     (ops.UnsupportedCsv) and host_csv=True go through read_events_csv and one upload per column, as every file did before:
-    the columns are the same either way."""
+    the columns are the same either way.
+
+    A path that ends in .aedat / .aedat2, or a file whose first bytes are '#!AER-DAT', is an AEDAT-2.0 file and goes through
+    event_read.read_events_aedat2 instead: hw = (height, width) of the sensor is then required, aedat_layout is 'davis' or
+    'v2e', aedat_flip_x / aedat_flip_y undo the writers' flips, and the two time-stamp flags become the decoder's divisor.  The
+    flags that describe text (delim_whitespace, swap_xy, host_csv) are refused by name, and a stream with backward time steps
+    raises ValueError("the event stream must be sorted by time")."""
     import torch
-    from . import ops
+    from . import event_read, ops
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if event_read.is_aedat_path(path):
+        for name, on in (("host_csv", host_csv), ("delim_whitespace", csv_flags.get("delim_whitespace")),
+                         ("swap_xy", csv_flags.get("swap_xy"))):
+            if on:
+                raise ValueError("%s describes a text file and cannot be used with the AEDAT-2.0 input %s" % (name, path))
+        if hw is None:
+            raise ValueError("an AEDAT-2.0 input needs the sensor size hw = (height, width)")
+        div = 1000000.0 if csv_flags.get("microseconds_timestamp") else (1000.0 if csv_flags.get("milliseconds_timestamp") else 0.0)
+        t, x, y, _, info = event_read.read_events_aedat2(path, hw, device=dev, layout=aedat_layout, flip_x=aedat_flip_x,
+                                                         flip_y=aedat_flip_y, t_divisor=div)
+        if info["n_backward"] > 0:
+            raise ValueError("the event stream must be sorted by time")
+        return t, x, y
     if not host_csv:
         try:
             t, x, y, _ = ops.parse_events_csv(path, device=dev, **csv_flags)
@@ -159,17 +179,21 @@ def frame_times_text(dvs_vid, times):
 
 
 def render_scene(scene_dir, hw, K=None, dist=None, interval=10000.0, full_scale=2, write_distorted=True, device=None,
-                 chunk_frames=256, exposure=None, host_csv=False, **csv_flags):
+                 chunk_frames=256, exposure=None, host_csv=False, aedat_layout="davis", **csv_flags):
     """scene_dir/events.csv -> scene_dir/event-frames/<t>.bmp (undistorted when K / dist are given) and, with
     write_distorted, scene_dir/event-frames-distorted/<t>.bmp: the directory contract of the reference's convert_aedats.py.
     The file is uploaded once, parsed and rendered on the device (read_events_device, ops.render_events); frames come back
     chunk_frames at a time.  host_csv: read the file with the pandas reader instead (the device parser's fallback).
     exposure: None (DURATION over `interval`) or ops.render_events keyword arguments (exposure_kwargs) that replace it.
-    Returns the list of frame names."""
+    A scene that holds events.aedat (AEDAT-2.0, address layout aedat_layout, sensor size hw) and no events.csv is rendered from
+    that file; when both exist, events.csv wins.  Returns the list of frame names."""
     import torch
     from . import ops
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    t, x, y = read_events_device(os.path.join(scene_dir, "events.csv"), dev, host_csv=host_csv, **csv_flags)
+    src = os.path.join(scene_dir, "events.csv")
+    if not os.path.exists(src) and os.path.exists(os.path.join(scene_dir, "events.aedat")):
+        src = os.path.join(scene_dir, "events.aedat")
+    t, x, y = read_events_device(src, dev, host_csv=host_csv, hw=hw, aedat_layout=aedat_layout, **csv_flags)
     out_dir = os.path.join(scene_dir, "event-frames"); dis_dir = os.path.join(scene_dir, "event-frames-distorted")
     os.makedirs(out_dir, exist_ok=True)
     if write_distorted:

@@ -473,6 +473,73 @@ def pack_events_aedat2(t, x, y, p, hw):
     return out, int(lead)
 
 
+AEDAT2_LAYOUTS = {"davis": nat.AEDAT2_LAYOUT_DAVIS, "v2e": nat.AEDAT2_LAYOUT_V2E}
+AEDAT2_INFO = ("n_events", "n_other", "n_special", "n_wraps", "n_backward")
+
+
+def _aedat2_layout(layout):
+    try:
+        return AEDAT2_LAYOUTS[str(layout).lower()]
+    except KeyError:
+        raise ValueError("unpack_events_aedat2: layout must be 'davis' or 'v2e' (got %r)" % (layout,))
+
+
+def _unpack_events_aedat2_into(buf, n, hw, layout, flip_x, flip_y, unwrap, t_divisor, t, x, y, p, capacity):
+    """One scpose_events_aedat2_unpack call on the current stream into caller-sized columns; returns count_status as a list
+    (the one small read-back)."""
+    h, w = int(hw[0]), int(hw[1])
+    lib = nat.lib()
+    ws = c_size_t()
+    nat.check(lib.scpose_events_aedat2_unpack_workspace_bytes(n, ctypes.byref(ws)), "events_aedat2_unpack_workspace_bytes")
+    with torch.cuda.device(buf.device):
+        cs = torch.empty(6, dtype=torch.int64, device=buf.device)
+        work = torch.empty(ws.value, dtype=torch.uint8, device=buf.device)
+        nat.check(lib.scpose_events_aedat2_unpack(_ptr(buf), n, h, w, _aedat2_layout(layout), int(bool(flip_x)), int(bool(flip_y)),
+                                                  int(bool(unwrap)), c_double(float(t_divisor)), _ptr(t), _ptr(x), _ptr(y), _ptr(p),
+                                                  int(capacity), _ptr(cs), _ptr(work), ws.value, _stream()), "events_aedat2_unpack")
+        return cs.tolist()
+
+
+def unpack_events_aedat2(records, hw, layout="davis", flip_x=True, flip_y=True, unwrap=True, t_divisor=0.0):
+    """AEDAT-2.0 records -> (t int64, x int32, y int32, p int8, info): the kept events in file order, decoded on the device
+    (csrc/events_aedat2_read.hip), in the dtypes render_events takes.  records: a uint8 device tensor of 8 * n bytes, the part
+    of the file after its '#' header (event_read.read_events_aedat2 splits it off).  hw = (height, width) of the sensor.
+    layout 'davis': jAER's DAVIS word, APS / IMU samples and special events dropped and counted; 'v2e': the records
+    pack_events_aedat2 and the reference's AEDat2Output write.  flip_x / flip_y: undo the writers' flips (the default, so that
+    unpack(pack(cols)) == cols).  unwrap: count full 32-bit roll-overs of the time stamp word into t; else t is the
+    sign-extended word.  t_divisor: 0, 1e3 or 1e6, applied as parse_events_csv applies its time-stamp flags.
+    info: the counters n_events, n_other, n_special, n_wraps, n_backward (include/scpose.h: scpose_events_aedat2_unpack).
+    One small read-back, count_status.  Raises ValueError when a polarity event lies outside the sensor."""
+    if not torch.is_tensor(records) or records.dtype != torch.uint8:
+        raise ValueError("unpack_events_aedat2: the records must be a uint8 device tensor")
+    _need_cuda(records)
+    buf = records.contiguous().view(-1)
+    if buf.numel() % 8:
+        raise ValueError("unpack_events_aedat2: %d bytes are not a whole number of 8-byte records" % buf.numel())
+    if buf.data_ptr() % 8:
+        buf = buf.clone()
+    n = int(buf.numel()) // 8
+    dev = buf.device
+    _aedat2_layout(layout)
+    with torch.cuda.device(dev):
+        t = torch.empty(n, dtype=torch.int64, device=dev)
+        x = torch.empty(n, dtype=torch.int32, device=dev)
+        y = torch.empty(n, dtype=torch.int32, device=dev)
+        p = torch.empty(n, dtype=torch.int8, device=dev)
+        cs = _unpack_events_aedat2_into(buf, n, hw, layout, flip_x, flip_y, unwrap, t_divisor, t, x, y, p, n)
+    status = cs[1]
+    if status & nat.AEDAT2_READ_RANGE:
+        raise ValueError("unpack_events_aedat2: a polarity event lies outside the %d x %d sensor under the %s layout"
+                         % (int(hw[1]), int(hw[0]), layout))
+    if status != 0:
+        raise nat.NativeError("unpack_events_aedat2: events_aedat2_unpack status %d" % status)
+    info = dict(zip(AEDAT2_INFO, (int(cs[0]), int(cs[2]), int(cs[3]), int(cs[4]), int(cs[5]))))
+    rows = info["n_events"]
+    if rows == n:
+        return t, x, y, p, info
+    return t[:rows].clone(), x[:rows].clone(), y[:rows].clone(), p[:rows].clone(), info
+
+
 class DvsEmulator:
     """Device DVS emulator (csrc/dvs_emulator.hip): see dvs_emulator().  The state lives in device memory between calls."""
 

@@ -2,7 +2,7 @@
 """Stage 0 of the reference's event pipeline (v2e/convert_aedats.py) on the MI355X HIP path.
 
 Same four arguments and the same directory contract as the reference script: for every scene directory under --scenes_dir
-that holds events.csv (t, x, y, p per line) it writes
+that holds events.csv (t, x, y, p per line), or an AEDAT-2.0 file events.aedat and no events.csv, it writes
     <scene>/event-frames-distorted/<t>.bmp   the events of each 10 000-tick window as a gray frame (e2v.py --dvs_exposure
                                              duration 10000 --dvs_vid_full_scale 2)
     <scene>/event-frames/<t>.bmp             the same frame after cv2.undistort with the calibration file's camera
@@ -13,8 +13,10 @@ output ops.crop_warp accepts as is.
 
 Extensions (optional): --no_distorted skips event-frames-distorted/; the CSV flags of e2v.py (--delim_whitespace, --swap_xy,
 --microseconds_timestamp, --milliseconds_timestamp); --host_csv reads events.csv with the pandas reader, which is also what a
-file outside the device parser's grammar (an exponent, a quoted field, ...) falls back to by itself.  Not reproduced: the AVI video and frame-times file e2v.py also
-writes, AEDAT parsing (aedat_to_csv.py)."""
+file outside the device parser's grammar (an exponent, a quoted field, ...) falls back to by itself; a scene's events.aedat
+is decoded on the device (csrc/events_aedat2_read.hip) with --image_height x --image_width as the sensor size and --aedat_layout
+as the address word, and events.csv wins when both exist.  Not reproduced: the AVI video and frame-times file e2v.py also
+writes, AEDAT-3/4 parsing (aedat_to_csv.py)."""
 import argparse
 import json
 import os
@@ -37,6 +39,8 @@ def parse_args(argv=None):
     p.add_argument("--microseconds_timestamp", action="store_true", help="divide the time stamps by 1e6 as e2v.py does")
     p.add_argument("--milliseconds_timestamp", action="store_true", help="divide the time stamps by 1e3 as e2v.py does")
     p.add_argument("--host_csv", action="store_true", help="read events.csv with the pandas reader on the host instead of the device parser")
+    p.add_argument("--aedat_layout", choices=("davis", "v2e"), default="davis",
+                   help="address word of a scene's events.aedat: jAER's DAVIS word, or the word v2e.py --events_aedat2 writes")
     return p.parse_args(argv)
 
 
@@ -52,11 +56,13 @@ def main(argv=None):
     dist = np.array(calib["intrinsics"]["distortion_coefficients"], dtype=np.float64).reshape(-1)[:5]
     for scene in sorted(os.listdir(args.scenes_dir)):
         full = os.path.join(args.scenes_dir, scene)
-        if os.path.isdir(full) and os.path.exists(os.path.join(full, "events.csv")):
+        if os.path.isdir(full) and (os.path.exists(os.path.join(full, "events.csv")) or
+                                    os.path.exists(os.path.join(full, "events.aedat"))):
             names = er.render_scene(full, (args.image_height, args.image_width), K=K, dist=dist,
                                     write_distorted=not args.no_distorted, delim_whitespace=args.delim_whitespace,
                                     swap_xy=args.swap_xy, microseconds_timestamp=args.microseconds_timestamp,
-                                    milliseconds_timestamp=args.milliseconds_timestamp, host_csv=args.host_csv)
+                                    milliseconds_timestamp=args.milliseconds_timestamp, host_csv=args.host_csv,
+                                    aedat_layout=args.aedat_layout)
             print("%s: %d frames" % (scene, len(names)))
 
 

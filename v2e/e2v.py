@@ -8,7 +8,11 @@ Same arguments and defaults as the reference script.  Every frame the reference'
 with all three exposure modes of --dvs_exposure: duration T, count N, area_count M D (event_render.parse_dvs_exposure).  The
 CSV parser, the histogram, the gray mapping and the frame ends of the count modes run on the device (csrc/events_csv.hip,
 csrc/events.hip, csrc/events_exposure.hip); --host_csv (an extension) reads the file with the pandas reader instead, which is
-also the fallback for text outside the device parser's grammar.  No undistortion, as in e2v.py.  The AVI video is not written
+also the fallback for text outside the device parser's grammar.  An --events_file that ends in .aedat / .aedat2 (or starts with
+'#!AER-DAT') is read as AEDAT-2.0 on the device instead (csrc/events_aedat2_read.hip, an extension): the sensor size is
+--output_height x --output_width, --aedat_layout picks jAER's DAVIS address word or the one v2e.py --events_aedat2 writes,
+--aedat_no_flip_x / --aedat_no_flip_y keep an axis as stored, the two time-stamp flags divide as for a CSV, and the flags that
+describe text (--delim_whitespace, --swap_xy, --host_csv) are refused.  No undistortion, as in e2v.py.  The AVI video is not written
 (there is no video encoder here); --no_preview and --avi_frame_rate are accepted and ignored."""
 import argparse
 import os
@@ -30,6 +34,12 @@ def e2v_args(parser):
                         help="divide the time stamps by 1e3 (int64, truncated) before rendering")
     parser.add_argument("--host_csv", action="store_true", default=False,
                         help="read the CSV with the pandas reader on the host instead of the device parser")
+    parser.add_argument("--aedat_layout", choices=("davis", "v2e"), default="davis",
+                        help="address word of an AEDAT-2.0 --events_file: jAER's DAVIS word, or the word v2e.py --events_aedat2 writes")
+    parser.add_argument("--aedat_no_flip_x", action="store_true", default=False,
+                        help="AEDAT-2.0 input: keep x as stored instead of undoing the writers' flip")
+    parser.add_argument("--aedat_no_flip_y", action="store_true", default=False,
+                        help="AEDAT-2.0 input: keep y as stored instead of undoing the writers' flip")
     parser.add_argument("--avi_frame_rate", type=int, default=30, help="accepted and ignored: no AVI is written")
     parser.add_argument("--dvs_vid", type=str, default="dvs-video.avi",
                         help="name the frame-times file is derived from (<stem>-frame_times.txt); no AVI is written")
@@ -46,8 +56,26 @@ def e2v_args(parser):
     return parser
 
 
+def is_aedat(path):
+    """An .aedat / .aedat2 name, or a file that starts with '#!AER-DAT' (event_read.is_aedat_path, without importing the package)."""
+    if path is None:
+        return False
+    if path.lower().endswith((".aedat", ".aedat2")):
+        return True
+    try:
+        with open(path, "rb") as f:
+            return f.read(9) == b"#!AER-DAT"
+    except OSError:
+        return False
+
+
 def main(argv=None):
     args = e2v_args(argparse.ArgumentParser(description="Event frames from an events CSV, on the device.")).parse_args(argv)
+    aedat = is_aedat(args.events_file)
+    if aedat:
+        for flag in ("delim_whitespace", "swap_xy", "host_csv"):
+            if getattr(args, flag):
+                sys.exit("e2v: --%s describes a text file and cannot be used with the AEDAT-2.0 input %s" % (flag, args.events_file))
     import torch
     import scpose  # noqa: F401
     from importlib import import_module
@@ -60,10 +88,17 @@ def main(argv=None):
     out_dir = os.path.join(args.output_folder, "event-frames")
     os.makedirs(out_dir, exist_ok=True)
     dev = torch.device("cuda", torch.cuda.current_device())
-    t, x, y = er.read_events_device(args.events_file, dev, host_csv=args.host_csv, delim_whitespace=args.delim_whitespace,
-                                    swap_xy=args.swap_xy, microseconds_timestamp=args.microseconds_timestamp,
-                                    milliseconds_timestamp=args.milliseconds_timestamp)
     h, w = args.output_height, args.output_width
+    try:
+        t, x, y = er.read_events_device(args.events_file, dev, host_csv=args.host_csv, hw=(h, w), aedat_layout=args.aedat_layout,
+                                        aedat_flip_x=not args.aedat_no_flip_x, aedat_flip_y=not args.aedat_no_flip_y,
+                                        delim_whitespace=args.delim_whitespace, swap_xy=args.swap_xy,
+                                        microseconds_timestamp=args.microseconds_timestamp,
+                                        milliseconds_timestamp=args.milliseconds_timestamp)
+    except ValueError as e:
+        if not aedat:
+            raise
+        sys.exit("e2v: %s" % e)
     times, names = [], []
     if len(t) > 0:
         frames, names = ops.render_events(t, x, y, None, (h, w),

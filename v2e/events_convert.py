@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""events_convert: an event text / CSV file into another event file, on the device.
+"""events_convert: an event text / CSV / AEDAT-2.0 file into another event file, on the device.
 
     python v2e/events_convert.py --events_file IN [--delim_whitespace] [--swap_xy] --output OUT [--width W --height H]
+                                 [--aedat_layout {davis,v2e}]
 
 IN is read by ops.parse_events_csv (csrc/events_csv.hip; --delim_whitespace and --swap_xy are e2v.py's flags of the same
 names) and the four columns go straight to one of the device writers (event_write), chosen by OUT's extension, without a host
@@ -12,6 +13,11 @@ copy of the columns:
     .aedat   AEDAT-2.0 for jAER; needs --width and --height, one of 346x260, 692x520, 1280x720, 640x480, 240x180, and time
              stamps in microseconds
 The text forms write x before y whatever --swap_xy says: the flag describes IN.
+
+An IN that ends in .aedat / .aedat2 is an AEDAT-2.0 file and is read by event_read.read_events_aedat2
+(csrc/events_aedat2_read.hip): it needs --width and --height, the sensor size, and --aedat_layout names its address word (jAER's
+DAVIS word, the default, or the word this tool and v2e.py --events_aedat2 write); the two text flags are refused.  With a .csv or
+.txt OUT this is the device counterpart of the reference's aedat_to_csv.py for AEDAT-2.0 files.
 """
 import argparse
 import os
@@ -29,8 +35,10 @@ def convert_args(parser):
     parser.add_argument("--delim_whitespace", action="store_true", default=False, help="fields are separated by blanks, not commas")
     parser.add_argument("--swap_xy", action="store_true", default=False, help="the second column of the input is y, the third x")
     parser.add_argument("--output", type=str, required=True, help="file to write; the extension picks the format: %s" % ", ".join(FORMATS))
-    parser.add_argument("--width", type=int, default=None, help="sensor width in pixels (.aedat only)")
-    parser.add_argument("--height", type=int, default=None, help="sensor height in pixels (.aedat only)")
+    parser.add_argument("--width", type=int, default=None, help="sensor width in pixels (.aedat input or output only)")
+    parser.add_argument("--height", type=int, default=None, help="sensor height in pixels (.aedat input or output only)")
+    parser.add_argument("--aedat_layout", choices=("davis", "v2e"), default="davis",
+                        help="address word of an .aedat input: jAER's DAVIS word, or the word the .aedat output here has")
     return parser
 
 
@@ -41,6 +49,12 @@ def main(argv=None):
         sys.exit("events_convert: --output %s: the extension must be one of %s" % (args.output, ", ".join(FORMATS)))
     if ext == ".aedat" and (args.width is None or args.height is None):
         sys.exit("events_convert: an .aedat output needs --width and --height")
+    aedat_in = args.events_file.lower().endswith((".aedat", ".aedat2"))
+    if aedat_in and (args.width is None or args.height is None):
+        sys.exit("events_convert: an .aedat input needs --width and --height, the sensor size")
+    if aedat_in and (args.delim_whitespace or args.swap_xy):
+        sys.exit("events_convert: --delim_whitespace and --swap_xy describe a text file and cannot be used with the AEDAT-2.0 "
+                 "input %s" % args.events_file)
     if not os.path.isfile(args.events_file):
         sys.exit("events_convert: --events_file %s is not a file" % args.events_file)
     import scpose  # noqa: F401
@@ -52,7 +66,15 @@ def main(argv=None):
         except ValueError as e:
             sys.exit("events_convert: %s" % e)
     ops = import_module("spacecraft-pose-estimation_amd.ops")
-    t, x, y, p = ops.parse_events_csv(args.events_file, delim_whitespace=args.delim_whitespace, swap_xy=args.swap_xy)
+    if aedat_in:
+        er = import_module("spacecraft-pose-estimation_amd.event_read")
+        try:
+            t, x, y, p, info = er.read_events_aedat2(args.events_file, (args.height, args.width), layout=args.aedat_layout)
+        except ValueError as e:
+            sys.exit("events_convert: %s" % e)
+        print("events_convert: %s: %s" % (args.events_file, ", ".join("%s=%d" % kv for kv in sorted(info.items()))))
+    else:
+        t, x, y, p = ops.parse_events_csv(args.events_file, delim_whitespace=args.delim_whitespace, swap_xy=args.swap_xy)
     if ext == ".aedat":
         try:
             n = ew.write_events_aedat2(args.output, t, x, y, p, (args.height, args.width))

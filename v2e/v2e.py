@@ -13,7 +13,8 @@ from the reference's DVSTextOutput, which writes float seconds and the constant 
 readers' cast to int64, and the real polarity is written.  The text is formatted on the device and streamed to the file
 (event_write.write_events_text); write_text below states the same bytes in Python.  --events_aedat2 NAME adds
 <output_folder>/<NAME>.aedat, the AEDAT-2.0 file the reference's AEDat2Output writes for jAER (same records, a header without
-date and user lines), for the reference's five sensor sizes.
+date and user lines), for the reference's five sensor sizes; e2v.py --aedat_layout v2e reads such a file back (all sizes but
+1280x720, whose address word cannot be inverted).
 
 Only the emulator core and these two writers exist here.  SloMo interpolation, video input / output, the h5 writer, the
 reference's --dvs_aedat2 and --ddd_output, shot noise and leak jitter do not: their arguments are refused by name, not ignored.
