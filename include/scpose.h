@@ -426,6 +426,43 @@ int32_t scpose_events_aedat2_unpack(const uint8_t* records, int64_t n_records, i
                                     int64_t* t, int32_t* x, int32_t* y, int8_t* p, int64_t capacity,
                                     int64_t* count_status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* (ABI 7, additive) Baseline JPEG files on the device (csrc/jpeg_decode.hip): the bytes of N files of one geometry -> (N, H, W, 3)
+ * uint8 frames, bit for bit what libjpeg's baseline decoder returns (Huffman decoding, jidctint.c's ISLOW inverse DCT, jdsample.c's
+ * fancy h2v2 upsampling, jdcolor.c's YCbCr -> RGB).  Decoded: SOF0, 8 bits, one interleaved scan, one component (SCPOSE_JPEG_GRAY)
+ * or YCbCr at 4:4:4 (SCPOSE_JPEG_444) or 4:2:0 (SCPOSE_JPEG_420), any tables, any restart interval, any width and height.  The
+ * host walks the markers (jpeg_read.py: parse_jpeg refuses everything else by name) and packs, little endian:
+ *   desc         device u8 [n][SCPOSE_JPEG_DESC_BYTES], 8-byte aligned.  Per image: int64 offset of the file in `data`; int32
+ *                first row of the image in `segs`, number of restart segments, number of subsequences, restart interval in MCUs
+ *                (the whole image when the file has none); zeros up to byte 64; uint16 [3][64] quantisation table of each
+ *                component in natural order; from byte 448 six tables of 1424 bytes, component c's DC (2 c) and AC (2 c + 1):
+ *                uint16 [512] indexed by the next 9 bits (code length << 8 | symbol, 0: the code is longer), int32 [18]
+ *                libjpeg's maxcode, int32 [18] its valoffset, uint8 [256] huffval
+ *   segs         device i32 [n_seg_rows][4]: per restart segment the first byte and the end of its raw bytes relative to the
+ *                file, the index of its first subsequence inside the image, 0; after an image's segments one closing row whose
+ *                third word is the image's number of subsequences.  A segment of L raw bytes has max(1, ceil(L /
+ *                SCPOSE_JPEG_SUBSEQ_BYTES)) subsequences.  A row that points outside `data` is treated as an empty segment.
+ *   data         device u8 [n_bytes]: the files, one after the other
+ *   max_subs     the most subsequences of one image of the batch (an image that claims more gets SCPOSE_JPEG_CORRUPT)
+ *   bgr          0: R, G, B order; != 0: B, G, R
+ *   max_rounds   1 .. 250 launches of the relaxation that finds the entry state of every subsequence (see the .hip file); an
+ *                image for which an entry still changed in the last launch gets SCPOSE_JPEG_NOT_CONVERGED
+ *   out          device u8 [n][h][w][3], 4-byte aligned;  y_out  device u8 [n][h][w] <- the luminance plane, or NULL
+ *   status       device i32 [n] <- SCPOSE_JPEG_NOT_CONVERGED | SCPOSE_JPEG_CORRUPT | rounds used << 8 (bits 8 .. 15).  CORRUPT:
+ *                a restart segment holds more or fewer blocks than the header implies, a code that no table holds, a run past
+ *                coefficient 63; next to NOT_CONVERGED the bit says nothing.  The pixels of an image with a status bit set are unspecified; nothing outside the outputs
+ *                and the workspace is ever written.
+ *   workspace    caller-owned, 256-byte aligned, scpose_jpeg_decode_workspace_bytes(n, h, w, mode, max_subs)
+ * No allocation, no synchronisation, no floating point, no atomics but integer ORs into status; two calls on the same bytes give
+ * bitwise equal outputs.  Argument errors return -1 with a message before anything is launched. */
+enum { SCPOSE_JPEG_GRAY = 0, SCPOSE_JPEG_444 = 1, SCPOSE_JPEG_420 = 2 };
+enum { SCPOSE_JPEG_NOT_CONVERGED = 1, SCPOSE_JPEG_CORRUPT = 2 };
+#define SCPOSE_JPEG_SUBSEQ_BYTES 128
+#define SCPOSE_JPEG_DESC_BYTES 9216
+int32_t scpose_jpeg_decode_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t mode, int32_t max_subs, size_t* bytes);
+int32_t scpose_jpeg_decode(const uint8_t* desc, const int32_t* segs, int64_t n_seg_rows, const uint8_t* data, int64_t n_bytes,
+                           int32_t n, int32_t h, int32_t w, int32_t mode, int32_t max_subs, int32_t bgr, int32_t max_rounds,
+                           uint8_t* out, uint8_t* y_out, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 /* (ABI 7, additive) DVS emulator core on the device (csrc/dvs_emulator.hip): time-stamped grayscale uint8 frames -> an event
  * stream, in the columns scpose_events_frame_bounds / scpose_events_render take.  Restates EventEmulator._init / generate_events
  * of the reference's v2e/v2ecore/emulator.py (with lin_log, rescale_intensity_frame, low_pass_filter, subtract_leak_current,

@@ -264,6 +264,45 @@ extern "C" int32_t scpose_events_aedat2_unpack(const uint8_t* records, int64_t n
                                      capacity, count_status, static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
 }
 
+static int32_t jpeg_check_shape(int32_t n, int32_t h, int32_t w, int32_t mode, int32_t max_subs, const char* who) {
+  SCP_REQUIRE(mode == SCPOSE_JPEG_GRAY || mode == SCPOSE_JPEG_444 || mode == SCPOSE_JPEG_420,
+              "%s: mode=%d: the modes are 0 (gray), 1 (4:4:4) and 2 (4:2:0)", who, mode);
+  SCP_REQUIRE(n >= 1 && n <= 65535, "%s: n=%d (1 .. 65535)", who, n);
+  SCP_REQUIRE(h >= 1 && h <= 65535 && w >= 1 && w <= 65535, "%s: frame %dx%d (HxW), each 1 .. 65535", who, h, w);
+  SCP_REQUIRE(max_subs >= 1 && max_subs <= (1 << 24), "%s: max_subs=%d (1 .. 2^24)", who, max_subs);
+  SCP_REQUIRE((int64_t)n * jpeg_decode_blocks(h, w, mode) < ((int64_t)1 << 31) && (int64_t)n * max_subs < ((int64_t)1 << 31),
+              "%s: n * blocks and n * max_subs must stay below 2^31: decode the batch in parts", who);
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_jpeg_decode_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t mode, int32_t max_subs, size_t* bytes) {
+  SCP_REQUIRE(bytes, "jpeg_decode_workspace_bytes: null argument");
+  if (int32_t rc = jpeg_check_shape(n, h, w, mode, max_subs, "jpeg_decode_workspace_bytes")) return rc;
+  *bytes = jpeg_decode_workspace_bytes(n, h, w, mode, max_subs);
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_jpeg_decode(const uint8_t* desc, const int32_t* segs, int64_t n_seg_rows, const uint8_t* data, int64_t n_bytes,
+                                      int32_t n, int32_t h, int32_t w, int32_t mode, int32_t max_subs, int32_t bgr, int32_t max_rounds,
+                                      uint8_t* out, uint8_t* y_out, int32_t* status, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+  if (int32_t rc = jpeg_check_shape(n, h, w, mode, max_subs, "jpeg_decode")) return rc;
+  SCP_REQUIRE(max_rounds >= 1 && max_rounds <= 250, "jpeg_decode: max_rounds=%d (1 .. 250)", max_rounds);
+  SCP_REQUIRE(n_seg_rows >= 2 * (int64_t)n && n_seg_rows < ((int64_t)1 << 31) && n_bytes >= 0, "jpeg_decode: n_seg_rows=%lld n_bytes=%lld",
+              (long long)n_seg_rows, (long long)n_bytes);
+  SCP_REQUIRE(desc && segs && (data || n_bytes == 0) && out && status, "jpeg_decode: null argument");
+  SCP_REQUIRE((reinterpret_cast<uintptr_t>(desc) & 7) == 0 && (reinterpret_cast<uintptr_t>(segs) & 3) == 0 &&
+                  (reinterpret_cast<uintptr_t>(out) & 3) == 0 && (reinterpret_cast<uintptr_t>(y_out) & 3) == 0 &&
+                  (reinterpret_cast<uintptr_t>(status) & 3) == 0,
+              "jpeg_decode: desc must be 8-byte aligned, segs, out, y_out and status 4-byte aligned");
+  const size_t need = jpeg_decode_workspace_bytes(n, h, w, mode, max_subs);
+  SCP_REQUIRE(workspace && workspace_bytes >= need, "jpeg_decode: workspace of %zu bytes needed (got %zu)", need,
+              workspace ? workspace_bytes : (size_t)0);
+  SCP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "jpeg_decode: workspace must be 256-byte aligned");
+  return jpeg_decode_launch(desc, segs, n_seg_rows, data, n_bytes, n, h, w, mode, max_subs, bgr != 0, max_rounds, out, y_out, status,
+                            static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
 static int32_t dvs_check_params(const scpose_dvs_params* p, const char* who) {
   SCP_REQUIRE(p, "%s: null params", who);
   SCP_REQUIRE(p->h > 0 && p->w > 0 && (int64_t)p->h * p->w <= (1 << 24), "%s: bad shape h=%d w=%d", who, p->h, p->w);

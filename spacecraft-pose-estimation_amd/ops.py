@@ -540,6 +540,127 @@ def unpack_events_aedat2(records, hw, layout="davis", flip_x=True, flip_y=True, 
     return t[:rows].clone(), x[:rows].clone(), y[:rows].clone(), p[:rows].clone(), info
 
 
+# ------------------------------------------------------------------ baseline JPEG files -> frames
+JPEG_MAX_ROUNDS = 96          # launches of the relaxation (measured distribution and head-room)
+_JPEG_WORKSPACE = {}          # device index -> uint8 tensor, grown on demand (2 bytes per coefficient: too large to allocate per call)
+
+
+def _jpeg_workspace(dev, nbytes):
+    ws = _JPEG_WORKSPACE.get(dev.index)
+    if ws is None or ws.numel() < nbytes:
+        _JPEG_WORKSPACE.pop(dev.index, None)
+        ws = None
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+        _JPEG_WORKSPACE[dev.index] = ws
+    return ws
+
+
+def _jpeg_decode_group(headers, files, rgb, max_rounds, dev, out=None, y_out=None):
+    """One scpose_jpeg_decode call on the current stream for images of one geometry; -> (frames, status list)."""
+    from . import jpeg_read as jr
+    h, w, mode = headers[0].geometry
+    n = len(headers)
+    desc, rows, data, max_subs = jr.pack_batch(headers, files)
+    lib = nat.lib()
+    ws = c_size_t()
+    nat.check(lib.scpose_jpeg_decode_workspace_bytes(n, h, w, jr.MODES[mode], max_subs, ctypes.byref(ws)), "jpeg_decode_workspace_bytes")
+    with torch.cuda.device(dev):
+        d_desc = torch.from_numpy(desc).to(dev, non_blocking=True)
+        d_rows = torch.from_numpy(rows).to(dev, non_blocking=True)
+        d_data = torch.from_numpy(data).to(dev, non_blocking=True)
+        if out is None:
+            out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        work = _jpeg_workspace(dev, ws.value)
+        nat.check(lib.scpose_jpeg_decode(_ptr(d_desc), _ptr(d_rows), int(rows.shape[0]), _ptr(d_data), int(data.size), n, h, w,
+                                         jr.MODES[mode], int(max_subs), 0 if rgb else 1, int(max_rounds), _ptr(out), _ptr(y_out),
+                                         _ptr(status), _ptr(work), ws.value, _stream()), "jpeg_decode")
+        return out, status.tolist()
+
+
+def _jpeg_host_decode(data, rgb):
+    import io
+    from PIL import Image
+    from . import jpeg_read as jr
+    try:
+        with Image.open(io.BytesIO(data)) as im:
+            arr = np.array(im.convert("RGB"))          # a copy: the decoder's own array is read-only
+    except Exception as e:
+        raise jr.JpegError("decode_jpeg: the host decoder cannot read the file either: %s" % e)
+    return arr if rgb else arr[:, :, ::-1].copy()
+
+
+def decode_jpeg(files, rgb=True, device=None, max_rounds=None, fallback=True):
+    """Baseline JPEG files -> ((N, H, W, 3) uint8 frames on the device, info), decoded by csrc/jpeg_decode.hip bit for bit as
+    libjpeg (PIL, cv2.imread) decodes them.  files: a list of bytes or of paths; all frames must have one size.  rgb: R, G, B
+    order, else B, G, R (what cv2.imread returns).  Files are grouped by (height, width, sampling) and every group is one call.
+    info = {"rounds": per image the relaxation rounds used (0: not decoded on the device), "fallback": {index: reason}}.
+    A file jpeg_read.parse_jpeg refuses, or one whose entry states have not converged after max_rounds launches, is decoded by PIL
+    on the host when `fallback`, else raises UnsupportedJpeg / JpegError.  A corrupt or truncated stream always raises JpegError."""
+    from . import jpeg_read as jr
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if dev.type != "cuda":
+        raise nat.NativeError("decode_jpeg needs a ROCm device (got %s); there is no CPU path" % dev)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    rounds_cap = JPEG_MAX_ROUNDS if max_rounds is None else int(max_rounds)
+    blobs = []
+    for f in files:
+        if isinstance(f, (bytes, bytearray, memoryview)):
+            blobs.append(bytes(f))
+        elif torch.is_tensor(f):
+            blobs.append(f.cpu().numpy().tobytes())
+        elif isinstance(f, np.ndarray):
+            blobs.append(f.tobytes())
+        else:
+            with open(f, "rb") as fh:
+                blobs.append(fh.read())
+    n = len(blobs)
+    if n == 0:
+        raise ValueError("decode_jpeg: no files")
+    headers, host, groups = [None] * n, {}, {}
+    for i, b in enumerate(blobs):
+        try:
+            headers[i] = jr.parse_jpeg(b)
+            groups.setdefault(headers[i].geometry, []).append(i)
+        except jr.UnsupportedJpeg as e:
+            if not fallback:
+                raise
+            host[i] = str(e)
+    rounds = [0] * n
+    decoded = {}                    # index -> (group tensor, row)
+    for geom, idx in groups.items():
+        frames, status = _jpeg_decode_group([headers[i] for i in idx], [blobs[i] for i in idx], rgb, rounds_cap, dev)
+        for row, i in enumerate(idx):
+            st = status[row]
+            rounds[i] = (st >> 8) & 255
+            # not converged: the walk started from entries that are not the stream's, so CORRUPT says nothing; the host decides
+            if st & nat.JPEG_CORRUPT and not st & nat.JPEG_NOT_CONVERGED:
+                raise jr.JpegError("decode_jpeg: file %d: corrupt or truncated entropy-coded data" % i)
+            if st & nat.JPEG_NOT_CONVERGED:
+                reason = "entry states not converged after %d rounds" % rounds_cap
+                if not fallback:
+                    raise jr.JpegError("decode_jpeg: file %d: %s" % (i, reason))
+                host[i] = reason
+            else:
+                decoded[i] = (frames, row)
+    host_px = {i: _jpeg_host_decode(blobs[i], rgb) for i in host}
+    sizes = {(h.height, h.width) for i, h in enumerate(headers) if i in decoded} | {a.shape[:2] for a in host_px.values()}
+    if len(sizes) != 1:
+        raise ValueError("decode_jpeg: the frames have different sizes %s: decode them in separate calls" % sorted(sizes))
+    info = {"rounds": rounds, "fallback": host}
+    if len(groups) == 1 and not host:
+        return next(iter(decoded.values()))[0], info
+    (hh, ww), = sizes
+    with torch.cuda.device(dev):
+        out = torch.empty((n, hh, ww, 3), dtype=torch.uint8, device=dev)
+        for i, (frames, row) in decoded.items():
+            out[i].copy_(frames[row])
+        for i, arr in host_px.items():
+            out[i].copy_(torch.from_numpy(np.ascontiguousarray(arr)))
+    return out, info
+
+
 class DvsEmulator:
     """Device DVS emulator (csrc/dvs_emulator.hip): see dvs_emulator().  The state lives in device memory between calls."""
 
