@@ -176,6 +176,7 @@ def decode_sequential(st):
     h = st.h
     coef = np.zeros((h.n_blocks, 64), dtype=np.int32)
     states = []
+    st.invalid = False                                            # a speculative walk of relax() before may have set it
     per_seg = h.mcus_per_segment * st.bpm
     zz = J.ZIGZAG.tolist()
     for si, seg in enumerate(st.segs):
