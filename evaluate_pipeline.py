@@ -13,7 +13,7 @@ levels up (:66) although it is one level below the root, and stage 3 reads pred.
 pred_test.mat (both are written here).
 
 Extensions (all optional): --cfg, --regression_opts KEY VAL ..., --nproc_per_node N (frames of a scene sharded over N
-GPUs, one process each), --no_overlay.
+GPUs, one process each), --no_overlay, --device_overlay.
 """
 import argparse
 import os
@@ -48,6 +48,8 @@ def parse_args(argv=None):
     p.add_argument("--regression_opts", nargs="*", default=[], help="extra yacs KEY VAL overrides for tools/test.py")
     p.add_argument("--nproc_per_node", type=int, default=1)
     p.add_argument("--no_overlay", action="store_true")
+    p.add_argument("--device_overlay", action="store_true",
+                   help="stage 3: passed to export_predicted_poses_real.py (overlay JPEGs drawn and encoded on the device)")
     p.add_argument("--pnp_refine", choices=("none", "lm"), default="none",
                    help="stage 3: passed to export_predicted_poses_real.py (lm: Levenberg-Marquardt refinement of the poses)")
     return p.parse_args(argv)
@@ -118,7 +120,7 @@ def main(argv=None):
              "--pose_annotations", pred, "--landmarks_file", under("pose", a.landmarks_file),
              "--calibration_file_path", a.calibration_file_path if os.path.isabs(a.calibration_file_path)
              else os.path.join(ROOT, a.calibration_file_path), "--output_dir", j["pose_out"]]
-            + (["--no_overlay"] if a.no_overlay else []) + (["--pnp_refine", a.pnp_refine] if a.pnp_refine != "none" else []),
+            + (["--no_overlay"] if a.no_overlay else []) + (["--device_overlay"] if a.device_overlay else []) + (["--pnp_refine", a.pnp_refine] if a.pnp_refine != "none" else []),
             STAGE_DIRS["pose"])
     return [j["pose_out"] for j in jobs]
 

@@ -463,6 +463,41 @@ int32_t scpose_jpeg_decode(const uint8_t* desc, const int32_t* segs, int64_t n_s
                            int32_t n, int32_t h, int32_t w, int32_t mode, int32_t max_subs, int32_t bgr, int32_t max_rounds,
                            uint8_t* out, uint8_t* y_out, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* (ABI 7, additive) Baseline JPEG encoder on the device (csrc/jpeg_encode.hip): (N, H, W, 3) uint8 RGB frames of one size ->
+ * N baseline JPEG byte streams, byte for byte what libjpeg's baseline encoder writes with the standard Huffman tables (PIL's
+ * save(quality=q, subsampling=..) with its other defaults): jccolor.c, jcsample.c's h2v2 downsampling, jfdctint.c's forward
+ * DCT, jcdctmgr.c's quantiser, jchuff.c's coder, one interleaved scan, no restart interval.  mode: SCPOSE_JPEG_GRAY (one
+ * component, Y of the three channels), SCPOSE_JPEG_444 or SCPOSE_JPEG_420.  quality 1 .. 100 scales the standard quantisation
+ * tables as jcparam.c does.  The host (jpeg_write.py) supplies
+ *   huff         device u32 [4][256], 4-byte aligned: DC luminance, AC luminance, DC chrominance, AC chrominance; per symbol
+ *                code | length << 16
+ *   header       device u8 [header_bytes] (1 .. 65535): the bytes from SOI up to and including SOS, copied in front of every stream
+ *   out          device u8 [capacity]: the streams packed in image order; stream i is out[offsets[i] .. offsets[i + 1])
+ *   offsets      device i64 [n + 1], 8-byte aligned; written for every image, whether it fits or not
+ *   status       device i32 [n] <- 0, SCPOSE_JPEG_ENC_CAPACITY (offsets[i + 1] > capacity: not one byte of the image is
+ *                written; every image behind it has the bit too) or SCPOSE_JPEG_ENC_TABLES (huff is not a Huffman code of at
+ *                most 16 bits: the image's bits exceed 1728 per block)
+ *   workspace    caller-owned, 256-byte aligned, scpose_jpeg_encode_workspace_bytes(n, h, w, mode)
+ * scpose_jpeg_encode_capacity_bytes: n * (header_bytes + 432 * blocks + 2), a capacity no frame content exceeds (at most
+ * 16 + 11 bits per coefficient, doubled by byte stuffing, EOI).  Nothing is ever written past out[capacity).  An image is limited
+ * to 2^31 / 2800 blocks.  No allocation, no synchronisation, no floating point, integer atomics only; two calls on the same
+ * frames give bitwise equal outputs.  Argument errors return -1 with a message before anything is launched. */
+enum { SCPOSE_JPEG_ENC_CAPACITY = 1, SCPOSE_JPEG_ENC_TABLES = 2 };
+int32_t scpose_jpeg_encode_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t mode, size_t* bytes);
+int32_t scpose_jpeg_encode_capacity_bytes(int32_t n, int32_t h, int32_t w, int32_t mode, int32_t header_bytes, int64_t* bytes);
+int32_t scpose_jpeg_encode(const uint8_t* frames, int32_t n, int32_t h, int32_t w, int32_t mode, int32_t quality, const uint32_t* huff,
+                           const uint8_t* header, int32_t header_bytes, uint8_t* out, int64_t capacity, int64_t* offsets,
+                           int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
+/* (ABI 7, additive) Pose overlay on the device (csrc/jpeg_encode.hip), in place on (N, H, W, 3) uint8 RGB frames: per frame the
+ * outline of PIL's ImageDraw.rectangle([x, y, x + w, y + h], outline=(0, 255, 0), width=2), then for every finite point the disc
+ * of ImageDraw.ellipse([int(px) - 5, int(py) - 5, int(px) + 5, int(py) + 5], fill=(0, 0, 255)), clipped to the frame.
+ *   bboxes       device i32 [n][4]: x, y, w, h with w >= 1 and h >= 2 (PIL draws thinner boxes as lines; not reproduced)
+ *   points       device f64 [n][j][2] (8-byte aligned; null when j = 0): a point with a NaN or an infinity is skipped, int()
+ *                truncates toward zero */
+int32_t scpose_overlay_draw(uint8_t* frames, int32_t n, int32_t h, int32_t w, const int32_t* bboxes, const double* points, int32_t j,
+                            void* stream);
+
 /* (ABI 7, additive) DVS emulator core on the device (csrc/dvs_emulator.hip): time-stamped grayscale uint8 frames -> an event
  * stream, in the columns scpose_events_frame_bounds / scpose_events_render take.  Restates EventEmulator._init / generate_events
  * of the reference's v2e/v2ecore/emulator.py (with lin_log, rescale_intensity_frame, low_pass_filter, subtract_leak_current,

@@ -2,7 +2,8 @@
 """Drop-in for the reference's pose_estimation/export_predicted_poses_real.py (:126-236): same six
 required arguments, same opencv_poses.json + overlay JPEGs; the per-frame cv2.solvePnPRansac
 loop is one batched launch of the HIP EPnP+RANSAC kernel.  --no_overlay skips the debug JPEGs
-(image I/O dominates the reference script's wall-clock; the poses do not depend on it).  --pnp_refine lm adds a
+(image I/O dominates the reference script's wall-clock; the poses do not depend on it); --device_overlay writes the same
+JPEGs from the device (decode, draw and encode in HIP kernels).  --pnp_refine lm adds a
 Levenberg-Marquardt refinement of each pose on its inliers (default none: the reference's poses, byte for byte)."""
 import argparse
 import os
@@ -27,6 +28,8 @@ def main():
     parser.add_argument("--calibration_file_path", required=True, type=str, help="file with camera calibration parameters")
     parser.add_argument("--output_dir", required=True, type=str, help="output directory")
     parser.add_argument("--no_overlay", action="store_true", help="do not write the per-frame reprojection JPEGs")
+    parser.add_argument("--device_overlay", action="store_true",
+                        help="draw and encode the reprojection JPEGs on the device (the same files, byte for byte)")
     parser.add_argument("--with_status", action="store_true", help="add the per-frame RANSAC status to the JSON records")
     parser.add_argument("--pnp_refine", choices=("none", "lm"), default="none",
                         help="lm: Levenberg-Marquardt refinement of each pose on its RANSAC inliers (20 iterations, "
@@ -34,7 +37,7 @@ def main():
     args = parser.parse_args()
     pose_export.export(args.frames_dir, args.detection_annotations, args.pose_annotations, args.landmarks_file,
                        args.calibration_file_path, args.output_dir, overlay=not args.no_overlay,
-                       include_status=args.with_status, refine_iters=PNP_REFINE_ITERS[args.pnp_refine])
+                       include_status=args.with_status, refine_iters=PNP_REFINE_ITERS[args.pnp_refine], device_overlay=args.device_overlay)
 
 
 if __name__ == "__main__":

@@ -30,6 +30,7 @@ AEDAT2_READ_RANGE, AEDAT2_READ_CAPACITY = 1, 2
 JPEG_GRAY, JPEG_444, JPEG_420 = 0, 1, 2
 JPEG_NOT_CONVERGED, JPEG_CORRUPT = 1, 2
 JPEG_SUBSEQ_BYTES, JPEG_DESC_BYTES = 128, 9216
+JPEG_ENC_CAPACITY, JPEG_ENC_TABLES = 1, 2
 ABI_VERSION = 7
 
 
@@ -136,6 +137,11 @@ SYMBOLS = {
     "scpose_jpeg_decode_workspace_bytes": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
     "scpose_jpeg_decode": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                      c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "scpose_jpeg_encode_workspace_bytes": (c_int32, [c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
+    "scpose_jpeg_encode_capacity_bytes": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int64)]),
+    "scpose_jpeg_encode": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
+                                     c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "scpose_overlay_draw": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
     "scpose_dvs_state_bytes": (c_int32, [c_int32, c_int32, POINTER(c_size_t)]),
     "scpose_dvs_workspace_bytes": (c_int32, [c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
     "scpose_dvs_init": (c_int32, [c_void_p, c_void_p, c_double, POINTER(DvsParams), c_void_p]),

@@ -303,6 +303,61 @@ extern "C" int32_t scpose_jpeg_decode(const uint8_t* desc, const int32_t* segs, 
                             static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
 }
 
+static int32_t jpeg_encode_check_shape(int32_t n, int32_t h, int32_t w, int32_t mode, const char* who) {
+  SCP_REQUIRE(mode == SCPOSE_JPEG_GRAY || mode == SCPOSE_JPEG_444 || mode == SCPOSE_JPEG_420,
+              "%s: mode=%d: the modes are 0 (gray), 1 (4:4:4) and 2 (4:2:0)", who, mode);
+  SCP_REQUIRE(n >= 1 && n <= 65535, "%s: n=%d (1 .. 65535)", who, n);
+  SCP_REQUIRE(h >= 1 && h <= 65535 && w >= 1 && w <= 65535, "%s: frame %dx%d (HxW), each 1 .. 65535", who, h, w);
+  SCP_REQUIRE(jpeg_encode_blocks(h, w, mode) * 2800 < ((int64_t)1 << 31),
+              "%s: frame %dx%d (HxW): the bits of one image must stay below 2^31 (blocks * 2800)", who, h, w);
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_jpeg_encode_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t mode, size_t* bytes) {
+  SCP_REQUIRE(bytes, "jpeg_encode_workspace_bytes: null argument");
+  if (int32_t rc = jpeg_encode_check_shape(n, h, w, mode, "jpeg_encode_workspace_bytes")) return rc;
+  *bytes = jpeg_encode_workspace_bytes(n, h, w, mode);
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_jpeg_encode_capacity_bytes(int32_t n, int32_t h, int32_t w, int32_t mode, int32_t header_bytes, int64_t* bytes) {
+  SCP_REQUIRE(bytes, "jpeg_encode_capacity_bytes: null argument");
+  if (int32_t rc = jpeg_encode_check_shape(n, h, w, mode, "jpeg_encode_capacity_bytes")) return rc;
+  SCP_REQUIRE(header_bytes >= 1 && header_bytes <= 65535, "jpeg_encode_capacity_bytes: header_bytes=%d (1 .. 65535)", header_bytes);
+  *bytes = jpeg_encode_capacity_bytes(n, h, w, mode, header_bytes);
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_jpeg_encode(const uint8_t* frames, int32_t n, int32_t h, int32_t w, int32_t mode, int32_t quality,
+                                      const uint32_t* huff, const uint8_t* header, int32_t header_bytes, uint8_t* out, int64_t capacity,
+                                      int64_t* offsets, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int32_t rc = jpeg_encode_check_shape(n, h, w, mode, "jpeg_encode")) return rc;
+  SCP_REQUIRE(quality >= 1 && quality <= 100, "jpeg_encode: quality=%d (1 .. 100)", quality);
+  SCP_REQUIRE(header_bytes >= 1 && header_bytes <= 65535, "jpeg_encode: header_bytes=%d (1 .. 65535)", header_bytes);
+  SCP_REQUIRE(capacity >= 0, "jpeg_encode: capacity=%lld", (long long)capacity);
+  SCP_REQUIRE(frames && huff && header && (out || capacity == 0) && offsets && status, "jpeg_encode: null argument");
+  SCP_REQUIRE((reinterpret_cast<uintptr_t>(huff) & 3) == 0 && (reinterpret_cast<uintptr_t>(offsets) & 7) == 0 &&
+                  (reinterpret_cast<uintptr_t>(status) & 3) == 0,
+              "jpeg_encode: huff and status must be 4-byte aligned, offsets 8-byte aligned");
+  const size_t need = jpeg_encode_workspace_bytes(n, h, w, mode);
+  SCP_REQUIRE(workspace && workspace_bytes >= need, "jpeg_encode: workspace of %zu bytes needed (got %zu)", need,
+              workspace ? workspace_bytes : (size_t)0);
+  SCP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "jpeg_encode: workspace must be 256-byte aligned");
+  return jpeg_encode_launch(frames, n, h, w, mode, quality, huff, header, header_bytes, out, capacity, offsets, status,
+                            static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t scpose_overlay_draw(uint8_t* frames, int32_t n, int32_t h, int32_t w, const int32_t* bboxes, const double* points,
+                                       int32_t j, void* stream) {
+  SCP_REQUIRE(n >= 1 && n <= 65535, "overlay_draw: n=%d (1 .. 65535)", n);
+  SCP_REQUIRE(h >= 1 && h <= 65535 && w >= 1 && w <= 65535, "overlay_draw: frame %dx%d (HxW), each 1 .. 65535", h, w);
+  SCP_REQUIRE(j >= 0 && j <= 65535, "overlay_draw: j=%d (0 .. 65535)", j);
+  SCP_REQUIRE(frames && bboxes && (points || j == 0), "overlay_draw: null argument");
+  SCP_REQUIRE((reinterpret_cast<uintptr_t>(bboxes) & 3) == 0 && (reinterpret_cast<uintptr_t>(points) & 7) == 0,
+              "overlay_draw: bboxes must be 4-byte aligned, points 8-byte aligned");
+  return overlay_draw_launch(frames, n, h, w, bboxes, points, j, static_cast<hipStream_t>(stream));
+}
+
 static int32_t dvs_check_params(const scpose_dvs_params* p, const char* who) {
   SCP_REQUIRE(p, "%s: null params", who);
   SCP_REQUIRE(p->h > 0 && p->w > 0 && (int64_t)p->h * p->w <= (1 << 24), "%s: bad shape h=%d w=%d", who, p->h, p->w);

@@ -285,6 +285,15 @@ int64_t jpeg_decode_blocks(int h, int w, int mode);
 int32_t jpeg_decode_launch(const uint8_t* desc, const int32_t* segs, int64_t n_rows, const uint8_t* data, int64_t n_bytes, int n, int h,
                            int w, int mode, int max_subs, int bgr, int max_rounds, uint8_t* out, uint8_t* y_out, int32_t* status,
                            uint8_t* ws, hipStream_t stream);
+
+// jpeg_encode.hip: (N, H, W, 3) uint8 frames -> baseline JPEG byte streams; the overlay draw in front of it
+int64_t jpeg_encode_blocks(int h, int w, int mode);
+size_t jpeg_encode_workspace_bytes(int n, int h, int w, int mode);
+int64_t jpeg_encode_capacity_bytes(int n, int h, int w, int mode, int header_bytes);
+int32_t jpeg_encode_launch(const uint8_t* frames, int n, int h, int w, int mode, int quality, const uint32_t* huff, const uint8_t* header,
+                           int header_bytes, uint8_t* out, int64_t capacity, int64_t* offsets, int32_t* status, uint8_t* ws,
+                           hipStream_t stream);
+int32_t overlay_draw_launch(uint8_t* frames, int n, int h, int w, const int32_t* bboxes, const double* points, int j, hipStream_t stream);
 // dvs_emulator.hip: intensity frames -> event stream (v2e/v2ecore/emulator.py: EventEmulator.generate_events)
 size_t dvs_state_bytes(int h, int w);
 size_t dvs_workspace_bytes(int h, int w, int frames, int max_iters);

@@ -661,6 +661,82 @@ def decode_jpeg(files, rgb=True, device=None, max_rounds=None, fallback=True):
     return out, info
 
 
+# ------------------------------------------------------------------ frames -> baseline JPEG files; the pose overlay
+_JPEG_ENC_HUFF = {}           # device index -> the standard Huffman tables as uploaded (uint32 [4][256])
+
+
+def _frames_u8(who, frames):
+    _need_cuda(frames)
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] < 1:
+        raise ValueError("%s: frames must be (N, H, W, 3) uint8 with N >= 1 (got %s %s)" % (who, tuple(frames.shape), frames.dtype))
+    return frames.contiguous()
+
+
+def encode_jpeg(frames, quality=75, subsampling="420", device=None, comment=None):
+    """(N, H, W, 3) uint8 RGB frames -> list of N bytes objects, each the file PIL writes for the frame with
+    save(format="JPEG", quality=quality, subsampling=...) and its other defaults, byte for byte (csrc/jpeg_encode.hip).
+    subsampling: "420", "444" or "gray" (one component: Y of the three channels, PIL's convert("L")).  comment: the body of a COM
+    segment in every file, where PIL's save(comment=...) puts it.  The streams are packed on the device; the host reads the
+    offsets, then the packed bytes."""
+    from . import jpeg_write as jw
+    if torch.is_tensor(frames) and device is not None:
+        frames = frames.to(device)
+    elif not torch.is_tensor(frames):
+        frames = torch.from_numpy(np.ascontiguousarray(frames)).to(device if device is not None else "cuda")
+    frames = _frames_u8("encode_jpeg", frames)
+    if subsampling not in jw.MODES:
+        raise ValueError("encode_jpeg: subsampling=%r (420, 444, gray)" % (subsampling,))
+    n, h, w = (int(v) for v in frames.shape[:3])
+    head = jw.header(h, w, subsampling, quality, comment)
+    mode = jw.MODES[subsampling]
+    dev = frames.device
+    lib = nat.lib()
+    ws, cap = c_size_t(), c_int64()
+    nat.check(lib.scpose_jpeg_encode_workspace_bytes(n, h, w, mode, ctypes.byref(ws)), "jpeg_encode_workspace_bytes")
+    nat.check(lib.scpose_jpeg_encode_capacity_bytes(n, h, w, mode, len(head), ctypes.byref(cap)), "jpeg_encode_capacity_bytes")
+    with torch.cuda.device(dev):
+        huff = _JPEG_ENC_HUFF.get(dev.index)
+        if huff is None:
+            huff = _JPEG_ENC_HUFF[dev.index] = torch.from_numpy(jw.huff_upload().view(np.int32)).to(dev)
+        d_head = torch.frombuffer(bytearray(head), dtype=torch.uint8).to(dev)
+        out = torch.empty(cap.value, dtype=torch.uint8, device=dev)
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        work = _jpeg_workspace(dev, ws.value)
+        nat.check(lib.scpose_jpeg_encode(_ptr(frames), n, h, w, mode, int(quality), _ptr(huff), _ptr(d_head), len(head), _ptr(out),
+                                         cap.value, _ptr(offsets), _ptr(status), _ptr(work), ws.value, _stream()), "jpeg_encode")
+        off = offsets.tolist()
+        bad = [i for i, st in enumerate(status.tolist()) if st]
+        if bad:
+            raise nat.NativeError("encode_jpeg: status %s for images %s" % (status.tolist(), bad))
+        packed = out[:off[n]].cpu().numpy().tobytes()
+    return [packed[off[i]:off[i + 1]] for i in range(n)]
+
+
+def draw_overlays(frames, bboxes, points):
+    """The pose overlay of pose_export.draw_overlay in place on (N, H, W, 3) uint8 RGB device frames: per frame the green outline of
+    ImageDraw.rectangle([x, y, x + w, y + h], width=2), then a blue disc of radius 5 at (int(px), int(py)) for every point whose
+    coordinates are finite.  bboxes (N, 4) ints x, y, w, h with w >= 1 and h >= 2; points (N, J, 2) float64.  -> frames."""
+    _need_cuda(frames)
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
+        raise ValueError("draw_overlays: frames must be contiguous (N, H, W, 3) uint8 (got %s %s)" % (tuple(frames.shape), frames.dtype))
+    n, h, w = (int(v) for v in frames.shape[:3])
+    bb = np.asarray(bboxes)
+    if bb.shape != (n, 4) or not np.issubdtype(bb.dtype, np.integer):
+        raise ValueError("draw_overlays: bboxes must be (%d, 4) integers (got %s %s)" % (n, bb.shape, bb.dtype))
+    if (bb[:, 2] < 1).any() or (bb[:, 3] < 2).any() or (np.abs(bb.astype(np.int64)) >= 1 << 30).any():
+        raise ValueError("draw_overlays: every box needs 1 <= w, 2 <= h and coordinates below 2^30")
+    pts = np.ascontiguousarray(points, dtype=np.float64)
+    if pts.ndim != 3 or pts.shape[0] != n or pts.shape[2] != 2:
+        raise ValueError("draw_overlays: points must be (%d, J, 2) (got %s)" % (n, pts.shape))
+    j = int(pts.shape[1])
+    with torch.cuda.device(frames.device):
+        d_bb = torch.from_numpy(np.ascontiguousarray(bb, dtype=np.int32)).to(frames.device)
+        d_pts = torch.from_numpy(pts).to(frames.device) if j else None
+        nat.check(nat.lib().scpose_overlay_draw(_ptr(frames), n, h, w, _ptr(d_bb), _ptr(d_pts), j, _stream()), "overlay_draw")
+    return frames
+
+
 class DvsEmulator:
     """Device DVS emulator (csrc/dvs_emulator.hip): see dvs_emulator().  The state lives in device memory between calls."""
 

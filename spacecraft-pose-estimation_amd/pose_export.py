@@ -45,6 +45,12 @@ def solve_poses(preds, landmarks, K, dist, device=None, **kw):
     return block[:, :9].reshape(-1, 3, 3), block[:, 9:12], block[:, 12].astype(np.int32)
 
 
+def project_landmarks(K, R, T, landmarks):
+    """Pinhole K[R|T]X without distortion (:206-216) in float64 -> (J, 2) pixel coordinates (non-finite where the depth is 0)"""
+    pts = (K @ np.column_stack((R, T.reshape(3, 1)))) @ np.column_stack((landmarks, np.ones(len(landmarks)))).T
+    return (pts / pts[2]).T[:, :2]
+
+
 def draw_overlay(frames_dir, file_name, out_path, bbox, K, R, T, landmarks):
     """Reprojection overlay of :206-233 (pinhole K[R|T]X without distortion, green bbox, r=5 discs)."""
     from PIL import Image, ImageDraw
@@ -53,20 +59,64 @@ def draw_overlay(frames_dir, file_name, out_path, bbox, K, R, T, landmarks):
         return False
     img = Image.open(src).convert("RGB")
     d = ImageDraw.Draw(img)
-    pts = (K @ np.column_stack((R, T.reshape(3, 1)))) @ np.column_stack((landmarks, np.ones(len(landmarks)))).T
-    pts = (pts / pts[2]).T
     x, y, w, h = [int(v) for v in bbox]
     d.rectangle([x, y, x + w, y + h], outline=(0, 255, 0), width=2)
-    for px, py in pts[:, :2]:
+    for px, py in project_landmarks(K, R, T, landmarks):
         if np.isfinite(px) and np.isfinite(py):
             d.ellipse([int(px) - 5, int(py) - 5, int(px) + 5, int(py) + 5], fill=(0, 0, 255))   # BGR (255,0,0) = blue
     img.save(out_path, quality=95)
     return True
 
 
+DEVICE_OVERLAY_BATCH = 64
+
+
+def draw_overlays_device(frames_dir, jobs, K, landmarks):
+    """The files draw_overlay writes, byte for byte, with the frames on the device: jobs = [(file name, output path, bbox, R, T)].
+    Frames go in batches of one size: source JPEGs through ops.decode_jpeg, other formats through PIL and one upload, then
+    ops.draw_overlays -> ops.encode_jpeg(quality=95, "420") -> files.  A frame PIL would write differently goes through draw_overlay:
+    one whose Image.info carries a comment (the only entry of Image.info this Pillow copies into a JPEG it saves), and one whose
+    box is thinner than an outline (w < 1 or h < 2: ImageDraw draws lines) or has coordinates no int32 holds.  A missing source
+    file is skipped.  -> the number of files written"""
+    from PIL import Image
+    written, groups = 0, {}
+    for job in jobs:
+        name, out_path, bbox, R, T = job
+        src = os.path.join(frames_dir, name)
+        if not os.path.exists(src):
+            continue
+        box = [int(v) for v in bbox]
+        with Image.open(src) as im:                    # the header only: size, format, info
+            size, fmt, plain = im.size, im.format, "comment" not in im.info
+        if not plain or box[2] < 1 or box[3] < 2 or max(abs(v) for v in box) >= 1 << 30:
+            written += bool(draw_overlay(frames_dir, name, out_path, bbox, K, R, T, landmarks))
+            continue
+        groups.setdefault((size[1], size[0]), []).append((src, fmt, out_path, box, project_landmarks(K, R, T, landmarks)))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    for (h, w), items in groups.items():
+        for lo in range(0, len(items), DEVICE_OVERLAY_BATCH):
+            part = items[lo:lo + DEVICE_OVERLAY_BATCH]
+            frames = torch.empty((len(part), h, w, 3), dtype=torch.uint8, device=dev)
+            jpeg = [i for i, it in enumerate(part) if it[1] == "JPEG"]
+            other = [i for i, it in enumerate(part) if it[1] != "JPEG"]
+            if jpeg:
+                decoded, _ = ops.decode_jpeg([part[i][0] for i in jpeg], rgb=True, device=dev)
+                frames[torch.tensor(jpeg, device=dev)] = decoded
+            if other:
+                px = np.stack([np.asarray(Image.open(part[i][0]).convert("RGB")) for i in other])
+                frames[torch.tensor(other, device=dev)] = torch.from_numpy(px).to(dev)
+            ops.draw_overlays(frames, np.array([it[3] for it in part], dtype=np.int64), np.stack([it[4] for it in part]))
+            for it, data in zip(part, ops.encode_jpeg(frames, quality=95, subsampling="420")):
+                with open(it[2], "wb") as f:
+                    f.write(data)
+                written += 1
+    return written
+
+
 def export(frames_dir, detection_annotations, pose_annotations, landmarks_file, calibration_file_path, output_dir,
-           overlay=True, include_status=False, refine_iters=0):
-    """refine_iters > 0: Levenberg-Marquardt refinement of every solved pose on its final point set (ops.pnp_epnp_ransac);
+           overlay=True, include_status=False, refine_iters=0, device_overlay=False):
+    """device_overlay: the overlay JPEGs are drawn and encoded on the device (draw_overlays_device), the same bytes as the host path.
+    refine_iters > 0: Levenberg-Marquardt refinement of every solved pose on its final point set (ops.pnp_epnp_ransac);
     0 keeps the reference's EPnP-only poses."""
     Path(output_dir).mkdir(parents=True, exist_ok=True)
     landmarks = read_landmarks(landmarks_file)
@@ -83,7 +133,7 @@ def export(frames_dir, detection_annotations, pose_annotations, landmarks_file, 
     min_pts = 15                                       # :192
     kw = {"refine_iters": refine_iters} if refine_iters else {}   # only when asked: stand-ins of ops.pnp_epnp_ransac need not know it
     R, T, status = solve_poses(preds[:n], landmarks, K, dist, min_pts=min_pts, **kw)
-    poses = []
+    poses, jobs = [], []
     if parallel.world()[1] != 0:
         return poses
     for i in range(n):
@@ -94,7 +144,12 @@ def export(frames_dir, detection_annotations, pose_annotations, landmarks_file, 
         poses.append(rec)
         if overlay:
             out = os.path.join(output_dir, os.path.basename(name).split(".")[0] + ".jpg")
-            draw_overlay(frames_dir, name, out, ann["annotations"][i]["bbox"], K, R[i], T[i], landmarks)
+            if device_overlay:
+                jobs.append((name, out, ann["annotations"][i]["bbox"], R[i], T[i]))
+            else:
+                draw_overlay(frames_dir, name, out, ann["annotations"][i]["bbox"], K, R[i], T[i], landmarks)
+    if jobs:
+        draw_overlays_device(frames_dir, jobs, K, landmarks)
     with open(os.path.join(output_dir, "opencv_poses.json"), "w") as f:
         f.write(dumps_poses(poses))
     return poses
