@@ -41,8 +41,20 @@ def pil_draw(frame, bbox, points):
     return np.array(img)
 
 
+def pil_points(points):
+    """the points ImageDraw.ellipse accepts: for coordinates of 1e300 its argument parser raises (this Pillow: SystemError), so
+    a point that large is held to the restatement alone"""
+    return [(px, py) for px, py in points if not (np.isfinite(px) and np.isfinite(py)) or max(abs(px), abs(py)) < 2.0 ** 62]
+
+
+def _scatter(h, w, count, seed):
+    """count points over the frame and a margin of 8 pixels around it: discs inside, cut by every edge, and wholly outside"""
+    rng = np.random.default_rng(seed)
+    return [(float(x), float(y)) for x, y in zip(rng.uniform(-8, w + 8, count), rng.uniform(-8, h + 8, count))]
+
+
 H, W = 48, 64
-# (bbox, points) of one 64 x 48 frame each
+# name: (bbox, points); the frame is H x W unless FRAME_SIZES says otherwise
 CASES = {
     "inside": ((10, 8, 30, 20), [(32.2, 24.9)]),
     "left": ((-5, 10, 20, 20), []),
@@ -56,8 +68,24 @@ CASES = {
     "overlap": ((5, 5, 10, 10), [(30.0, 20.0), (34.5, 23.5), (12.0, 12.0)]),
     "nonfinite": ((8, 8, 8, 8), [(float("nan"), 10.0), (10.0, float("inf")), (float("-inf"), float("nan")), (40.0, 30.0)]),
     "minus_half": ((1, 1, 5, 5), [(-0.5, 20.0), (20.0, -0.5), (-0.99, -0.99)]),
+    # around the kernel's |p| < 1e9 test and the int32 conversion behind it: none of the six draws, the last point does.
+    # ImageDraw.ellipse raises for the last two of the six (pil_points): those are held to the restatement alone
+    "guards": ((8, 8, 8, 8), [(999999999.0, 5.0), (1e9, 5.0), (-1e9, 5.0), (2147483648.0, 5.0), (1e300, -1e300), (5.0, 1.7e308),
+                              (40.0, 30.0)]),
+    # a tall frame: H > W, the rows of the rectangle take fewer threads than its columns
+    "tall_inside": ((6, 20, 25, 60), _scatter(96, 40, 16, 1)),
+    "tall_crossing": ((22, 70, 30, 40), _scatter(96, 40, 17, 2)),      # over the right and the bottom edge
+    # 4 (W + H) = 3280 threads: thirteen workgroups for the rectangle, eight and more for the discs
+    "large_inside": ((100, 50, 300, 200), _scatter(300, 520, 16, 3)),
+    "large_crossing": ((-40, -25, 200, 120), _scatter(300, 520, 20, 4)),     # over the left and the top edge
 }
+FRAME_SIZES = {"tall_inside": (96, 40), "tall_crossing": (96, 40), "large_inside": (300, 520), "large_crossing": (300, 520)}     # (H, W)
+DRAWN = ("inside", "corners", "overlap", "nonfinite", "guards", "tall_inside", "tall_crossing", "large_inside", "large_crossing")
 
 
-def base_frame():
-    return np.random.default_rng(7).integers(0, 256, (H, W, 3), dtype=np.uint8)
+def size_of(case):
+    return FRAME_SIZES.get(case, (H, W))
+
+
+def base_frame(h=H, w=W):
+    return np.random.default_rng(7).integers(0, 256, (h, w, 3), dtype=np.uint8)

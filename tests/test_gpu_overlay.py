@@ -15,25 +15,40 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _draw_and_compare(gpu_ops, part):
+    """the cases `part`, all of one frame size, in one call"""
+    (h, w), = {O.size_of(c) for c in part}
+    jmax = max(max(len(O.CASES[c][1]) for c in part), 6)
+    pts = np.full((len(part), jmax, 2), np.nan)                     # a NaN point is skipped: pads the shorter lists
+    for i, c in enumerate(part):
+        p = np.asarray(O.CASES[c][1], dtype=np.float64).reshape(-1, 2)
+        pts[i, :len(p)] = p
+    frames = torch.from_numpy(np.stack([O.base_frame(h, w) for _ in part])).cuda()
+    out = gpu_ops.draw_overlays(frames, np.array([O.CASES[c][0] for c in part]), pts)
+    assert out.data_ptr() == frames.data_ptr()
+    got = out.cpu().numpy()
+    for i, c in enumerate(part):
+        bbox, p = O.CASES[c]
+        assert np.array_equal(got[i], O.draw(O.base_frame(h, w), bbox, p)), (c, "restatement")
+        assert np.array_equal(got[i], O.pil_draw(O.base_frame(h, w), bbox, O.pil_points(p))), (c, "PIL")
+    return frames, pts
+
+
 def test_draw_overlays_equals_restatement_and_pil(gpu_ops):
-    names = sorted(O.CASES)
-    jmax = max(len(O.CASES[c][1]) for c in names)
-    for lo in range(0, len(names), 4):                              # 4 frames per call
-        part = names[lo:lo + 4]
-        pts = np.full((len(part), jmax, 2), np.nan)                 # a NaN point is skipped: pads the shorter lists
-        for i, c in enumerate(part):
-            p = np.asarray(O.CASES[c][1], dtype=np.float64).reshape(-1, 2)
-            pts[i, :len(p)] = p
-        frames = torch.from_numpy(np.stack([O.base_frame() for _ in part])).cuda()
-        out = gpu_ops.draw_overlays(frames, np.array([O.CASES[c][0] for c in part]), pts)
-        assert out.data_ptr() == frames.data_ptr()
-        got = out.cpu().numpy()
-        for i, c in enumerate(part):
-            bbox, p = O.CASES[c]
-            assert np.array_equal(got[i], O.draw(O.base_frame(), bbox, p)), (c, "restatement")
-            assert np.array_equal(got[i], O.pil_draw(O.base_frame(), bbox, p)), (c, "PIL")
+    sizes = sorted({O.size_of(c) for c in O.CASES})
+    assert sizes == [(48, 64), (96, 40), (300, 520)]
+    for size in sizes:
+        names = sorted(c for c in O.CASES if O.size_of(c) == size)
+        for lo in range(0, len(names), 4):                          # 4 frames per call
+            part = names[lo:lo + 4]
+            frames, pts = _draw_and_compare(gpu_ops, part)
     with pytest.raises(ValueError):
         gpu_ops.draw_overlays(frames, np.array([[1, 1, 0, 5]] * len(part)), pts)
+
+
+def test_draw_overlays_batch_of_five(gpu_ops):
+    _draw_and_compare(gpu_ops, ["guards", "corners", "overlap", "nonfinite", "inside"])
+    _draw_and_compare(gpu_ops, ["large_crossing", "large_inside", "large_inside", "large_crossing", "large_inside"])
 
 
 def _scene(tmp_path):

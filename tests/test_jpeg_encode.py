@@ -1,11 +1,13 @@
 """The NumPy restatement of the baseline encoder equals PIL's bytes, and the restated overlay equals PIL's ImageDraw: the two pins
-the device kernels are held to (tests/test_gpu_jpeg_encode.py, tests/test_gpu_overlay.py)."""
+the device kernels are held to (tests/test_gpu_jpeg_encode.py, tests/test_gpu_jpeg_encode_edges.py, tests/test_gpu_overlay.py).
+The cases of jpeg_encode_edges.py are proven here, from PIL's bytes and the restatement alone, to have the property each exists for."""
 import importlib
 
 import numpy as np
 import pytest
 
 import jpeg_encode_cases as C
+import jpeg_encode_edges as E
 import jpeg_encode_restated as R
 import overlay_restated as O
 
@@ -53,7 +55,109 @@ def test_host_module_states_the_same_header_and_tables(scpose):
         jw.header(8, 8, "422", 75)
 
 
+# ---- the cases of jpeg_encode_edges.py: restatement == PIL, and each family has the property it is named for
+@pytest.mark.parametrize("mode", C.MODES)
+def test_multi_tile_batches_take_more_than_one_scan_tile(scpose, mode):
+    case = E.multi_tile(mode)
+    frames = case[0]
+    assert E.restated_files(("multi", mode), case) == E.pil_files(("multi", mode), case)
+    h, w = frames.shape[1:3]
+    assert E.blocks_of(h, w, mode) > E.SCAN_TILE
+    assert len(R.scan_blocks(frames[1], case[1], mode)[0]) == E.blocks_of(h, w, mode)
+    sizes = [len(E.raw_scan(f)) for f in E.pil_files(("multi", mode), case)]
+    assert sizes[0] > 4 * sizes[2] and sizes[2] > 4 * sizes[1]     # the totals of one launch differ widely
+    if mode == "420":                                              # a dummy row, a dummy column, an odd height and width
+        my, mx = -(-h // 16), -(-w // 16)
+        assert 2 * my > -(-h // 8) and 2 * mx > -(-w // 8)
+        assert h % 2 == 1 and w % 2 == 1
+
+
+def test_many_raw_tiles_frame_takes_a_second_step_of_the_tile_count_scan(scpose):
+    case = E.many_raw_tiles()
+    pil, = E.pil_files("many_raw_tiles", case)
+    assert E.restated_files("many_raw_tiles", case) == [pil]
+    assert len(E.raw_scan(pil)) > E.COUNT_STEP * E.RAW_TILE
+
+
+@pytest.mark.parametrize("name", sorted(E.EDGES))
+def test_stream_edge_frames_have_their_edge(scpose, name):
+    case = E.edge(name)
+    pil, = E.pil_files(name, case)
+    assert E.restated_files(name, case) == [pil]
+    raw = E.raw_scan(pil)
+    assert E.EDGE_PROPERTIES[E.EDGES[name][3]](raw), (name, len(raw))
+    if E.EDGES[name][3] == "last_ff":
+        assert pil.endswith(b"\xff\x00\xff\xd9")
+
+
+def test_stream_edge_batch_is_the_444_frames(scpose):
+    frames, q, mode = E.edge_batch()
+    assert frames.shape == (4, 40, 48, 3) and (q, mode) == (100, "444")
+    assert sorted(E.EDGE_BATCH) == sorted(n for n, (hw, m, _, _) in E.EDGES.items() if hw == (40, 48) and m == "444")
+    assert [C.pil_bytes(f, q, mode) for f in frames] == [E.pil_files(n, E.edge(n))[0] for n in E.EDGE_BATCH]
+
+
+def test_raw_scan_unstuffs_and_refuses_markers(scpose):
+    head = R.header(8, 8, "gray", 75)
+    assert E.raw_scan(head + b"\x12\xff\x00\xff\x00\x34\xff\xd9") == b"\x12\xff\xff\x34"
+    assert E.raw_scan(head + b"\xff\xd9") == b""
+    with pytest.raises(AssertionError):
+        E.raw_scan(head + b"\x12\xff\xd0\x34\xff\xd9")
+
+
+@pytest.mark.parametrize("mode", C.MODES)
+def test_colour_lattice_states_every_component_value_in_a_dc_value(scpose, mode):
+    case = E.lattice(mode)
+    frame = case[0][0]
+    assert E.restated_files(("lattice", mode), case) == E.pil_files(("lattice", mode), case)
+    colours = E.lattice_colours()
+    assert len(colours) == 1344 and len({tuple(c) for c in colours[:1331].tolist()}) == 1331
+    assert {tuple(c) for c in colours[:1331].tolist()} == {(r, g, b) for r in E.LEVELS for g in E.LEVELS for b in E.LEVELS}
+    assert frame.shape[:2] == ((512, 672) if mode == "420" else (256, 336))
+    blocks, _ = R.scan_blocks(frame, 100, mode)                    # the coefficients of the restatement that equals PIL
+    assert not np.asarray(blocks)[:, 1:].any()
+    want = E.jccolor(colours)                                      # (cells, 3)
+    assert np.array_equal(E.lattice_dc(blocks, mode), 8 * (want[:, :1 if mode == "gray" else 3] - 128))
+    # the rounding constants differ between Y and the chroma components exactly where a product ends in .5
+    assert tuple(want[list(map(tuple, colours)).index((0, 0, 1))]) == (0, 128, 128)
+
+
+@pytest.mark.parametrize("mode", C.MODES)
+def test_size_sweep_restatement_equals_pil(scpose, mode):
+    assert len(E.SWEEP_SIZES) == 100 and len(set(E.SWEEP_SIZES)) == 100
+    for h, w in E.SWEEP_SIZES:
+        case = E.size_case(h, w, mode)
+        assert E.restated_files(("size", h, w, mode), case) == E.pil_files(("size", h, w, mode), case), (h, w, mode)
+
+
+@pytest.mark.parametrize("mode", C.MODES)
+def test_quality_sweep_restatement_equals_pil(scpose, mode):
+    assert E.QUALITY_SWEEP == tuple(range(1, 101))
+    for q in E.QUALITY_SWEEP:
+        case = E.quality_case(q, mode)
+        assert E.restated_files(("quality", q, mode), case) == E.pil_files(("quality", q, mode), case), (q, mode)
+
+
+# ---- overlay
 @pytest.mark.parametrize("case", sorted(O.CASES))
 def test_overlay_restatement_equals_imagedraw(case):
-    bbox, pts = O.CASES[case]
-    assert np.array_equal(O.draw(O.base_frame(), bbox, pts), O.pil_draw(O.base_frame(), bbox, pts))
+    (h, w), (bbox, pts) = O.size_of(case), O.CASES[case]
+    got = O.draw(O.base_frame(h, w), bbox, pts)
+    assert np.array_equal(got, O.pil_draw(O.base_frame(h, w), bbox, O.pil_points(pts)))
+    if case in O.DRAWN:                                            # the case is not vacuous: green and blue pixels both appear
+        changed = (got != O.base_frame(h, w)).any(axis=2)
+        assert (got[changed] == O.GREEN).all(axis=1).any() and (got[changed] == O.BLUE).all(axis=1).any()
+
+
+def test_overlay_cases_keep_the_twelve_and_add_two_frames_and_the_guards():
+    small = [c for c in O.CASES if O.size_of(c) == (48, 64)]
+    assert len(small) == 13 and "guards" in small
+    for size in ((96, 40), (300, 520)):
+        names = [c for c in O.CASES if O.size_of(c) == size]
+        assert len(names) >= 2 and all(len(O.CASES[c][1]) * 121 > 256 * 7 for c in names)
+    # the guard points change nothing: the frame equals the one with the ordinary point alone
+    (h, w), (bbox, pts) = O.size_of("guards"), O.CASES["guards"]
+    assert len(pts) == 7
+    assert np.array_equal(O.draw(O.base_frame(h, w), bbox, pts), O.draw(O.base_frame(h, w), bbox, pts[-1:]))
+    assert not np.array_equal(O.draw(O.base_frame(h, w), bbox, pts), O.draw(O.base_frame(h, w), bbox, []))
+    assert len(O.pil_points(pts)) == 5
