@@ -1,9 +1,19 @@
 // extern "C" surface (include/scpose.h) over the kernels: decode, PnP, single-layer entry points.
 // The HRNet entry points live next to the plan in hrnet.cpp.
-#include "common.h"
+#include "jpeg_common.h"
 #include <new>
 
 using namespace scpose;
+
+static bool aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+
+// The caller's workspace: there, at least `need` bytes and, where the entry point asks for one, on an `align`-byte boundary.
+static int32_t workspace_ok(const char* who, const void* workspace, size_t workspace_bytes, size_t need, int align = 0) {
+  SCP_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace of %zu bytes needed (got %zu)", who, need,
+              workspace ? workspace_bytes : (size_t)0);
+  SCP_REQUIRE(!align || aligned(workspace, align), "%s: workspace must be %d-byte aligned", who, align);
+  return SCPOSE_OK;
+}
 
 struct scpose_conv { PackedConv pc; };
 
@@ -131,9 +141,9 @@ extern "C" int32_t scpose_events_area_bounds(const int32_t* x, const int32_t* y,
   const int64_t fcap = n_events >= 2 ? (n_events - 2) / (area_count - 1) : 0;
   SCP_REQUIRE(capacity >= fcap, "events_area_bounds: capacity=%lld < (n_events - 2) / (area_count - 1) = %lld",
               (long long)capacity, (long long)fcap);
-  const size_t need = events_area_workspace_bytes(n_events, area_count, area_dimension, h, w);
-  SCP_REQUIRE(workspace && workspace_bytes >= need, "events_area_bounds: workspace of %zu bytes needed (got %zu)", need,
-              workspace ? workspace_bytes : (size_t)0);
+  if (int32_t rc = workspace_ok("events_area_bounds", workspace, workspace_bytes,
+                                events_area_workspace_bytes(n_events, area_count, area_dimension, h, w)))
+    return rc;
   SCP_REQUIRE(count_status && (bounds || fcap == 0) && ((x && y) || n_events == 0), "events_area_bounds: null argument");
   return events_area_bounds_launch(x, y, n_events, area_count, area_dimension, h, w, bounds, capacity, count_status,
                                    static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
@@ -160,11 +170,9 @@ extern "C" int32_t scpose_events_csv_parse(const uint8_t* data, int64_t n_bytes,
   SCP_REQUIRE(n_bytes >= 0 && capacity >= 0, "events_csv_parse: n_bytes=%lld capacity=%lld", (long long)n_bytes, (long long)capacity);
   SCP_REQUIRE(t_divisor >= 0.0 && t_divisor <= 1e300, "events_csv_parse: t_divisor=%g (0: none, else a positive divisor)", t_divisor);
   SCP_REQUIRE(count_status && (data || n_bytes == 0) && ((t && x && y && p) || capacity == 0), "events_csv_parse: null argument");
-  SCP_REQUIRE((reinterpret_cast<uintptr_t>(data) & 15) == 0, "events_csv_parse: data must be 16-byte aligned");
-  SCP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "events_csv_parse: workspace must be 16-byte aligned");
-  const size_t need = events_csv_workspace_bytes(n_bytes);
-  SCP_REQUIRE(workspace && workspace_bytes >= need, "events_csv_parse: workspace of %zu bytes needed (got %zu)", need,
-              workspace ? workspace_bytes : (size_t)0);
+  SCP_REQUIRE(aligned(data, 16), "events_csv_parse: data must be 16-byte aligned");
+  SCP_REQUIRE(aligned(workspace, 16), "events_csv_parse: workspace must be 16-byte aligned");      // reported before its size here
+  if (int32_t rc = workspace_ok("events_csv_parse", workspace, workspace_bytes, events_csv_workspace_bytes(n_bytes))) return rc;
   return events_csv_parse_launch(data, n_bytes, delim_whitespace != 0, swap_xy != 0, t_divisor, t, x, y, p, capacity, count_status,
                                  static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
 }
@@ -175,11 +183,7 @@ static int32_t text_args_ok(const char* who, const void* t, const void* x, const
                             const int64_t* count_status, const void* workspace, size_t workspace_bytes) {
   SCP_REQUIRE(n >= 0 && n <= kMaxWriteEvents, "%s: n=%lld (0 .. 2^38)", who, (long long)n);
   SCP_REQUIRE(count_status && ((t && x && y && p) || n == 0), "%s: null argument", who);
-  const size_t need = events_text_workspace_bytes(n);
-  SCP_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace of %zu bytes needed (got %zu)", who, need,
-              workspace ? workspace_bytes : (size_t)0);
-  SCP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: workspace must be 16-byte aligned", who);
-  return SCPOSE_OK;
+  return workspace_ok(who, workspace, workspace_bytes, events_text_workspace_bytes(n), 16);
 }
 
 extern "C" int32_t scpose_events_text_tiling(int32_t* tile_rows, int32_t* scan_rows) {
@@ -211,7 +215,7 @@ extern "C" int32_t scpose_events_text_emit(const int64_t* t, const int32_t* x, c
   const int32_t rc = text_args_ok("events_text_emit", t, x, y, p, n, count_status, workspace, workspace_bytes);
   if (rc != SCPOSE_OK) return rc;
   SCP_REQUIRE(out || capacity == 0, "events_text_emit: null argument");
-  SCP_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0, "events_text_emit: out must be 16-byte aligned");
+  SCP_REQUIRE(aligned(out, 16), "events_text_emit: out must be 16-byte aligned");
   return events_text_emit_launch(t, x, y, p, n, sep, swap_xy != 0, out, capacity, count_status, static_cast<uint8_t*>(workspace),
                                  static_cast<hipStream_t>(stream));
 }
@@ -223,7 +227,7 @@ extern "C" int32_t scpose_events_aedat2_pack(const int64_t* t, const int32_t* x,
               "W 1 .. 1280", h, w);
   SCP_REQUIRE(n >= 0 && n <= kMaxWriteEvents, "events_aedat2_pack: n=%lld (0 .. 2^38)", (long long)n);
   SCP_REQUIRE(count_status && ((t && x && y && p && out) || n == 0), "events_aedat2_pack: null argument");
-  SCP_REQUIRE((reinterpret_cast<uintptr_t>(out) & 7) == 0, "events_aedat2_pack: out must be 8-byte aligned");
+  SCP_REQUIRE(aligned(out, 8), "events_aedat2_pack: out must be 8-byte aligned");
   return events_aedat2_pack_launch(t, x, y, p, n, h, w, out, count_status, static_cast<hipStream_t>(stream));
 }
 
@@ -255,22 +259,30 @@ extern "C" int32_t scpose_events_aedat2_unpack(const uint8_t* records, int64_t n
               t_divisor);
   SCP_REQUIRE(count_status && (n_records == 0 || (records && ((t && x && y && p) || capacity == 0))),
               "events_aedat2_unpack: null argument");
-  SCP_REQUIRE((reinterpret_cast<uintptr_t>(records) & 7) == 0, "events_aedat2_unpack: records must be 8-byte aligned");
-  const size_t need = events_aedat2_unpack_workspace_bytes(n_records);
-  SCP_REQUIRE(workspace && workspace_bytes >= need, "events_aedat2_unpack: workspace of %zu bytes needed (got %zu)", need,
-              workspace ? workspace_bytes : (size_t)0);
-  SCP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "events_aedat2_unpack: workspace must be 16-byte aligned");
+  SCP_REQUIRE(aligned(records, 8), "events_aedat2_unpack: records must be 8-byte aligned");
+  if (int32_t rc = workspace_ok("events_aedat2_unpack", workspace, workspace_bytes, events_aedat2_unpack_workspace_bytes(n_records), 16))
+    return rc;
   return events_aedat2_unpack_launch(records, n_records, h, w, layout, flip_x != 0, flip_y != 0, unwrap != 0, t_divisor, t, x, y, p,
                                      capacity, count_status, static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
 }
 
-static int32_t jpeg_check_shape(int32_t n, int32_t h, int32_t w, int32_t mode, int32_t max_subs, const char* who) {
-  SCP_REQUIRE(mode == SCPOSE_JPEG_GRAY || mode == SCPOSE_JPEG_444 || mode == SCPOSE_JPEG_420,
-              "%s: mode=%d: the modes are 0 (gray), 1 (4:4:4) and 2 (4:2:0)", who, mode);
+// what the decoder, the encoder and the overlay draw ask of a batch of frames
+static int32_t frames_ok(const char* who, int32_t n, int32_t h, int32_t w) {
   SCP_REQUIRE(n >= 1 && n <= 65535, "%s: n=%d (1 .. 65535)", who, n);
   SCP_REQUIRE(h >= 1 && h <= 65535 && w >= 1 && w <= 65535, "%s: frame %dx%d (HxW), each 1 .. 65535", who, h, w);
+  return SCPOSE_OK;
+}
+
+static int32_t jpeg_frame_ok(const char* who, int32_t n, int32_t h, int32_t w, int32_t mode) {
+  SCP_REQUIRE(mode == SCPOSE_JPEG_GRAY || mode == SCPOSE_JPEG_444 || mode == SCPOSE_JPEG_420,
+              "%s: mode=%d: the modes are 0 (gray), 1 (4:4:4) and 2 (4:2:0)", who, mode);
+  return frames_ok(who, n, h, w);
+}
+
+static int32_t jpeg_check_shape(int32_t n, int32_t h, int32_t w, int32_t mode, int32_t max_subs, const char* who) {
+  if (int32_t rc = jpeg_frame_ok(who, n, h, w, mode)) return rc;
   SCP_REQUIRE(max_subs >= 1 && max_subs <= (1 << 24), "%s: max_subs=%d (1 .. 2^24)", who, max_subs);
-  SCP_REQUIRE((int64_t)n * jpeg_decode_blocks(h, w, mode) < ((int64_t)1 << 31) && (int64_t)n * max_subs < ((int64_t)1 << 31),
+  SCP_REQUIRE((int64_t)n * jpeg_blocks(h, w, mode) < ((int64_t)1 << 31) && (int64_t)n * max_subs < ((int64_t)1 << 31),
               "%s: n * blocks and n * max_subs must stay below 2^31: decode the batch in parts", who);
   return SCPOSE_OK;
 }
@@ -291,24 +303,17 @@ extern "C" int32_t scpose_jpeg_decode(const uint8_t* desc, const int32_t* segs, 
   SCP_REQUIRE(n_seg_rows >= 2 * (int64_t)n && n_seg_rows < ((int64_t)1 << 31) && n_bytes >= 0, "jpeg_decode: n_seg_rows=%lld n_bytes=%lld",
               (long long)n_seg_rows, (long long)n_bytes);
   SCP_REQUIRE(desc && segs && (data || n_bytes == 0) && out && status, "jpeg_decode: null argument");
-  SCP_REQUIRE((reinterpret_cast<uintptr_t>(desc) & 7) == 0 && (reinterpret_cast<uintptr_t>(segs) & 3) == 0 &&
-                  (reinterpret_cast<uintptr_t>(out) & 3) == 0 && (reinterpret_cast<uintptr_t>(y_out) & 3) == 0 &&
-                  (reinterpret_cast<uintptr_t>(status) & 3) == 0,
+  SCP_REQUIRE(aligned(desc, 8) && aligned(segs, 4) && aligned(out, 4) && aligned(y_out, 4) && aligned(status, 4),
               "jpeg_decode: desc must be 8-byte aligned, segs, out, y_out and status 4-byte aligned");
-  const size_t need = jpeg_decode_workspace_bytes(n, h, w, mode, max_subs);
-  SCP_REQUIRE(workspace && workspace_bytes >= need, "jpeg_decode: workspace of %zu bytes needed (got %zu)", need,
-              workspace ? workspace_bytes : (size_t)0);
-  SCP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "jpeg_decode: workspace must be 256-byte aligned");
+  if (int32_t rc = workspace_ok("jpeg_decode", workspace, workspace_bytes, jpeg_decode_workspace_bytes(n, h, w, mode, max_subs), 256))
+    return rc;
   return jpeg_decode_launch(desc, segs, n_seg_rows, data, n_bytes, n, h, w, mode, max_subs, bgr != 0, max_rounds, out, y_out, status,
                             static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
 }
 
 static int32_t jpeg_encode_check_shape(int32_t n, int32_t h, int32_t w, int32_t mode, const char* who) {
-  SCP_REQUIRE(mode == SCPOSE_JPEG_GRAY || mode == SCPOSE_JPEG_444 || mode == SCPOSE_JPEG_420,
-              "%s: mode=%d: the modes are 0 (gray), 1 (4:4:4) and 2 (4:2:0)", who, mode);
-  SCP_REQUIRE(n >= 1 && n <= 65535, "%s: n=%d (1 .. 65535)", who, n);
-  SCP_REQUIRE(h >= 1 && h <= 65535 && w >= 1 && w <= 65535, "%s: frame %dx%d (HxW), each 1 .. 65535", who, h, w);
-  SCP_REQUIRE(jpeg_encode_blocks(h, w, mode) * 2800 < ((int64_t)1 << 31),
+  if (int32_t rc = jpeg_frame_ok(who, n, h, w, mode)) return rc;
+  SCP_REQUIRE(jpeg_blocks(h, w, mode) * 2800 < ((int64_t)1 << 31),
               "%s: frame %dx%d (HxW): the bits of one image must stay below 2^31 (blocks * 2800)", who, h, w);
   return SCPOSE_OK;
 }
@@ -336,24 +341,19 @@ extern "C" int32_t scpose_jpeg_encode(const uint8_t* frames, int32_t n, int32_t 
   SCP_REQUIRE(header_bytes >= 1 && header_bytes <= 65535, "jpeg_encode: header_bytes=%d (1 .. 65535)", header_bytes);
   SCP_REQUIRE(capacity >= 0, "jpeg_encode: capacity=%lld", (long long)capacity);
   SCP_REQUIRE(frames && huff && header && (out || capacity == 0) && offsets && status, "jpeg_encode: null argument");
-  SCP_REQUIRE((reinterpret_cast<uintptr_t>(huff) & 3) == 0 && (reinterpret_cast<uintptr_t>(offsets) & 7) == 0 &&
-                  (reinterpret_cast<uintptr_t>(status) & 3) == 0,
+  SCP_REQUIRE(aligned(huff, 4) && aligned(offsets, 8) && aligned(status, 4),
               "jpeg_encode: huff and status must be 4-byte aligned, offsets 8-byte aligned");
-  const size_t need = jpeg_encode_workspace_bytes(n, h, w, mode);
-  SCP_REQUIRE(workspace && workspace_bytes >= need, "jpeg_encode: workspace of %zu bytes needed (got %zu)", need,
-              workspace ? workspace_bytes : (size_t)0);
-  SCP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "jpeg_encode: workspace must be 256-byte aligned");
+  if (int32_t rc = workspace_ok("jpeg_encode", workspace, workspace_bytes, jpeg_encode_workspace_bytes(n, h, w, mode), 256)) return rc;
   return jpeg_encode_launch(frames, n, h, w, mode, quality, huff, header, header_bytes, out, capacity, offsets, status,
                             static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
 }
 
 extern "C" int32_t scpose_overlay_draw(uint8_t* frames, int32_t n, int32_t h, int32_t w, const int32_t* bboxes, const double* points,
                                        int32_t j, void* stream) {
-  SCP_REQUIRE(n >= 1 && n <= 65535, "overlay_draw: n=%d (1 .. 65535)", n);
-  SCP_REQUIRE(h >= 1 && h <= 65535 && w >= 1 && w <= 65535, "overlay_draw: frame %dx%d (HxW), each 1 .. 65535", h, w);
+  if (int32_t rc = frames_ok("overlay_draw", n, h, w)) return rc;
   SCP_REQUIRE(j >= 0 && j <= 65535, "overlay_draw: j=%d (0 .. 65535)", j);
   SCP_REQUIRE(frames && bboxes && (points || j == 0), "overlay_draw: null argument");
-  SCP_REQUIRE((reinterpret_cast<uintptr_t>(bboxes) & 3) == 0 && (reinterpret_cast<uintptr_t>(points) & 7) == 0,
+  SCP_REQUIRE(aligned(bboxes, 4) && aligned(points, 8),
               "overlay_draw: bboxes must be 4-byte aligned, points 8-byte aligned");
   return overlay_draw_launch(frames, n, h, w, bboxes, points, j, static_cast<hipStream_t>(stream));
 }
@@ -394,7 +394,7 @@ extern "C" int32_t scpose_dvs_init(void* state, const uint8_t* frame0, double t0
   const int32_t rc = dvs_check_params(params, "dvs_init");
   if (rc != SCPOSE_OK) return rc;
   SCP_REQUIRE(state && frame0, "dvs_init: null argument");
-  SCP_REQUIRE((reinterpret_cast<uintptr_t>(state) & 255) == 0, "dvs_init: state must be 256-byte aligned");
+  SCP_REQUIRE(aligned(state, 256), "dvs_init: state must be 256-byte aligned");
   SCP_REQUIRE(t0 == t0 && t0 >= -1e300 && t0 <= 1e300, "dvs_init: t0=%g", t0);
   return dvs_init_launch(state, frame0, t0, params->h, params->w, params->lin_log_table, params->refractory_period_s,
                          static_cast<hipStream_t>(stream));
@@ -408,11 +408,10 @@ extern "C" int32_t scpose_dvs_emulate(void* state, const uint8_t* frames, const 
   SCP_REQUIRE(n_frames >= 0 && capacity >= 0, "dvs_emulate: n_frames=%d capacity=%lld", n_frames, (long long)capacity);
   SCP_REQUIRE(state && count_status && ((frames && t) || n_frames == 0) && ((t_s && t_us && x && y && p) || capacity == 0),
               "dvs_emulate: null argument");
-  SCP_REQUIRE((reinterpret_cast<uintptr_t>(state) & 255) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
-              "dvs_emulate: state and workspace must be 256-byte aligned");
-  const size_t need = dvs_workspace_bytes(params->h, params->w, n_frames, params->max_iters);
-  SCP_REQUIRE(workspace && workspace_bytes >= need, "dvs_emulate: workspace of %zu bytes needed (got %zu)", need,
-              workspace ? workspace_bytes : (size_t)0);
+  SCP_REQUIRE(aligned(state, 256) && aligned(workspace, 256), "dvs_emulate: state and workspace must be 256-byte aligned");
+  if (int32_t rc = workspace_ok("dvs_emulate", workspace, workspace_bytes,
+                                dvs_workspace_bytes(params->h, params->w, n_frames, params->max_iters)))
+    return rc;
   return dvs_emulate_launch(state, frames, t, n_frames, *params, t_s, t_us, x, y, p, capacity, count_status,
                             static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
 }

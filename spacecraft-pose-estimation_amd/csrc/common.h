@@ -279,15 +279,13 @@ size_t events_aedat2_unpack_workspace_bytes(int64_t n);
 int32_t events_aedat2_unpack_launch(const uint8_t* records, int64_t n, int h, int w, int layout, int flip_x, int flip_y, int unwrap,
                                     double t_div, int64_t* t, int32_t* x, int32_t* y, int8_t* p, int64_t capacity, int64_t* count_status,
                                     uint8_t* ws, hipStream_t stream);
-// jpeg_decode.hip: baseline JPEG files -> (N, H, W, 3) uint8 frames
+// jpeg_decode.hip: baseline JPEG files -> (N, H, W, 3) uint8 frames (jpeg_common.h: jpeg_blocks(h, w, mode), the blocks of one frame)
 size_t jpeg_decode_workspace_bytes(int n, int h, int w, int mode, int max_subs);
-int64_t jpeg_decode_blocks(int h, int w, int mode);
 int32_t jpeg_decode_launch(const uint8_t* desc, const int32_t* segs, int64_t n_rows, const uint8_t* data, int64_t n_bytes, int n, int h,
                            int w, int mode, int max_subs, int bgr, int max_rounds, uint8_t* out, uint8_t* y_out, int32_t* status,
                            uint8_t* ws, hipStream_t stream);
 
 // jpeg_encode.hip: (N, H, W, 3) uint8 frames -> baseline JPEG byte streams; the overlay draw in front of it
-int64_t jpeg_encode_blocks(int h, int w, int mode);
 size_t jpeg_encode_workspace_bytes(int n, int h, int w, int mode);
 int64_t jpeg_encode_capacity_bytes(int n, int h, int w, int mode, int header_bytes);
 int32_t jpeg_encode_launch(const uint8_t* frames, int n, int h, int w, int mode, int quality, const uint32_t* huff, const uint8_t* header,

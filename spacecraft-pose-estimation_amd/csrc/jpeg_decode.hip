@@ -26,7 +26,7 @@
 // the subsequence (plus one code word) or the segment, zeros are fed past the end of the data, and nothing but the thread's own
 // slot and count is written.  No code word starts in the encoder's fill bits (the last min(7, trailing ones) bits of a segment):
 // no Huffman code is all ones.  No floating point, no atomics but integer ORs into status; two runs are bitwise equal.
-#include "common.h"
+#include "jpeg_common.h"
 #include "scan_device.h"
 
 namespace scpose {
@@ -41,25 +41,16 @@ constexpr int kQuantOff = 64, kTablesOff = 448, kSlot = 1424, kSlots = 6;
 constexpr int kTableWords = kSlots * kSlot / 4;
 static_assert(kTablesOff + kSlots * kSlot <= kDesc, "the tables fit the descriptor");
 
-__constant__ uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                    41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                    30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
 struct Geo {
   int32_t n, h, w, mode, bpm, ycount, hs, mcus_x, mcus_y, n_mcus, n_blocks, max_subs, pw, ph, pcw, pch;
   int64_t n_bytes, n_rows;
 };
 
 Geo make_geo(int n, int h, int w, int mode, int max_subs, int64_t n_bytes, int64_t n_rows) {
+  const JpegFrame f = jpeg_frame(h, w, mode);
   Geo g{};
   g.n = n; g.h = h; g.w = w; g.mode = mode; g.max_subs = max_subs; g.n_bytes = n_bytes; g.n_rows = n_rows;
-  g.hs = mode == SCPOSE_JPEG_420 ? 2 : 1;
-  g.ycount = g.hs * g.hs;
-  g.bpm = mode == SCPOSE_JPEG_GRAY ? 1 : g.ycount + 2;
-  g.mcus_x = (w + 8 * g.hs - 1) / (8 * g.hs);
-  g.mcus_y = (h + 8 * g.hs - 1) / (8 * g.hs);
-  g.n_mcus = g.mcus_x * g.mcus_y;
-  g.n_blocks = g.n_mcus * g.bpm;
+  g.hs = f.hs; g.ycount = f.ycount; g.bpm = f.bpm; g.mcus_x = f.mcus_x; g.mcus_y = f.mcus_y; g.n_mcus = f.n_mcus; g.n_blocks = f.n_blocks;
   g.pw = g.mcus_x * 8 * g.hs; g.ph = g.mcus_y * 8 * g.hs;
   g.pcw = g.mcus_x * 8; g.pch = g.mcus_y * 8;
   return g;
@@ -168,8 +159,7 @@ __device__ __forceinline__ uint32_t walk(const Sub& s, uint32_t entry, const Geo
     r.refill();
     if (r.at() >= r.limit) break;
     const uint32_t w = (uint32_t)(r.acc >> 32);
-    const int comp = blk < geo.ycount ? 0 : blk - geo.ycount + 1;
-    const int slot = comp * 2 + (k != 0);
+    const int slot = SCP_MCU_COMP_INDEX(blk, geo.ycount) * 2 + (k != 0);
     const uint32_t e = tab16[slot * (kSlot / 2) + (w >> 23)];
     int len = (int)(e >> 8), sym = (int)(e & 255u);
     if (len == 0) {                                    // longer than 9 bits: libjpeg's maxcode / valoffset
@@ -326,14 +316,14 @@ __global__ __launch_bounds__(kThreads) void jpeg_write_kernel(const uint8_t* __r
 // one workgroup per (component, image): dc[] of the component's blocks, in scan order, <- inclusive sums
 __global__ __launch_bounds__(kThreads) void jpeg_dc_kernel(Geo geo, int32_t* dc) {
   __shared__ int32_t sc[kThreads];
-  const int comp = blockIdx.x, img = blockIdx.y;
-  const int cb = comp == 0 ? geo.ycount : 1, first = comp == 0 ? 0 : geo.ycount + comp - 1;
-  const int32_t total = geo.n_mcus * cb;
+  const int img = blockIdx.y;
+  const McuComp mc = mcu_comp(blockIdx.x, geo.ycount);
+  const int32_t total = geo.n_mcus * mc.count;
   int32_t* d = dc + (size_t)img * geo.n_blocks;
   int32_t carry = 0;
   for (int32_t j0 = 0; j0 < total; j0 += kThreads) {
     const int32_t j = j0 + threadIdx.x;
-    const int32_t b = j < total ? (j / cb) * geo.bpm + first + j % cb : 0;
+    const int32_t b = j < total ? (j / mc.count) * geo.bpm + mc.first + j % mc.count : 0;
     const int32_t v = j < total ? d[b] : 0;
     const int32_t inc = block_inclusive_scan<0>(v, sc);
     sc[threadIdx.x] = inc;
@@ -345,10 +335,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_dc_kernel(Geo geo, int32_t* dc)
   }
 }
 
-// jidctint.c, CONST_BITS 13, PASS1_BITS 2
-constexpr int32_t F0298 = 2446, F0390 = 3196, F0541 = 4433, F0765 = 6270, F0899 = 7373, F1175 = 9633, F1501 = 12299, F1847 = 15137,
-                  F1961 = 16069, F2053 = 16819, F2562 = 20995, F3072 = 25172;
-
+// jidctint.c's jpeg_idct_islow (the constants: jpeg_common.h)
 template <int SHIFT>
 __device__ __forceinline__ void idct_1d(const int32_t (&in)[8], int32_t (&out)[8]) {
   int32_t z2 = in[2], z3 = in[6];
@@ -394,14 +381,14 @@ __global__ __launch_bounds__(kThreads) void jpeg_idct_kernel(const uint8_t* __re
   const int32_t b = blockIdx.x * kThreads + threadIdx.x;
   if (b >= geo.n_blocks) return;
   const int32_t mcu = b / geo.bpm, blk = b - mcu * geo.bpm;
-  const int comp = blk < geo.ycount ? 0 : blk - geo.ycount + 1;
-  const int cb = comp == 0 ? geo.ycount : 1, first = comp == 0 ? 0 : geo.ycount + comp - 1;
+  const McuComp mc = mcu_comp_of_block(blk, geo.ycount);
+  const int comp = mc.comp;
   const int32_t* d = dc + (size_t)img * geo.n_blocks;
   // the DC value: inclusive sum up to this block minus the sum up to the block before its restart segment
   const int32_t ri = head[5] >= 1 ? head[5] : 1;
   const int32_t seg_mcu = (mcu / ri) * ri;
   int32_t dcv = d[b];
-  if (seg_mcu > 0) dcv -= d[(seg_mcu - 1) * geo.bpm + first + cb - 1];
+  if (seg_mcu > 0) dcv -= d[(seg_mcu - 1) * geo.bpm + mc.first + mc.count - 1];
   const uint4* src = reinterpret_cast<const uint4*>(coef + ((size_t)img * geo.n_blocks + b) * 64);
   int32_t ws[8][8];                                    // [row][column]
 #pragma unroll
@@ -546,8 +533,6 @@ Plan make_plan(const Geo& g, uint8_t* ws) {
 size_t jpeg_decode_workspace_bytes(int n, int h, int w, int mode, int max_subs) {
   return make_plan(make_geo(n, h, w, mode, max_subs, 0, 0), nullptr).bytes;
 }
-
-int64_t jpeg_decode_blocks(int h, int w, int mode) { return make_geo(1, h, w, mode, 1, 0, 0).n_blocks; }
 
 int32_t jpeg_decode_launch(const uint8_t* desc, const int32_t* segs, int64_t n_rows, const uint8_t* data, int64_t n_bytes, int n, int h,
                            int w, int mode, int max_subs, int bgr, int max_rounds, uint8_t* out, uint8_t* y_out, int32_t* status,

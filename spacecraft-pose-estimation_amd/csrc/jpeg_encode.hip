@@ -25,7 +25,7 @@
 // Stuffing at most doubles it: header + 432 x blocks + 2 (EOI) bytes per image always suffice.  The streams are packed; an
 // image whose end lies past the caller's capacity gets SCPOSE_JPEG_ENC_CAPACITY and not one of its bytes is written.
 // No floating point; integer atomics only.
-#include "common.h"
+#include "jpeg_common.h"
 #include "scan_device.h"
 
 #include <utility>
@@ -47,14 +47,10 @@ struct EncGeo {
 };
 
 EncGeo make_geo(int n, int h, int w, int mode, int header_bytes) {
+  const JpegFrame f = jpeg_frame(h, w, mode);
   EncGeo g{};
   g.n = n; g.h = h; g.w = w; g.mode = mode; g.header_bytes = header_bytes;
-  g.hs = mode == SCPOSE_JPEG_420 ? 2 : 1;
-  g.ycount = g.hs * g.hs;
-  g.bpm = mode == SCPOSE_JPEG_GRAY ? 1 : g.ycount + 2;
-  g.mcus_x = (w + 8 * g.hs - 1) / (8 * g.hs);
-  g.mcus_y = (h + 8 * g.hs - 1) / (8 * g.hs);
-  g.n_blocks = g.mcus_x * g.mcus_y * g.bpm;
+  g.hs = f.hs; g.ycount = f.ycount; g.bpm = f.bpm; g.mcus_x = f.mcus_x; g.mcus_y = f.mcus_y; g.n_blocks = f.n_blocks;
   g.ybc = (w + 7) / 8; g.ybr = (h + 7) / 8;
   g.scan_tiles = (g.n_blocks + kScanTile - 1) / kScanTile;
   const int64_t words = (int64_t)g.n_blocks * kBlockWords + 1;
@@ -70,17 +66,10 @@ __constant__ uint8_t kBaseQuant[2][64] = {
     {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
      99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
 
-// natural index of the k-th coefficient in zig-zag order; used in constant expressions only
-__host__ __device__ constexpr int zig(int k) {
-  constexpr int t[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20,
-                         13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45,
-                         38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-  return t[k];
-}
-
+// the K-th coefficient in zig-zag order: its place is a constant expression
 template <int K>
 __device__ __forceinline__ int32_t zig_of(const int32_t (&ws)[8][8]) {
-  constexpr int i = zig(K);
+  constexpr int i = kZigzag[K];
   return ws[i >> 3][i & 7];
 }
 
@@ -90,10 +79,7 @@ __device__ __forceinline__ void pack_zigzag(const int32_t (&ws)[8][8], bool dumm
   ((packed[I] = ((uint32_t)((dummy && I != 0) ? 0 : zig_of<2 * I>(ws)) & 0xffffu) | ((uint32_t)(dummy ? 0 : zig_of<2 * I + 1>(ws)) << 16)), ...);
 }
 
-// jfdctint.c, CONST_BITS 13, PASS1_BITS 2
-constexpr int32_t F0298 = 2446, F0390 = 3196, F0541 = 4433, F0765 = 6270, F0899 = 7373, F1175 = 9633, F1501 = 12299, F1847 = 15137,
-                  F1961 = 16069, F2053 = 16819, F2562 = 20995, F3072 = 25172;
-
+// jfdctint.c's jpeg_fdct_islow (the constants: jpeg_common.h)
 template <bool FIRST>
 __device__ __forceinline__ void fdct_1d(const int32_t (&d)[8], int32_t (&out)[8]) {
   constexpr int N = FIRST ? 13 - 2 : 13 + 2;
@@ -146,7 +132,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_enc_dct_kernel(const uint8_t* _
   const int32_t b = blockIdx.x * kThreads + threadIdx.x;
   if (b >= geo.n_blocks) return;
   const int32_t mcu = b / geo.bpm, blk = b - mcu * geo.bpm;
-  const int comp = blk < geo.ycount ? 0 : blk - geo.ycount + 1;
+  const int comp = mcu_comp_index(blk, geo.ycount);
   const int32_t mx = mcu % geo.mcus_x, my = mcu / geo.mcus_x;
   int32_t bx = mx, by = my;                            // block coordinates in the component's plane
   bool dummy = false;
@@ -241,7 +227,8 @@ template <bool EMIT>
 __device__ __forceinline__ int32_t code_block(const EncGeo& geo, const int16_t* __restrict__ coef_img, int32_t b, const uint32_t* huff,
                                               BitSink& sink) {
   const int32_t mcu = b / geo.bpm, blk = b - mcu * geo.bpm;
-  const bool luma = blk < geo.ycount;
+  const McuComp mc = mcu_comp_of_block(blk, geo.ycount);
+  const bool luma = mc.comp == 0;
   const uint32_t* dc = huff + (luma ? 0 : 512);
   const uint32_t* ac = dc + 256;
   const uint4* src = reinterpret_cast<const uint4*>(coef_img + (size_t)b * 64);
@@ -252,8 +239,8 @@ __device__ __forceinline__ int32_t code_block(const EncGeo& geo, const int16_t* 
     u[4 * i] = v.x; u[4 * i + 1] = v.y; u[4 * i + 2] = v.z; u[4 * i + 3] = v.w;
   }
   int32_t pred = 0;                                    // the DC value of the component's block before this one in the scan
-  if (luma && blk > 0) pred = coef_img[(size_t)(b - 1) * 64];
-  else if (mcu > 0) pred = coef_img[(size_t)(b - geo.bpm + (luma ? geo.ycount - 1 : 0)) * 64];
+  if (blk > mc.first) pred = coef_img[(size_t)(b - 1) * 64];
+  else if (mcu > 0) pred = coef_img[(size_t)(b - geo.bpm + mc.count - 1) * 64];   // the component's last block of the MCU before
   int32_t bits = 0;
   {
     const int32_t diff = (int32_t)(int16_t)(u[0] & 0xffffu) - pred;
@@ -519,12 +506,10 @@ __global__ __launch_bounds__(kThreads) void overlay_disc_kernel(uint8_t* frames,
 
 }  // namespace
 
-int64_t jpeg_encode_blocks(int h, int w, int mode) { return make_geo(1, h, w, mode, 0).n_blocks; }
-
 size_t jpeg_encode_workspace_bytes(int n, int h, int w, int mode) { return make_plan(make_geo(n, h, w, mode, 0), nullptr).bytes; }
 
 int64_t jpeg_encode_capacity_bytes(int n, int h, int w, int mode, int header_bytes) {
-  return (int64_t)n * (header_bytes + 2 * (int64_t)(kBlockBits / 8) * make_geo(1, h, w, mode, 0).n_blocks + 2);
+  return (int64_t)n * (header_bytes + 2 * (int64_t)(kBlockBits / 8) * jpeg_blocks(h, w, mode) + 2);
 }
 
 int32_t jpeg_encode_launch(const uint8_t* frames, int n, int h, int w, int mode, int quality, const uint32_t* huff, const uint8_t* header,

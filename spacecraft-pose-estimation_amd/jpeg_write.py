@@ -8,11 +8,10 @@ import struct
 
 import numpy as np
 
-MODES = {"gray": 0, "444": 1, "420": 2}          # SCPOSE_JPEG_GRAY / _444 / _420
-HUFF_WORDS = 4 * 256                              # the uploaded table: [DC lum, AC lum, DC chroma, AC chroma][symbol]
+from .jpeg_read import MODES, ZIGZAG as _ZIGZAG
 
-ZIGZAG = [0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
-          35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63]
+HUFF_WORDS = 4 * 256                              # the uploaded table: [DC lum, AC lum, DC chroma, AC chroma][symbol]
+ZIGZAG = _ZIGZAG.tolist()                         # a list of ints: header() builds bytes from it
 
 # T.81 annex K.1, natural order
 STD_QUANT = (

@@ -36,6 +36,18 @@ def _need_cuda(*ts):
             raise nat.NativeError("scpose ops need device tensors (got %s); there is no CPU path" % t.device)
 
 
+def _query_bytes(name, *args):
+    """The size query scpose_<name>(*args, &bytes) of the C ABI -> bytes."""
+    b = c_size_t()
+    nat.check(getattr(nat.lib(), "scpose_" + name)(*args, ctypes.byref(b)), name)
+    return b.value
+
+
+def _empty_event_columns(n, dev):
+    """Uninitialised (t int64, x int32, y int32, p int8) columns of n rows on dev."""
+    return tuple(torch.empty(n, dtype=dt, device=dev) for dt in (torch.int64, torch.int32, torch.int32, torch.int8))
+
+
 # ------------------------------------------------------------------ layout
 def to_blocked(x, dtype="bf16"):
     """float32 NCHW (C % 8 == 0) -> blocked [N][C/8][H][W][8] 16-bit tensor."""
@@ -208,53 +220,51 @@ def render_events(t, x, y, p, hw, interval=10000.0, full_scale=2, fold_polarity=
     mode = str(exposure).lower()
     if mode not in ("duration", "count", "area_count"):
         raise ValueError("render_events: exposure must be 'duration', 'count' or 'area_count' (got %r)" % (exposure,))
-    if mode != "duration":
-        return _render_events_counted(t, x, y, p, hw, mode, event_count, area_count, area_dimension, full_scale, fold_polarity,
-                                      K, dist, max_frames, want_distorted, want_times)
-    if p is None and not fold_polarity:
-        raise ValueError("render_events: fold_polarity=False needs the polarity column")
-    _need_cuda(t, x, y, p)
-    n = int(t.numel())
-    if t.dtype != torch.int64 or x.dtype != torch.int32 or y.dtype != torch.int32 or x.numel() != n or y.numel() != n:
-        raise ValueError("render_events: t must be int64, x and y int32, all of one length")
-    if p is not None and (p.dtype not in (torch.int8, torch.int32) or p.numel() != n):
-        raise ValueError("render_events: p must be int8 or int32 of the stream's length")
-    if (K is None) != (dist is None):
-        raise ValueError("render_events: give K and dist together, or neither")
+    n = _check_stream(t, x, y, p, fold_polarity, K, dist)
     t, x, y = t.contiguous(), x.contiguous(), y.contiguous()
     p = p.contiguous() if p is not None else None
     dev = t.device
     h, w = int(hw[0]), int(hw[1])
     lut = er.gray_table(full_scale)
-    if n >= 2:
-        first, before_last, last = t[torch.tensor([0, n - 2, n - 1], device=dev)].tolist()
-        starts, names = er.frame_schedule(first, before_last, last, interval, max_frames)
-    else:
-        starts, names = np.zeros(1), []
-    f = len(names)
     lib = nat.lib()
-    ws = c_size_t()
-    nat.check(lib.scpose_events_workspace_bytes(f, h, w, ctypes.byref(ws)), "events_workspace_bytes")
-    frames = torch.empty((f, h, w, 3), dtype=torch.uint8, device=dev)
-    out = {"flat": frames.view(-1), "offsets": torch.arange(f, dtype=torch.int64) * (h * w * 3),
-           "hw": torch.tensor([[h, w]] * f, dtype=torch.int32).reshape(-1, 2)}
-    distorted = torch.empty((f, h, w, 3), dtype=torch.uint8, device=dev) if want_distorted else None
-    if want_distorted:
-        out["distorted"] = distorted
+    times = None
     with torch.cuda.device(dev):
-        starts_d = torch.from_numpy(starts).to(dev)
-        bounds = torch.empty((f, 2), dtype=torch.int64, device=dev)
+        if mode == "duration":
+            if n >= 2:
+                first, before_last, last = t[torch.tensor([0, n - 2, n - 1], device=dev)].tolist()
+                starts, names = er.frame_schedule(first, before_last, last, interval, max_frames)
+            else:
+                starts, names = np.zeros(1), []
+            f = len(names)
+            starts_d = torch.from_numpy(starts).to(dev)
+            bounds = torch.empty((f, 2), dtype=torch.int64, device=dev)
+            nat.check(lib.scpose_events_frame_bounds(_ptr(t), n, _ptr(starts_d), f, _ptr(bounds), _stream()), "events_frame_bounds")
+            if want_times:
+                step = 1.0 / (1.0 / float(interval))
+                times = np.asarray([starts[k + 1] + step / 2 for k in range(f)], dtype=np.float64)
+        else:
+            bounds = _counted_bounds(x, y, n, h, w, mode, event_count, area_count, area_dimension, max_frames)
+            f = int(bounds.shape[0])
+            mids = torch.empty(f, dtype=torch.float64, device=dev)
+            nat.check(lib.scpose_events_bounds_midpoints(_ptr(t), _ptr(bounds), f, _ptr(mids), _stream()), "events_bounds_midpoints")
+            times = mids.cpu().numpy()
+            names = ["{:.0f}".format(v) for v in times.tolist()]
+        ws = _query_bytes("events_workspace_bytes", f, h, w)
+        frames = torch.empty((f, h, w, 3), dtype=torch.uint8, device=dev)
+        out = {"flat": frames.view(-1), "offsets": torch.arange(f, dtype=torch.int64) * (h * w * 3),
+               "hw": torch.tensor([[h, w]] * f, dtype=torch.int32).reshape(-1, 2)}
+        distorted = torch.empty((f, h, w, 3), dtype=torch.uint8, device=dev) if want_distorted else None
+        if want_distorted:
+            out["distorted"] = distorted
         lut_d = torch.from_numpy(lut).to(dev)
         k_d = torch.as_tensor(np.asarray(K.cpu() if torch.is_tensor(K) else K, dtype=np.float64).reshape(3, 3)).to(dev) if K is not None else None
         d_d = torch.as_tensor(np.asarray(dist.cpu() if torch.is_tensor(dist) else dist, dtype=np.float64).reshape(5)).to(dev) if dist is not None else None
-        work = torch.empty(ws.value if K is not None else 0, dtype=torch.uint8, device=dev)
-        nat.check(lib.scpose_events_frame_bounds(_ptr(t), n, _ptr(starts_d), f, _ptr(bounds), _stream()), "events_frame_bounds")
+        work = torch.empty(ws if K is not None else 0, dtype=torch.uint8, device=dev)
         nat.check(lib.scpose_events_render(_ptr(x), _ptr(y), _ptr(p), p.element_size() if p is not None else 0, _ptr(bounds), f, h, w,
                                            int(full_scale), int(bool(fold_polarity)), _ptr(lut_d), _ptr(k_d), _ptr(d_d), _ptr(frames),
                                            _ptr(distorted), _ptr(work), work.numel(), _stream()), "events_render")
     if want_times:
-        step = 1.0 / (1.0 / float(interval))
-        out["times"] = np.asarray([starts[k + 1] + step / 2 for k in range(f)], dtype=np.float64)
+        out["times"] = times
     return out, names
 
 
@@ -272,78 +282,46 @@ def _check_stream(t, x, y, p, fold_polarity, K, dist):
     return n
 
 
-def _render_events_counted(t, x, y, p, hw, mode, event_count, area_count, area_dimension, full_scale, fold_polarity, K, dist,
-                           max_frames, want_distorted, want_times):
-    """render_events for exposure = "count" / "area_count": the bounds come from csrc/events_exposure.hip, the frames from the
-    same scpose_events_render as the duration mode."""
-    from . import event_render as er
-    n = _check_stream(t, x, y, p, fold_polarity, K, dist)
-    t, x, y = t.contiguous(), x.contiguous(), y.contiguous()
-    p = p.contiguous() if p is not None else None
-    dev = t.device
-    h, w = int(hw[0]), int(hw[1])
-    lut = er.gray_table(full_scale)
+def _counted_bounds(x, y, n, h, w, mode, event_count, area_count, area_dimension, max_frames):
+    """The (F, 2) frame bounds of render_events' exposure = "count" / "area_count" (csrc/events_exposure.hip), on the current
+    device; max_frames caps F."""
     lib = nat.lib()
-    with torch.cuda.device(dev):
-        if mode == "count":
-            if event_count is None:
-                raise ValueError("render_events: exposure='count' needs event_count")
-            N = int(float(event_count))
-            if N < 1:
-                raise ValueError("render_events: event_count must be >= 1 after truncation (got %r)" % (event_count,))
-            fc = c_int64()
-            nat.check(lib.scpose_events_count_frames(n, N, ctypes.byref(fc)), "events_count_frames")
-            f = fc.value if max_frames is None else min(fc.value, int(max_frames))
-            bounds = torch.empty((f, 2), dtype=torch.int64, device=dev)
-            nat.check(lib.scpose_events_count_bounds(n, N, f, _ptr(bounds), _stream()), "events_count_bounds")
-        else:
-            if area_count is None or area_dimension is None:
-                raise ValueError("render_events: exposure='area_count' needs area_count and area_dimension")
-            M, D = int(area_count), int(area_dimension)
-            if M < 2:
-                raise ValueError("render_events: area_count must be >= 2 (got %d)" % M)
-            if D < 1:
-                raise ValueError("render_events: area_dimension must be >= 1 (got %d)" % D)
-            ws = c_size_t()
-            nat.check(lib.scpose_events_area_bounds_workspace_bytes(n, M, D, h, w, ctypes.byref(ws)), "events_area_bounds_workspace_bytes")
-            cap = (n - 2) // (M - 1) if n >= 2 else 0
-            bounds = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=dev)
-            cs = torch.empty(2, dtype=torch.int64, device=dev)
-            work = torch.empty(ws.value, dtype=torch.uint8, device=dev)
-            nat.check(lib.scpose_events_area_bounds(_ptr(x), _ptr(y), n, M, D, h, w, _ptr(bounds), cap, _ptr(cs), _ptr(work), ws.value,
-                                                    _stream()), "events_area_bounds")
-            f_all, status = cs.tolist()                            # the one small read-back: [F, status]
-            del work
-            if status == 1:
-                raise ValueError("render_events: an event lies off the %d x %d area grid of area_dimension %d (x in [-%d, %d), "
-                                 "y in [-%d, %d))" % (1 + w // D, 1 + h // D, D, (1 + w // D) * D, (1 + w // D) * D,
-                                                      (1 + h // D) * D, (1 + h // D) * D))
-            if status != 0:
-                raise nat.NativeError("render_events: events_area_bounds status %d" % status)
-            f = f_all if max_frames is None else min(f_all, int(max_frames))
-            bounds = bounds[:f]
-        mids = torch.empty(f, dtype=torch.float64, device=dev)
-        nat.check(lib.scpose_events_bounds_midpoints(_ptr(t), _ptr(bounds), f, _ptr(mids), _stream()), "events_bounds_midpoints")
-        times = mids.cpu().numpy()
-        names = ["{:.0f}".format(v) for v in times.tolist()]
-        ws = c_size_t()
-        nat.check(lib.scpose_events_workspace_bytes(f, h, w, ctypes.byref(ws)), "events_workspace_bytes")
-        frames = torch.empty((f, h, w, 3), dtype=torch.uint8, device=dev)
-        out = {"flat": frames.view(-1), "offsets": torch.arange(f, dtype=torch.int64) * (h * w * 3),
-               "hw": torch.tensor([[h, w]] * f, dtype=torch.int32).reshape(-1, 2)}
-        distorted = torch.empty((f, h, w, 3), dtype=torch.uint8, device=dev) if want_distorted else None
-        if want_distorted:
-            out["distorted"] = distorted
-        lut_d = torch.from_numpy(lut).to(dev)
-        k_d = torch.as_tensor(np.asarray(K.cpu() if torch.is_tensor(K) else K, dtype=np.float64).reshape(3, 3)).to(dev) if K is not None else None
-        d_d = torch.as_tensor(np.asarray(dist.cpu() if torch.is_tensor(dist) else dist, dtype=np.float64).reshape(5)).to(dev) if dist is not None else None
-        work = torch.empty(ws.value if K is not None else 0, dtype=torch.uint8, device=dev)
-        nat.check(lib.scpose_events_render(_ptr(x), _ptr(y), _ptr(p), p.element_size() if p is not None else 0, _ptr(bounds), f, h, w,
-                                           int(full_scale), int(bool(fold_polarity)), _ptr(lut_d), _ptr(k_d), _ptr(d_d), _ptr(frames),
-                                           _ptr(distorted), _ptr(work), work.numel(), _stream()), "events_render")
-    if want_times:
-        out["times"] = times
-    return out, names
+    dev = x.device
+    if mode == "count":
+        if event_count is None:
+            raise ValueError("render_events: exposure='count' needs event_count")
+        N = int(float(event_count))
+        if N < 1:
+            raise ValueError("render_events: event_count must be >= 1 after truncation (got %r)" % (event_count,))
+        fc = c_int64()
+        nat.check(lib.scpose_events_count_frames(n, N, ctypes.byref(fc)), "events_count_frames")
+        f = fc.value if max_frames is None else min(fc.value, int(max_frames))
+        bounds = torch.empty((f, 2), dtype=torch.int64, device=dev)
+        nat.check(lib.scpose_events_count_bounds(n, N, f, _ptr(bounds), _stream()), "events_count_bounds")
+        return bounds
+    if area_count is None or area_dimension is None:
+        raise ValueError("render_events: exposure='area_count' needs area_count and area_dimension")
+    M, D = int(area_count), int(area_dimension)
+    if M < 2:
+        raise ValueError("render_events: area_count must be >= 2 (got %d)" % M)
+    if D < 1:
+        raise ValueError("render_events: area_dimension must be >= 1 (got %d)" % D)
+    ws = _query_bytes("events_area_bounds_workspace_bytes", n, M, D, h, w)
+    cap = (n - 2) // (M - 1) if n >= 2 else 0
+    bounds = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=dev)
+    cs = torch.empty(2, dtype=torch.int64, device=dev)
+    work = torch.empty(ws, dtype=torch.uint8, device=dev)
+    nat.check(lib.scpose_events_area_bounds(_ptr(x), _ptr(y), n, M, D, h, w, _ptr(bounds), cap, _ptr(cs), _ptr(work), ws, _stream()),
+              "events_area_bounds")
+    f_all, status = cs.tolist()                            # the one small read-back: [F, status]
+    del work
+    if status == 1:
+        raise ValueError("render_events: an event lies off the %d x %d area grid of area_dimension %d (x in [-%d, %d), "
+                         "y in [-%d, %d))" % (1 + w // D, 1 + h // D, D, (1 + w // D) * D, (1 + w // D) * D,
+                                              (1 + h // D) * D, (1 + h // D) * D))
+    if status != 0:
+        raise nat.NativeError("render_events: events_area_bounds status %d" % status)
+    return bounds[:f_all if max_frames is None else min(f_all, int(max_frames))]
 
 
 class UnsupportedCsv(ValueError):
@@ -379,17 +357,13 @@ def parse_events_csv(data, delim_whitespace=False, swap_xy=False, microseconds_t
     div = 1000000.0 if microseconds_timestamp else (1000.0 if milliseconds_timestamp else 0.0)
     cap = (n + 1) // 8                                          # the shortest row, '1,2,3,4' and a line end, takes 8 bytes
     lib = nat.lib()
-    ws = c_size_t()
-    nat.check(lib.scpose_events_csv_workspace_bytes(n, ctypes.byref(ws)), "events_csv_workspace_bytes")
+    ws = _query_bytes("events_csv_workspace_bytes", n)
     with torch.cuda.device(dev):
-        t = torch.empty(cap, dtype=torch.int64, device=dev)
-        x = torch.empty(cap, dtype=torch.int32, device=dev)
-        y = torch.empty(cap, dtype=torch.int32, device=dev)
-        p = torch.empty(cap, dtype=torch.int8, device=dev)
+        t, x, y, p = _empty_event_columns(cap, dev)
         cs = torch.empty(2, dtype=torch.int64, device=dev)
-        work = torch.empty(ws.value, dtype=torch.uint8, device=dev)
+        work = torch.empty(ws, dtype=torch.uint8, device=dev)
         nat.check(lib.scpose_events_csv_parse(_ptr(buf), n, int(bool(delim_whitespace)), int(bool(swap_xy)), c_double(div), _ptr(t),
-                                              _ptr(x), _ptr(y), _ptr(p), cap, _ptr(cs), _ptr(work), ws.value, _stream()),
+                                              _ptr(x), _ptr(y), _ptr(p), cap, _ptr(cs), _ptr(work), ws, _stream()),
                   "events_csv_parse")
         rows, status = cs.tolist()                              # the one small read-back
         if status == nat.CSV_UNSUPPORTED:
@@ -436,18 +410,17 @@ def format_events_text(t, x, y, p, sep=" ", swap_xy=False):
     sb = _sep_byte(sep)
     t, x, y, p, dev, n = _event_columns("format_events_text", t, x, y, p)
     lib = nat.lib()
-    ws = c_size_t()
-    nat.check(lib.scpose_events_text_workspace_bytes(n, ctypes.byref(ws)), "events_text_workspace_bytes")
+    ws = _query_bytes("events_text_workspace_bytes", n)
     with torch.cuda.device(dev):
-        work = torch.empty(ws.value, dtype=torch.uint8, device=dev)
+        work = torch.empty(ws, dtype=torch.uint8, device=dev)
         cs = torch.empty(2, dtype=torch.int64, device=dev)
-        nat.check(lib.scpose_events_text_measure(_ptr(t), _ptr(x), _ptr(y), _ptr(p), n, _ptr(cs), _ptr(work), ws.value, _stream()),
+        nat.check(lib.scpose_events_text_measure(_ptr(t), _ptr(x), _ptr(y), _ptr(p), n, _ptr(cs), _ptr(work), ws, _stream()),
                   "events_text_measure")
         n_bytes = int(cs.tolist()[0])                           # the one small read-back
         out = torch.empty(n_bytes, dtype=torch.uint8, device=dev)
         # capacity == n_bytes: the status word of emit cannot be set, and is not read back
         nat.check(lib.scpose_events_text_emit(_ptr(t), _ptr(x), _ptr(y), _ptr(p), n, sb, int(bool(swap_xy)), _ptr(out), n_bytes,
-                                              _ptr(cs), _ptr(work), ws.value, _stream()), "events_text_emit")
+                                              _ptr(cs), _ptr(work), ws, _stream()), "events_text_emit")
     return out
 
 
@@ -489,14 +462,13 @@ def _unpack_events_aedat2_into(buf, n, hw, layout, flip_x, flip_y, unwrap, t_div
     (the one small read-back)."""
     h, w = int(hw[0]), int(hw[1])
     lib = nat.lib()
-    ws = c_size_t()
-    nat.check(lib.scpose_events_aedat2_unpack_workspace_bytes(n, ctypes.byref(ws)), "events_aedat2_unpack_workspace_bytes")
+    ws = _query_bytes("events_aedat2_unpack_workspace_bytes", n)
     with torch.cuda.device(buf.device):
         cs = torch.empty(6, dtype=torch.int64, device=buf.device)
-        work = torch.empty(ws.value, dtype=torch.uint8, device=buf.device)
+        work = torch.empty(ws, dtype=torch.uint8, device=buf.device)
         nat.check(lib.scpose_events_aedat2_unpack(_ptr(buf), n, h, w, _aedat2_layout(layout), int(bool(flip_x)), int(bool(flip_y)),
                                                   int(bool(unwrap)), c_double(float(t_divisor)), _ptr(t), _ptr(x), _ptr(y), _ptr(p),
-                                                  int(capacity), _ptr(cs), _ptr(work), ws.value, _stream()), "events_aedat2_unpack")
+                                                  int(capacity), _ptr(cs), _ptr(work), ws, _stream()), "events_aedat2_unpack")
         return cs.tolist()
 
 
@@ -522,10 +494,7 @@ def unpack_events_aedat2(records, hw, layout="davis", flip_x=True, flip_y=True, 
     dev = buf.device
     _aedat2_layout(layout)
     with torch.cuda.device(dev):
-        t = torch.empty(n, dtype=torch.int64, device=dev)
-        x = torch.empty(n, dtype=torch.int32, device=dev)
-        y = torch.empty(n, dtype=torch.int32, device=dev)
-        p = torch.empty(n, dtype=torch.int8, device=dev)
+        t, x, y, p = _empty_event_columns(n, dev)
         cs = _unpack_events_aedat2_into(buf, n, hw, layout, flip_x, flip_y, unwrap, t_divisor, t, x, y, p, n)
     status = cs[1]
     if status & nat.AEDAT2_READ_RANGE:
@@ -562,8 +531,7 @@ def _jpeg_decode_group(headers, files, rgb, max_rounds, dev, out=None, y_out=Non
     n = len(headers)
     desc, rows, data, max_subs = jr.pack_batch(headers, files)
     lib = nat.lib()
-    ws = c_size_t()
-    nat.check(lib.scpose_jpeg_decode_workspace_bytes(n, h, w, jr.MODES[mode], max_subs, ctypes.byref(ws)), "jpeg_decode_workspace_bytes")
+    ws = _query_bytes("jpeg_decode_workspace_bytes", n, h, w, jr.MODES[mode], max_subs)
     with torch.cuda.device(dev):
         d_desc = torch.from_numpy(desc).to(dev, non_blocking=True)
         d_rows = torch.from_numpy(rows).to(dev, non_blocking=True)
@@ -571,10 +539,10 @@ def _jpeg_decode_group(headers, files, rgb, max_rounds, dev, out=None, y_out=Non
         if out is None:
             out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
         status = torch.empty(n, dtype=torch.int32, device=dev)
-        work = _jpeg_workspace(dev, ws.value)
+        work = _jpeg_workspace(dev, ws)
         nat.check(lib.scpose_jpeg_decode(_ptr(d_desc), _ptr(d_rows), int(rows.shape[0]), _ptr(d_data), int(data.size), n, h, w,
                                          jr.MODES[mode], int(max_subs), 0 if rgb else 1, int(max_rounds), _ptr(out), _ptr(y_out),
-                                         _ptr(status), _ptr(work), ws.value, _stream()), "jpeg_decode")
+                                         _ptr(status), _ptr(work), ws, _stream()), "jpeg_decode")
         return out, status.tolist()
 
 
@@ -691,8 +659,7 @@ def encode_jpeg(frames, quality=75, subsampling="420", device=None, comment=None
     mode = jw.MODES[subsampling]
     dev = frames.device
     lib = nat.lib()
-    ws, cap = c_size_t(), c_int64()
-    nat.check(lib.scpose_jpeg_encode_workspace_bytes(n, h, w, mode, ctypes.byref(ws)), "jpeg_encode_workspace_bytes")
+    ws, cap = _query_bytes("jpeg_encode_workspace_bytes", n, h, w, mode), c_int64()
     nat.check(lib.scpose_jpeg_encode_capacity_bytes(n, h, w, mode, len(head), ctypes.byref(cap)), "jpeg_encode_capacity_bytes")
     with torch.cuda.device(dev):
         huff = _JPEG_ENC_HUFF.get(dev.index)
@@ -702,9 +669,9 @@ def encode_jpeg(frames, quality=75, subsampling="420", device=None, comment=None
         out = torch.empty(cap.value, dtype=torch.uint8, device=dev)
         offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
         status = torch.empty(n, dtype=torch.int32, device=dev)
-        work = _jpeg_workspace(dev, ws.value)
+        work = _jpeg_workspace(dev, ws)
         nat.check(lib.scpose_jpeg_encode(_ptr(frames), n, h, w, mode, int(quality), _ptr(huff), _ptr(d_head), len(head), _ptr(out),
-                                         cap.value, _ptr(offsets), _ptr(status), _ptr(work), ws.value, _stream()), "jpeg_encode")
+                                         cap.value, _ptr(offsets), _ptr(status), _ptr(work), ws, _stream()), "jpeg_encode")
         off = offsets.tolist()
         bad = [i for i, st in enumerate(status.tolist()) if st]
         if bad:
@@ -747,13 +714,10 @@ class DvsEmulator:
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         if self.device.type != "cuda":
             raise nat.NativeError("dvs_emulator needs a ROCm device (got %s); there is no CPU path" % self.device)
-        lib = nat.lib()
-        sb = c_size_t()
-        nat.check(lib.scpose_dvs_state_bytes(self.h, self.w, ctypes.byref(sb)), "dvs_state_bytes")
         up = lambda a: torch.from_numpy(a).to(self.device) if a is not None else None
         self._maps = [up(self._p[k]) for k in ("pos_map", "neg_map", "noise_map")]
         self._lut = up(de.lin_log_table())
-        self._state = torch.zeros(sb.value, dtype=torch.uint8, device=self.device)
+        self._state = torch.zeros(_query_bytes("dvs_state_bytes", self.h, self.w), dtype=torch.uint8, device=self.device)
         self._c = nat.DvsParams(self.h, self.w, self._p["pos"], self._p["neg"], self._maps[0].data_ptr() if self._maps[0] is not None else None,
                                 self._maps[1].data_ptr() if self._maps[1] is not None else None,
                                 self._maps[2].data_ptr() if self._maps[2] is not None else None, self._lut.data_ptr(),
@@ -799,23 +763,19 @@ class DvsEmulator:
                 self._t_prev = float(th[0])
                 fr, th = fr[1:], th[1:]
             f = int(fr.shape[0])
-            empty = lambda dt: torch.empty(0, dtype=dt, device=dev)
             if f == 0:
-                return empty(torch.int64), empty(torch.int32), empty(torch.int32), empty(torch.int8), empty(torch.float32)
+                return _empty_event_columns(0, dev) + (torch.empty(0, dtype=torch.float32, device=dev),)
             t_d = (t.to(dev, torch.float64)[-f:] if torch.is_tensor(t) else torch.from_numpy(th).to(dev)).contiguous()
-            ws = c_size_t()
-            nat.check(lib.scpose_dvs_workspace_bytes(self.h, self.w, f, self._p["max_iters"], ctypes.byref(ws)), "dvs_workspace_bytes")
-            work = torch.empty(ws.value, dtype=torch.uint8, device=dev)
+            ws = _query_bytes("dvs_workspace_bytes", self.h, self.w, f, self._p["max_iters"])
+            work = torch.empty(ws, dtype=torch.uint8, device=dev)
             cs = torch.empty(2, dtype=torch.int64, device=dev)
             fixed = capacity is not None
             cap = int(capacity) if fixed else max(4096, int(self._per_frame * 1.25 * f * self.h * self.w) + 1024)
             saved = None if fixed else self._state.clone()
             while True:
-                cols = (torch.empty(cap, dtype=torch.float32, device=dev), torch.empty(cap, dtype=torch.int64, device=dev),
-                        torch.empty(cap, dtype=torch.int32, device=dev), torch.empty(cap, dtype=torch.int32, device=dev),
-                        torch.empty(cap, dtype=torch.int8, device=dev))
+                cols = (torch.empty(cap, dtype=torch.float32, device=dev),) + _empty_event_columns(cap, dev)
                 nat.check(lib.scpose_dvs_emulate(_ptr(self._state), _ptr(fr), _ptr(t_d), f, ctypes.byref(self._c), _ptr(cols[0]), _ptr(cols[1]),
-                                                 _ptr(cols[2]), _ptr(cols[3]), _ptr(cols[4]), cap, _ptr(cs), _ptr(work), ws.value, _stream()),
+                                                 _ptr(cols[2]), _ptr(cols[3]), _ptr(cols[4]), cap, _ptr(cs), _ptr(work), ws, _stream()),
                           "dvs_emulate")
                 n, status = cs.tolist()                             # the one small read-back
                 self.last_status = status
@@ -1052,9 +1012,37 @@ class HrnetEngine:
         self._ws = None
 
     def workspace_bytes(self, n, h, w):
-        b = c_size_t()
-        nat.check(nat.lib().scpose_hrnet_workspace_bytes(self._h, n, h, w, ctypes.byref(b)), "hrnet_workspace_bytes")
-        return b.value
+        return _query_bytes("hrnet_workspace_bytes", self._h, n, h, w)
+
+    @staticmethod
+    def _input_format(x, who=None):
+        """(fmt, n, h, w) of the input batch x: uint8 (N, H, W, 3) or float32 (N, 3, H, W).  who: the capture method that binds x
+        by address and so refuses a dtype it would have to convert; the forward methods convert before they ask."""
+        if x.dtype == torch.uint8:
+            n, h, w, c = x.shape
+            fmt = nat.IN_U8_NHWC
+        elif x.dtype == torch.float32:
+            n, c, h, w = x.shape
+            fmt = nat.IN_F32_NCHW
+        else:
+            raise nat.NativeError("%s: input must be uint8 NHWC or float32 NCHW" % who)
+        if c != 3:
+            raise nat.NativeError("HRNet input must have 3 channels, got %d" % c)
+        return fmt, n, h, w
+
+    def _grow_workspace(self, n, h, w, device):
+        need = self.workspace_bytes(n, h, w)
+        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=device)
+
+    def _heatmap_buffer(self, who, n, h, w, device, out):
+        """out, checked against the heat-map shape of an (n, h, w) input, or a new buffer of that shape when out is None."""
+        shape = (n, self.num_joints) + self.heatmap_size(h, w)
+        if out is None:
+            return torch.empty(shape, dtype=torch.float32, device=device)
+        if tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
+            raise nat.NativeError("%s: out must be contiguous float32 %s" % (who, shape))
+        return out
 
     def heatmap_size(self, h, w):
         oh = c_int32(); ow = c_int32()
@@ -1070,24 +1058,10 @@ class HrnetEngine:
         """x: float32 (N,3,H,W) normalised, or uint8 (N,H,W,3) raw RGB.  Returns f32 (N,J,H/4,W/4).
         profile=True records a HIP event around every launch (read with profile_read())."""
         _need_cuda(x)
-        x = x.contiguous()
-        if x.dtype == torch.uint8:
-            n, h, w, c = x.shape
-            fmt = nat.IN_U8_NHWC
-        else:
-            x = x.float()
-            n, c, h, w = x.shape
-            fmt = nat.IN_F32_NCHW
-        if c != 3:
-            raise nat.NativeError("HRNet input must have 3 channels, got %d" % c)
-        need = self.workspace_bytes(n, h, w)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != x.device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=x.device)
-        oh, ow = self.heatmap_size(h, w)
-        if out is None:
-            out = torch.empty((n, self.num_joints, oh, ow), dtype=torch.float32, device=x.device)
-        elif tuple(out.shape) != (n, self.num_joints, oh, ow) or out.dtype != torch.float32 or not out.is_contiguous():
-            raise nat.NativeError("hrnet_forward: out must be contiguous float32 %s" % ((n, self.num_joints, oh, ow),))
+        x = x.contiguous() if x.dtype == torch.uint8 else x.contiguous().float()
+        fmt, n, h, w = self._input_format(x)
+        self._grow_workspace(n, h, w, x.device)
+        out = self._heatmap_buffer("hrnet_forward", n, h, w, x.device, out)
         fn = nat.lib().scpose_hrnet_forward_profiled if profile else nat.lib().scpose_hrnet_forward
         nat.check(fn(self._h, _ptr(x), fmt, n, h, w, _ptr(out), _ptr(self._ws), self._ws.numel(), _stream()), "hrnet_forward")
         self._last_hw = (h, w)
@@ -1105,19 +1079,9 @@ class HrnetEngine:
         unless heatmaps=True (then (preds, heatmaps) is returned); other heads always go through a heat-map buffer.
         profile=True records a HIP event around every launch (read with profile_read())."""
         _need_cuda(x, center, scale)
-        x = x.contiguous()
-        if x.dtype == torch.uint8:
-            n, h, w, c = x.shape
-            fmt = nat.IN_U8_NHWC
-        else:
-            x = x.float()
-            n, c, h, w = x.shape
-            fmt = nat.IN_F32_NCHW
-        if c != 3:
-            raise nat.NativeError("HRNet input must have 3 channels, got %d" % c)
-        need = self.workspace_bytes(n, h, w)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != x.device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        x = x.contiguous() if x.dtype == torch.uint8 else x.contiguous().float()
+        fmt, n, h, w = self._input_format(x)
+        self._grow_workspace(n, h, w, x.device)
         oh, ow = self.heatmap_size(h, w)
         hm = None
         if heatmaps or not self.tail_fused(n, h, w):
@@ -1140,14 +1104,7 @@ class HrnetEngine:
                 raise nat.NativeError("capture_decode: the %s buffer must be contiguous (it is bound by address)" % name)
         if center.dtype != torch.float32 or scale.dtype != torch.float32:
             raise nat.NativeError("capture_decode: center / scale must be float32")
-        if x.dtype == torch.uint8:
-            n, h, w, c = x.shape
-            fmt = nat.IN_U8_NHWC
-        elif x.dtype == torch.float32:
-            n, c, h, w = x.shape
-            fmt = nat.IN_F32_NCHW
-        else:
-            raise nat.NativeError("capture_decode: input must be uint8 NHWC or float32 NCHW")
+        fmt, n, h, w = self._input_format(x, "capture_decode")
         oh, ow = self.heatmap_size(h, w)
         hm = None
         if heatmaps or not self.tail_fused(n, h, w):
@@ -1163,21 +1120,8 @@ class HrnetEngine:
         _need_cuda(x)
         if not x.is_contiguous():
             raise nat.NativeError("capture: the input buffer must be contiguous (it is bound by address)")
-        if x.dtype == torch.uint8:
-            n, h, w, c = x.shape
-            fmt = nat.IN_U8_NHWC
-        elif x.dtype == torch.float32:
-            n, c, h, w = x.shape
-            fmt = nat.IN_F32_NCHW
-        else:
-            raise nat.NativeError("capture: input must be uint8 NHWC or float32 NCHW")
-        if c != 3:
-            raise nat.NativeError("HRNet input must have 3 channels, got %d" % c)
-        oh, ow = self.heatmap_size(h, w)
-        if out is None:
-            out = torch.empty((n, self.num_joints, oh, ow), dtype=torch.float32, device=x.device)
-        elif tuple(out.shape) != (n, self.num_joints, oh, ow) or out.dtype != torch.float32 or not out.is_contiguous():
-            raise nat.NativeError("capture: out must be contiguous float32 %s" % ((n, self.num_joints, oh, ow),))
+        fmt, n, h, w = self._input_format(x, "capture")
+        out = self._heatmap_buffer("capture", n, h, w, x.device, out)
         return HrnetGraph(self, x, fmt, (n, h, w), out, concurrent)
 
     def tap_names(self):
@@ -1195,17 +1139,9 @@ class HrnetEngine:
         """Intermediate tensor `tap` ("stem2", "layer1", "stage3.1.out0", ...) of the forward of x as float32
         (N, C, h, w): the forward is run up to the op that produces it (unit-level parity against the oracle's taps)."""
         _need_cuda(x)
-        x = x.contiguous()
-        if x.dtype == torch.uint8:
-            n, h, w, _ = x.shape
-            fmt = nat.IN_U8_NHWC
-        else:
-            x = x.float()
-            n, _, h, w = x.shape
-            fmt = nat.IN_F32_NCHW
-        need = self.workspace_bytes(n, h, w)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != x.device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        x = x.contiguous() if x.dtype == torch.uint8 else x.contiguous().float()
+        fmt, n, h, w = self._input_format(x)
+        self._grow_workspace(n, h, w, x.device)
         c = c_int32(); oh = c_int32(); ow = c_int32()
         fn = nat.lib().scpose_hrnet_forward_tap
         nat.check(fn(self._h, None, fmt, n, h, w, tap.encode(), None, ctypes.byref(c), ctypes.byref(oh), ctypes.byref(ow), None, 0, None),
@@ -1274,10 +1210,8 @@ class HrnetGraph:
 
     def __init__(self, engine, x, fmt, nhw, out, concurrent, decode=None):
         n, h, w = nhw
-        b = c_size_t()
-        nat.check(nat.lib().scpose_hrnet_graph_workspace_bytes(engine._h, n, h, w, ctypes.byref(b)), "hrnet_graph_workspace_bytes")
         self.engine, self.x, self.out = engine, x, out
-        self._ws = torch.empty(b.value, dtype=torch.uint8, device=x.device)       # owned by the graph: addresses are baked in
+        self._ws = torch.empty(_query_bytes("hrnet_graph_workspace_bytes", engine._h, n, h, w), dtype=torch.uint8, device=x.device)       # owned by the graph: addresses are baked in
         torch.cuda.synchronize(x.device)     # create runs one eager forward on an internal stream: every pending write to x / out,
                                              # on any stream of x's device (not only the current one), must have landed
         g = c_void_p()
