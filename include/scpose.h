@@ -463,6 +463,29 @@ int32_t scpose_jpeg_decode(const uint8_t* desc, const int32_t* segs, int64_t n_s
                            int32_t n, int32_t h, int32_t w, int32_t mode, int32_t max_subs, int32_t bgr, int32_t max_rounds,
                            uint8_t* out, uint8_t* y_out, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* (ABI 7, additive) Baseline JPEG files -> network crops on the device (csrc/jpeg_decode.hip): crops[i] is, bit for bit, what
+ * scpose_crop_warp_roi returns for the window roi_xywh[i] of the frame scpose_jpeg_decode returns for file i -- without that frame.
+ * The entropy decoding and the DC sums run on the whole frame (the stream has no entry points); the inverse DCT runs only for the
+ * blocks that hold a sample a pixel of the window reads (at 4:2:0 one chroma sample more on each side, clamped at the plane's
+ * edge: the reach of the fancy upsampling); every one of the four bilinear taps of a crop pixel is then computed from the sample
+ * planes.  A tap outside the frame or outside the window counts as 0, as in scpose_crop_warp_roi.
+ *   desc, segs, n_seg_rows, data, n_bytes, n, h, w, mode, max_subs, bgr, max_rounds, status, workspace
+ *                as for scpose_jpeg_decode; the workspace is the same scpose_jpeg_decode_workspace_bytes(n, h, w, mode, max_subs)
+ *   minv         device f64 [n][6], 8-byte aligned: the inverse affine (crop -> frame) of each image, what scpose_crop_warp_roi takes
+ *   roi_xywh     HOST i32 [n][4]: [x0, y0, w, h], a window of the frame that holds every pixel the warp reads (w or h may be 0:
+ *                the crop is all zeros).  Read before the call returns: each is checked to lie inside the frame -- it bounds
+ *                every sample the crop kernel reads -- and travels to the kernels in their arguments, 128 images per launch
+ *   out_h, out_w 1 .. 65535 each
+ *   crops        device u8 [n][out_h][out_w][3] <- the crops, channels in the order `bgr` selects.  The crop of an image with a
+ *                status bit set is unspecified.
+ * No allocation, no synchronisation, no atomics but integer ORs into status; floating point only in the source position of a
+ * crop pixel (contraction off, as in scpose_crop_warp); two calls on the same bytes give bitwise equal outputs.  Argument errors
+ * return -1 with a message before anything is launched. */
+int32_t scpose_jpeg_decode_crop(const uint8_t* desc, const int32_t* segs, int64_t n_seg_rows, const uint8_t* data, int64_t n_bytes,
+                                int32_t n, int32_t h, int32_t w, int32_t mode, int32_t max_subs, int32_t bgr, int32_t max_rounds,
+                                const double* minv, const int32_t* roi_xywh, int32_t out_h, int32_t out_w, uint8_t* crops,
+                                int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 /* (ABI 7, additive) Baseline JPEG encoder on the device (csrc/jpeg_encode.hip): (N, H, W, 3) uint8 RGB frames of one size ->
  * N baseline JPEG byte streams, byte for byte what libjpeg's baseline encoder writes with the standard Huffman tables (PIL's
  * save(quality=q, subsampling=..) with its other defaults): jccolor.c, jcsample.c's h2v2 downsampling, jfdctint.c's forward

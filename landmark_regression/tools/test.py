@@ -50,6 +50,10 @@ def parse_args():
                         help="(extension, the default) warp the crops on the GPU (scpose_crop_warp): the loader only decodes the frames")
     parser.add_argument("--host_crop", dest="device_crop", action="store_false",
                         help="(extension) warp and normalise the crops in the data loader, as the reference does")
+    parser.add_argument("--device_decode", action="store_true",
+                        help="(extension) decode baseline JPEG frames on the GPU, straight into the crops (ops.decode_crop): the loader only reads "
+                             "the files; any other file is decoded by the loader as usual.  Same pred .mat, bit for bit; not with --host_crop.  "
+                             "The same as the override DATASET.DEVICE_DECODE True, which tools/test_cv_ensemble.py takes as well")
     parser.add_argument("--no_auto_workers", action="store_true",
                         help="(extension) keep cfg.WORKERS = 0 as 'decode in this process'.  By default a data set of 512 frames or more is decoded by "
                              "min(32, cores / 4) worker processes even when the YAML says WORKERS: 0 (the reference's events-config.yaml does): same "
@@ -61,7 +65,10 @@ def parse_args():
     parser.add_argument("--log_metrics", action="store_true",
                         help="(extension) compute the loss / PCK the reference logs per batch; they need the heat-maps, so the forward "
                              "then writes them instead of handing key points out of its last kernel (same pred .mat, bit for bit)")
-    return parser.parse_args()
+    args = parser.parse_args()
+    if args.device_decode and not args.device_crop:
+        parser.error("--device_decode cannot be combined with --host_crop: the device decodes a frame straight into its crop")
+    return args
 
 
 def main():
@@ -93,6 +100,7 @@ def main():
         transforms.Compose([transforms.ToTensor(), normalize]))
     lo, hi = parallel.shard_range(len(valid_dataset), rank, ws)
     valid_dataset.device_crop = bool(args.device_crop)
+    valid_dataset.device_decode = bool(args.device_decode or cfg.DATASET.DEVICE_DECODE)      # the flag, or the config key every CLI takes
     valid_dataset.want_target = bool(args.log_metrics)     # gaussian targets feed the logged loss / PCK only
     workers = parallel.auto_workers(hi - lo, cfg.WORKERS, keep=args.no_auto_workers)
     if workers != int(cfg.WORKERS):

@@ -137,6 +137,8 @@ SYMBOLS = {
     "scpose_jpeg_decode_workspace_bytes": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
     "scpose_jpeg_decode": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                      c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "scpose_jpeg_decode_crop": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                          c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "scpose_jpeg_encode_workspace_bytes": (c_int32, [c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
     "scpose_jpeg_encode_capacity_bytes": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int64)]),
     "scpose_jpeg_encode": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p,

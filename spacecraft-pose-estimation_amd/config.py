@@ -170,6 +170,9 @@ def _defaults():
                     "IMAGE_WIDTH": 1280, "IMAGE_HEIGHT": 720, "HYBRID_JOINTS_TYPE": "", "SELECT_DATA": False,
                     "FLIP": True, "SCALE_FACTOR": 0.25, "ROT_FACTOR": 30, "PROB_HALF_BODY": 0.0,
                     "NUM_JOINTS_HALF_BODY": 8, "COLOR_RGB": False})
+    # extension (not in the reference's tree): decode baseline JPEG frames on the device (dataset/JointsDataset.py: device_decode).  A
+    # config key, so that every CLI that takes KEY VAL overrides takes it: tools/test_cv_ensemble.py DATASET.DEVICE_DECODE True
+    c.DATASET.DEVICE_DECODE = False
     c.TRAIN = CN({"LR_FACTOR": 0.1, "LR_STEP": [90, 110], "LR": 0.001, "OPTIMIZER": "adam", "MOMENTUM": 0.9,
                   "WD": 0.0001, "NESTEROV": False, "GAMMA1": 0.99, "GAMMA2": 0.0, "BEGIN_EPOCH": 0,
                   "END_EPOCH": 140, "RESUME": False, "CHECKPOINT": "", "BATCH_SIZE_PER_GPU": 32,

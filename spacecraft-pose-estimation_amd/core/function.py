@@ -103,6 +103,24 @@ class _Coalescer:
         return out
 
 
+def _decode_crops(config, frames, meta, dev):
+    """A device_decode batch (dataset.collate_device_crop) -> its crops in loader order: ops.decode_crop for the compressed files,
+    in the channel order _imread gives for COLOR_RGB, ops.crop_warp for the windows of the rows the loader decoded itself."""
+    size_wh = (int(config.MODEL.IMAGE_SIZE[0]), int(config.MODEL.IMAGE_SIZE[1]))
+    trans, rows, offs = meta["trans"].numpy(), frames["file_rows"], frames["file_offsets"].tolist()
+    files = [frames["files"][offs[k]:offs[k + 1]] for k in range(len(offs) - 1)]
+    crops, _ = ops.decode_crop(files, trans[rows.numpy()], size_wh, rgb=bool(config.DATASET.COLOR_RGB), device=dev)
+    if "window_rows" not in frames:
+        return crops                # collate keeps the files in row order
+    wrows = frames["window_rows"]
+    other = ops.crop_warp({k: frames[k] for k in ("flat", "offsets", "hw")}, trans[wrows.numpy()], size_wh, device=dev,
+                          roi=meta["roi"].numpy()[wrows.numpy()], frame_hw=meta["frame_hw"].numpy()[wrows.numpy()])
+    out = torch.empty((int(rows.numel() + wrows.numel()),) + tuple(crops.shape[1:]), dtype=torch.uint8, device=dev)
+    out.index_copy_(0, rows.to(dev), crops)
+    out.index_copy_(0, wrows.to(dev), other)
+    return out
+
+
 def _run(config, val_loader, val_dataset, models, criterion, output_dir, pred_file_name, log_metrics, flip_test, print_freq=None, print_table=True,
          engine_batch=None):
     batch_time, losses, acc = AverageMeter(), AverageMeter(), AverageMeter()
@@ -149,7 +167,11 @@ def _run(config, val_loader, val_dataset, models, criterion, output_dir, pred_fi
     with torch.no_grad():
         end = time.time()
         for i, (input, target, target_weight, meta) in enumerate(val_loader):
-            if isinstance(input, (list, tuple, dict)):   # dataset.device_crop: frame windows -> uint8 NHWC crops on the GPU
+            if isinstance(input, dict) and "files" in input:   # dataset.device_decode: compressed files -> uint8 NHWC crops on the GPU
+                if i == 0:
+                    logger.info("validate: baseline JPEG frames are decoded on the device, straight into the crops (ops.decode_crop)")
+                input = _decode_crops(config, input, meta, dev)
+            elif isinstance(input, (list, tuple, dict)):   # dataset.device_crop: frame windows -> uint8 NHWC crops on the GPU
                 size_wh = config.MODEL.IMAGE_SIZE
                 input = ops.crop_warp(input, meta["trans"].numpy(), (int(size_wh[0]), int(size_wh[1])), device=dev,
                                       roi=meta["roi"].numpy() if "roi" in meta else None,

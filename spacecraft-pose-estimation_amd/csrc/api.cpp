@@ -311,6 +311,30 @@ extern "C" int32_t scpose_jpeg_decode(const uint8_t* desc, const int32_t* segs, 
                             static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
 }
 
+extern "C" int32_t scpose_jpeg_decode_crop(const uint8_t* desc, const int32_t* segs, int64_t n_seg_rows, const uint8_t* data, int64_t n_bytes,
+                                           int32_t n, int32_t h, int32_t w, int32_t mode, int32_t max_subs, int32_t bgr, int32_t max_rounds,
+                                           const double* minv, const int32_t* roi_xywh, int32_t out_h, int32_t out_w, uint8_t* crops,
+                                           int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int32_t rc = jpeg_check_shape(n, h, w, mode, max_subs, "jpeg_decode_crop")) return rc;
+  SCP_REQUIRE(max_rounds >= 1 && max_rounds <= 250, "jpeg_decode_crop: max_rounds=%d (1 .. 250)", max_rounds);
+  SCP_REQUIRE(n_seg_rows >= 2 * (int64_t)n && n_seg_rows < ((int64_t)1 << 31) && n_bytes >= 0, "jpeg_decode_crop: n_seg_rows=%lld n_bytes=%lld",
+              (long long)n_seg_rows, (long long)n_bytes);
+  SCP_REQUIRE(out_h >= 1 && out_w >= 1 && out_h <= 65535 && out_w <= 65535, "jpeg_decode_crop: bad output size %dx%d (each 1 .. 65535)", out_h,
+              out_w);
+  SCP_REQUIRE(desc && segs && (data || n_bytes == 0) && minv && roi_xywh && crops && status, "jpeg_decode_crop: null argument");
+  SCP_REQUIRE(aligned(desc, 8) && aligned(minv, 8) && aligned(segs, 4) && aligned(status, 4),
+              "jpeg_decode_crop: desc and minv must be 8-byte aligned, segs and status 4-byte aligned");
+  for (int32_t i = 0; i < n; ++i) {      // roi_xywh is host memory: the window bounds every sample the crop kernel reads
+    const int32_t* r = roi_xywh + 4 * (size_t)i;
+    SCP_REQUIRE(r[0] >= 0 && r[1] >= 0 && r[2] >= 0 && r[3] >= 0 && (int64_t)r[0] + r[2] <= w && (int64_t)r[1] + r[3] <= h,
+                "jpeg_decode_crop: roi %d = [%d, %d, %d, %d] (x, y, w, h) is not inside the %dx%d (HxW) frame", i, r[0], r[1], r[2], r[3], h, w);
+  }
+  if (int32_t rc = workspace_ok("jpeg_decode_crop", workspace, workspace_bytes, jpeg_decode_workspace_bytes(n, h, w, mode, max_subs), 256))
+    return rc;
+  return jpeg_decode_crop_launch(desc, segs, n_seg_rows, data, n_bytes, n, h, w, mode, max_subs, bgr != 0, max_rounds, minv, roi_xywh, out_h,
+                                 out_w, crops, status, static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
 static int32_t jpeg_encode_check_shape(int32_t n, int32_t h, int32_t w, int32_t mode, const char* who) {
   if (int32_t rc = jpeg_frame_ok(who, n, h, w, mode)) return rc;
   SCP_REQUIRE(jpeg_blocks(h, w, mode) * 2800 < ((int64_t)1 << 31),

@@ -284,6 +284,10 @@ size_t jpeg_decode_workspace_bytes(int n, int h, int w, int mode, int max_subs);
 int32_t jpeg_decode_launch(const uint8_t* desc, const int32_t* segs, int64_t n_rows, const uint8_t* data, int64_t n_bytes, int n, int h,
                            int w, int mode, int max_subs, int bgr, int max_rounds, uint8_t* out, uint8_t* y_out, int32_t* status,
                            uint8_t* ws, hipStream_t stream);
+// the same files -> the crop_warp of each frame, (N, out_h, out_w, 3), without the frame.  roi_host: host int32 [n][4], each inside the frame
+int32_t jpeg_decode_crop_launch(const uint8_t* desc, const int32_t* segs, int64_t n_rows, const uint8_t* data, int64_t n_bytes, int n, int h,
+                                int w, int mode, int max_subs, int bgr, int max_rounds, const double* minv, const int32_t* roi_host,
+                                int out_h, int out_w, uint8_t* crops, int32_t* status, uint8_t* ws, hipStream_t stream);
 
 // jpeg_encode.hip: (N, H, W, 3) uint8 frames -> baseline JPEG byte streams; the overlay draw in front of it
 size_t jpeg_encode_workspace_bytes(int n, int h, int w, int mode);

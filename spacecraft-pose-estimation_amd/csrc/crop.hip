@@ -37,11 +37,9 @@ __global__ __launch_bounds__(256) void crop_warp_kernel(const uint8_t* __restric
     // roi != null: only the window [ry, ry + rh) x [rx, rx + rw) of frame n is stored (the loader ships the part of the frame the
     // warp can touch instead of 1920 x 1200 x 3 bytes per frame); coordinates, weights and the frame border stay those of the whole frame
     const int rx = roi ? roi[4 * n] : 0, ry = roi ? roi[4 * n + 1] : 0, rw = roi ? roi[4 * n + 2] : sw, rh = roi ? roi[4 * n + 3] : sh;
-    const double xs = (double)x, ys = (double)y;
-    const long long X = (sat_round_int32((m[1] * ys + m[2]) * 1024.0) + 16 + sat_round_int32(m[0] * xs * 1024.0)) >> 5;
-    const long long Y = (sat_round_int32((m[4] * ys + m[5]) * 1024.0) + 16 + sat_round_int32(m[3] * xs * 1024.0)) >> 5;
-    const long long x0 = sat_int16(X >> 5), y0 = sat_int16(Y >> 5);
-    const BilinearTap bil((int)(X & 31), (int)(Y & 31));      // bilinear_fixed.h: the tap shared with events.hip
+    const AffineSource p = affine_source(m, x, y);            // bilinear_fixed.h: the position shared with jpeg_decode.hip's crop tail
+    const long long x0 = p.x0, y0 = p.y0;
+    const BilinearTap bil(p.a, p.b);                          // bilinear_fixed.h: the tap shared with events.hip
     uint8_t res[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {

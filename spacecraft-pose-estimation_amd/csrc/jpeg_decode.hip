@@ -22,12 +22,20 @@
 //   jpeg_idct_kernel    one thread per block: de-quantise, ISLOW inverse DCT in registers, range limit, 8 x 8 bytes into the
 //       component's plane (padded to whole MCUs).
 //   jpeg_output_kernel  four pixels per thread: fancy h2v2 chroma upsampling (4:2:0), colour conversion, crop to H x W.
+// scpose_jpeg_decode_crop ends differently: it wants the crop_warp of each frame (crop.hip), not the frame.  The passes up to the
+// DC sums run on the whole frame as above -- the entropy-coded bytes have no entry points and a DC value needs every block before
+// it -- and then
+//   jpeg_idct_window_kernel  the same inverse DCT, for the blocks that hold a sample the crop can read (sample_span below)
+//   jpeg_crop_kernel         one thread per crop pixel: crop.hip's source position and bilinear tap (bilinear_fixed.h), each of the
+//       four taps computed from the sample planes by jpeg_pixel(), the arithmetic of jpeg_output_kernel.  No frame is written;
+//       a sample outside the window stays uninitialised and is never read.
 // A speculative walk from a wrong state decodes garbage by design: every iteration consumes at least one bit, the walk ends with
 // the subsequence (plus one code word) or the segment, zeros are fed past the end of the data, and nothing but the thread's own
 // slot and count is written.  No code word starts in the encoder's fill bits (the last min(7, trailing ones) bits of a segment):
 // no Huffman code is all ones.  No floating point, no atomics but integer ORs into status; two runs are bitwise equal.
 #include "jpeg_common.h"
 #include "scan_device.h"
+#include "bilinear_fixed.h"
 
 namespace scpose {
 
@@ -369,11 +377,26 @@ __device__ __forceinline__ uint32_t limit8(int32_t v) {
   return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
 
-__global__ __launch_bounds__(kThreads) void jpeg_idct_kernel(const uint8_t* __restrict__ desc, Geo geo, const int16_t* __restrict__ coef,
-                                                             const int32_t* __restrict__ dc, uint8_t* __restrict__ plane_y,
-                                                             uint8_t* __restrict__ plane_c) {
+// The samples [lo, hi] of one axis of a component's plane that the pixels [p0, p0 + len) of that axis read (hi < lo: none).
+// Luma, and chroma at 4:4:4 (`half` false): the pixel's own sample.  Chroma at 4:2:0: chroma420() below reads sample p >> 1 and,
+// per axis, its neighbour on one side or the other, never one outside the plane of ceil(full / 2) samples -- so one sample more on
+// each side, clamped at the plane's edge.  jpeg_read.py: sample_span says the same to the host and the tests.
+struct Span {
+  int32_t lo, hi;
+};
+__device__ __forceinline__ Span sample_span(int32_t p0, int32_t len, int32_t full, bool half) {
+  if (len <= 0) return {0, -1};
+  if (!half) return {p0, p0 + len - 1};
+  const int32_t lo = (p0 >> 1) - 1, hi = ((p0 + len - 1) >> 1) + 1, last = ((full + 1) >> 1) - 1;
+  return {lo < 0 ? 0 : lo, hi > last ? last : hi};
+}
+
+// One thread per block of image `img`.  WINDOW: only a block that holds a sample the pixels of roi = [x0, y0, w, h] read.
+template <bool WINDOW>
+__device__ __forceinline__ void idct_blocks(const uint8_t* __restrict__ desc, const Geo& geo, const int16_t* __restrict__ coef,
+                                            const int32_t* __restrict__ dc, uint8_t* __restrict__ plane_y, uint8_t* __restrict__ plane_c,
+                                            int img, const int32_t* roi) {
   __shared__ int32_t q[3][64];
-  const int img = blockIdx.y;
   const int32_t* head = reinterpret_cast<const int32_t*>(desc + (size_t)img * kDesc);
   const uint16_t* qsrc = reinterpret_cast<const uint16_t*>(desc + (size_t)img * kDesc + kQuantOff);
   if (threadIdx.x < 192) q[threadIdx.x >> 6][threadIdx.x & 63] = qsrc[threadIdx.x];
@@ -383,6 +406,13 @@ __global__ __launch_bounds__(kThreads) void jpeg_idct_kernel(const uint8_t* __re
   const int32_t mcu = b / geo.bpm, blk = b - mcu * geo.bpm;
   const McuComp mc = mcu_comp_of_block(blk, geo.ycount);
   const int comp = mc.comp;
+  const int32_t mx = mcu % geo.mcus_x, my = mcu / geo.mcus_x;
+  const int32_t bx = comp == 0 ? mx * geo.hs + blk % geo.hs : mx, by = comp == 0 ? my * geo.hs + blk / geo.hs : my;   // in the component's plane
+  if (WINDOW) {
+    const bool half = comp != 0 && geo.mode == SCPOSE_JPEG_420;
+    const Span sx = sample_span(roi[0], roi[2], geo.w, half), sy = sample_span(roi[1], roi[3], geo.h, half);
+    if (sx.hi < sx.lo || sy.hi < sy.lo || bx < (sx.lo >> 3) || bx > (sx.hi >> 3) || by < (sy.lo >> 3) || by > (sy.hi >> 3)) return;
+  }
   const int32_t* d = dc + (size_t)img * geo.n_blocks;
   // the DC value: inclusive sum up to this block minus the sum up to the block before its restart segment
   const int32_t ri = head[5] >= 1 ? head[5] : 1;
@@ -411,15 +441,14 @@ __global__ __launch_bounds__(kThreads) void jpeg_idct_kernel(const uint8_t* __re
 #pragma unroll
     for (int row = 0; row < 8; ++row) ws[row][col] = out[row];
   }
-  const int32_t mx = mcu % geo.mcus_x, my = mcu / geo.mcus_x;
   uint8_t* dst;
   int32_t stride;
   if (comp == 0) {
     stride = geo.pw;
-    dst = plane_y + ((size_t)img * geo.ph + (size_t)(my * geo.hs + blk / geo.hs) * 8) * geo.pw + (size_t)(mx * geo.hs + blk % geo.hs) * 8;
+    dst = plane_y + ((size_t)img * geo.ph + (size_t)by * 8) * geo.pw + (size_t)bx * 8;
   } else {
     stride = geo.pcw;
-    dst = plane_c + (((size_t)(comp - 1) * geo.n + img) * geo.pch + (size_t)my * 8) * geo.pcw + (size_t)mx * 8;
+    dst = plane_c + (((size_t)(comp - 1) * geo.n + img) * geo.pch + (size_t)by * 8) * geo.pcw + (size_t)bx * 8;
   }
 #pragma unroll
   for (int row = 0; row < 8; ++row) {                  // pass 2: rows
@@ -430,6 +459,25 @@ __global__ __launch_bounds__(kThreads) void jpeg_idct_kernel(const uint8_t* __re
     px.y = limit8(out[4]) | (limit8(out[5]) << 8) | (limit8(out[6]) << 16) | (limit8(out[7]) << 24);
     *reinterpret_cast<uint2*>(dst + (size_t)row * stride) = px;
   }
+}
+
+__global__ __launch_bounds__(kThreads) void jpeg_idct_kernel(const uint8_t* __restrict__ desc, Geo geo, const int16_t* __restrict__ coef,
+                                                             const int32_t* __restrict__ dc, uint8_t* __restrict__ plane_y,
+                                                             uint8_t* __restrict__ plane_c) {
+  idct_blocks<false>(desc, geo, coef, dc, plane_y, plane_c, blockIdx.y, nullptr);
+}
+
+// The windows of up to kRoiChunk images travel in the kernel arguments: the host has them (api.cpp checks each against the frame),
+// and the workspace keeps the size scpose_jpeg_decode_workspace_bytes() states.  Image img0 + blockIdx.y has rois.v[blockIdx.y].
+constexpr int kRoiChunk = 128;
+struct RoiChunk {
+  int32_t v[kRoiChunk][4];
+};
+
+__global__ __launch_bounds__(kThreads) void jpeg_idct_window_kernel(const uint8_t* __restrict__ desc, Geo geo, const int16_t* __restrict__ coef,
+                                                                    const int32_t* __restrict__ dc, uint8_t* __restrict__ plane_y,
+                                                                    uint8_t* __restrict__ plane_c, RoiChunk rois, int img0) {
+  idct_blocks<true>(desc, geo, coef, dc, plane_y, plane_c, img0 + (int)blockIdx.y, rois.v[blockIdx.y]);
 }
 
 __device__ __forceinline__ int32_t clamp255(int32_t v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
@@ -451,40 +499,55 @@ __device__ __forceinline__ int32_t chroma420(const uint8_t* __restrict__ c, int3
   return (3 * here + 3 * rn[cx - 1] + rf[cx - 1] + 8) >> 4;
 }
 
+// the sample planes of one image; dw x dh: its chroma plane at 4:2:0
+struct Planes {
+  const uint8_t *y, *cb, *cr;
+  int32_t dw, dh;
+};
+__device__ __forceinline__ Planes image_planes(const Geo& geo, const uint8_t* __restrict__ plane_y, const uint8_t* __restrict__ plane_c, int img) {
+  return {plane_y + (size_t)img * geo.ph * geo.pw, plane_c + (size_t)img * geo.pch * geo.pcw,
+          plane_c + ((size_t)geo.n + img) * geo.pch * geo.pcw, (geo.w + 1) >> 1, (geo.h + 1) >> 1};
+}
+
+// Pixel (x, y) of the frame from the sample planes: what jpeg_output_kernel writes and what a tap of jpeg_crop_kernel is worth.
+struct Pixel {
+  int32_t y, r, g, b;
+};
+__device__ __forceinline__ Pixel jpeg_pixel(const Geo& geo, const Planes& p, int32_t x, int32_t y) {
+  const int32_t Y = p.y[(size_t)y * geo.pw + x];
+  Pixel v{Y, Y, Y, Y};
+  if (geo.mode != SCPOSE_JPEG_GRAY) {
+    int32_t cb, cr;
+    if (geo.mode == SCPOSE_JPEG_420) {
+      cb = chroma420(p.cb, geo.pcw, p.dw, p.dh, x, y);
+      cr = chroma420(p.cr, geo.pcw, p.dw, p.dh, x, y);
+    } else {
+      cb = p.cb[(size_t)y * geo.pcw + x];
+      cr = p.cr[(size_t)y * geo.pcw + x];
+    }
+    cb -= 128; cr -= 128;                              // jdcolor.c: SCALEBITS 16, FIX(1.40200), FIX(1.77200), FIX(0.71414), FIX(0.34414)
+    v.r = clamp255(Y + ((91881 * cr + 32768) >> 16));
+    v.g = clamp255(Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16));
+    v.b = clamp255(Y + ((116130 * cb + 32768) >> 16));
+  }
+  return v;
+}
+
 __global__ __launch_bounds__(kThreads) void jpeg_output_kernel(Geo geo, int bgr, const uint8_t* __restrict__ plane_y,
                                                                const uint8_t* __restrict__ plane_c, uint8_t* __restrict__ out,
                                                                uint8_t* __restrict__ y_out) {
   const int32_t x0 = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4, y = blockIdx.y * 4 + (threadIdx.x >> 6), img = blockIdx.z;
   if (x0 >= geo.w || y >= geo.h) return;
-  const uint8_t* py = plane_y + ((size_t)img * geo.ph + y) * geo.pw;
-  const uint8_t* pcb = plane_c + (size_t)img * geo.pch * geo.pcw;
-  const uint8_t* pcr = plane_c + ((size_t)geo.n + img) * geo.pch * geo.pcw;
-  const int32_t dw = (geo.w + 1) >> 1, dh = (geo.h + 1) >> 1;
+  const Planes pl = image_planes(geo, plane_y, plane_c, img);
   uint8_t px[12];
   uint8_t yy[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int32_t x = x0 + i < geo.w ? x0 + i : geo.w - 1;
-    const int32_t Y = py[x];
-    yy[i] = (uint8_t)Y;
-    int32_t r = Y, g = Y, b = Y;
-    if (geo.mode != SCPOSE_JPEG_GRAY) {
-      int32_t cb, cr;
-      if (geo.mode == SCPOSE_JPEG_420) {
-        cb = chroma420(pcb, geo.pcw, dw, dh, x, y);
-        cr = chroma420(pcr, geo.pcw, dw, dh, x, y);
-      } else {
-        cb = pcb[(size_t)y * geo.pcw + x];
-        cr = pcr[(size_t)y * geo.pcw + x];
-      }
-      cb -= 128; cr -= 128;                            // jdcolor.c: SCALEBITS 16, FIX(1.40200), FIX(1.77200), FIX(0.71414), FIX(0.34414)
-      r = clamp255(Y + ((91881 * cr + 32768) >> 16));
-      g = clamp255(Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16));
-      b = clamp255(Y + ((116130 * cb + 32768) >> 16));
-    }
-    px[3 * i] = (uint8_t)(bgr ? b : r);
-    px[3 * i + 1] = (uint8_t)g;
-    px[3 * i + 2] = (uint8_t)(bgr ? r : b);
+    const Pixel v = jpeg_pixel(geo, pl, x0 + i < geo.w ? x0 + i : geo.w - 1, y);
+    yy[i] = (uint8_t)v.y;
+    px[3 * i] = (uint8_t)(bgr ? v.b : v.r);
+    px[3 * i + 1] = (uint8_t)v.g;
+    px[3 * i + 2] = (uint8_t)(bgr ? v.r : v.b);
   }
   const size_t pix = ((size_t)img * geo.h + y) * geo.w + x0;
   if ((geo.w & 3) == 0) {                              // whole quads, 4-byte aligned rows
@@ -499,6 +562,40 @@ __global__ __launch_bounds__(kThreads) void jpeg_output_kernel(Geo geo, int bgr,
       out[(pix + i) * 3 + 2] = px[3 * i + 2];
       if (y_out) y_out[pix + i] = yy[i];
     }
+  }
+}
+
+// crop_warp_kernel (crop.hip) of frame img0 + blockIdx.y without the frame: the same source position and weights, every tap from
+// the sample planes.  A tap outside the frame or outside the image's window counts as 0 -- the window bounds every plane sample
+// that is read, and idct_blocks<true> has written exactly those (sample_span).
+__global__ __launch_bounds__(kThreads) void jpeg_crop_kernel(Geo geo, int bgr, const uint8_t* __restrict__ plane_y,
+                                                             const uint8_t* __restrict__ plane_c, const double* __restrict__ minv,
+                                                             RoiChunk rois, int img0, int oh, int ow, uint8_t* __restrict__ out) {
+  const int img = img0 + (int)blockIdx.y;
+  const int32_t rx = rois.v[blockIdx.y][0], ry = rois.v[blockIdx.y][1], rw = rois.v[blockIdx.y][2], rh = rois.v[blockIdx.y][3];
+  const Planes pl = image_planes(geo, plane_y, plane_c, img);
+  const double* m = minv + (size_t)img * 6;
+  const int64_t total = (int64_t)oh * ow;
+  uint8_t* o = out + (size_t)img * total * 3;
+  for (int64_t pix = (int64_t)blockIdx.x * kThreads + threadIdx.x; pix < total; pix += (int64_t)gridDim.x * kThreads) {
+    const AffineSource p = affine_source(m, (int)(pix % ow), (int)(pix / ow));
+    const BilinearTap bil(p.a, p.b);
+    Pixel t[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const long long yy = p.y0 + (j >> 1), xx = p.x0 + (j & 1);
+      const bool ok = yy >= 0 && yy < geo.h && xx >= 0 && xx < geo.w && yy >= ry && yy < ry + rh && xx >= rx && xx < rx + rw;
+      t[j] = ok ? jpeg_pixel(geo, pl, (int32_t)xx, (int32_t)yy) : Pixel{0, 0, 0, 0};
+    }
+    const uint8_t r = bil(t[0].r, t[1].r, t[2].r, t[3].r);
+    uint8_t g = r, b = r;
+    if (geo.mode != SCPOSE_JPEG_GRAY) {
+      g = bil(t[0].g, t[1].g, t[2].g, t[3].g);
+      b = bil(t[0].b, t[1].b, t[2].b, t[3].b);
+    }
+    o[pix * 3] = bgr ? b : r;
+    o[pix * 3 + 1] = g;
+    o[pix * 3 + 2] = bgr ? r : b;
   }
 }
 
@@ -534,23 +631,54 @@ size_t jpeg_decode_workspace_bytes(int n, int h, int w, int mode, int max_subs) 
   return make_plan(make_geo(n, h, w, mode, max_subs, 0, 0), nullptr).bytes;
 }
 
+namespace {
+
+// memset, relaxation, scan, coefficient write, DC sums: the passes every entry point runs on the whole frame
+int32_t launch_entropy_passes(const Geo& g, const Plan& p, const uint8_t* desc, const int32_t* segs, const uint8_t* data, int max_rounds,
+                           int32_t* status, uint8_t* ws, hipStream_t stream) {
+  SCP_CHECK_HIP(hipMemsetAsync(ws, 0, p.zero_bytes, stream));
+  const dim3 subs_grid((unsigned)((g.max_subs + kThreads - 1) / kThreads), (unsigned)g.n);
+  for (int launch = 1; launch <= max_rounds; ++launch)
+    hipLaunchKernelGGL(jpeg_relax_kernel, subs_grid, dim3(kThreads), 0, stream, desc, segs, data, g, launch, p.slots, p.counts);
+  hipLaunchKernelGGL(jpeg_scan_kernel, dim3((unsigned)g.n), dim3(kThreads), 0, stream, desc, g, max_rounds, p.slots, p.counts, p.totals, status);
+  hipLaunchKernelGGL(jpeg_write_kernel, subs_grid, dim3(kThreads), 0, stream, desc, segs, data, g, p.slots, p.counts, p.totals, p.coef, p.dc,
+                     status);
+  hipLaunchKernelGGL(jpeg_dc_kernel, dim3(g.mode == SCPOSE_JPEG_GRAY ? 1u : 3u, (unsigned)g.n), dim3(kThreads), 0, stream, g, p.dc);
+  return SCPOSE_OK;
+}
+
+}  // namespace
+
 int32_t jpeg_decode_launch(const uint8_t* desc, const int32_t* segs, int64_t n_rows, const uint8_t* data, int64_t n_bytes, int n, int h,
                            int w, int mode, int max_subs, int bgr, int max_rounds, uint8_t* out, uint8_t* y_out, int32_t* status,
                            uint8_t* ws, hipStream_t stream) {
   const Geo g = make_geo(n, h, w, mode, max_subs, n_bytes, n_rows);
   const Plan p = make_plan(g, ws);
-  SCP_CHECK_HIP(hipMemsetAsync(ws, 0, p.zero_bytes, stream));
-  const dim3 subs_grid((unsigned)((max_subs + kThreads - 1) / kThreads), (unsigned)n);
-  for (int launch = 1; launch <= max_rounds; ++launch)
-    hipLaunchKernelGGL(jpeg_relax_kernel, subs_grid, dim3(kThreads), 0, stream, desc, segs, data, g, launch, p.slots, p.counts);
-  hipLaunchKernelGGL(jpeg_scan_kernel, dim3((unsigned)n), dim3(kThreads), 0, stream, desc, g, max_rounds, p.slots, p.counts, p.totals, status);
-  hipLaunchKernelGGL(jpeg_write_kernel, subs_grid, dim3(kThreads), 0, stream, desc, segs, data, g, p.slots, p.counts, p.totals, p.coef, p.dc,
-                     status);
-  hipLaunchKernelGGL(jpeg_dc_kernel, dim3(mode == SCPOSE_JPEG_GRAY ? 1u : 3u, (unsigned)n), dim3(kThreads), 0, stream, g, p.dc);
+  if (int32_t rc = launch_entropy_passes(g, p, desc, segs, data, max_rounds, status, ws, stream)) return rc;
   hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((g.n_blocks + kThreads - 1) / kThreads), (unsigned)n), dim3(kThreads), 0, stream, desc, g,
                      p.coef, p.dc, p.plane_y, p.plane_c);
   hipLaunchKernelGGL(jpeg_output_kernel, dim3((unsigned)((w + 255) / 256), (unsigned)((h + 3) / 4), (unsigned)n), dim3(kThreads), 0, stream, g, bgr,
                      p.plane_y, p.plane_c, out, y_out);
+  SCP_CHECK_HIP(hipGetLastError());
+  return SCPOSE_OK;
+}
+
+int32_t jpeg_decode_crop_launch(const uint8_t* desc, const int32_t* segs, int64_t n_rows, const uint8_t* data, int64_t n_bytes, int n, int h,
+                                int w, int mode, int max_subs, int bgr, int max_rounds, const double* minv, const int32_t* roi_host,
+                                int out_h, int out_w, uint8_t* crops, int32_t* status, uint8_t* ws, hipStream_t stream) {
+  const Geo g = make_geo(n, h, w, mode, max_subs, n_bytes, n_rows);
+  const Plan p = make_plan(g, ws);
+  if (int32_t rc = launch_entropy_passes(g, p, desc, segs, data, max_rounds, status, ws, stream)) return rc;
+  const int64_t crop_groups = ((int64_t)out_h * out_w + kThreads - 1) / kThreads;
+  for (int img0 = 0; img0 < n; img0 += kRoiChunk) {
+    const int count = n - img0 < kRoiChunk ? n - img0 : kRoiChunk;
+    RoiChunk rois{};
+    for (int k = 0; k < count * 4; ++k) rois.v[k / 4][k % 4] = roi_host[(size_t)img0 * 4 + k];
+    hipLaunchKernelGGL(jpeg_idct_window_kernel, dim3((unsigned)((g.n_blocks + kThreads - 1) / kThreads), (unsigned)count), dim3(kThreads), 0,
+                       stream, desc, g, p.coef, p.dc, p.plane_y, p.plane_c, rois, img0);
+    hipLaunchKernelGGL(jpeg_crop_kernel, dim3((unsigned)(crop_groups < 4096 ? crop_groups : 4096), (unsigned)count), dim3(kThreads), 0, stream, g,
+                       bgr, p.plane_y, p.plane_c, minv, rois, img0, out_h, out_w, crops);
+  }
   SCP_CHECK_HIP(hipGetLastError());
   return SCPOSE_OK;
 }

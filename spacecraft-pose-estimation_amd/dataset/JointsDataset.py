@@ -8,7 +8,9 @@ Image decoding uses PIL (cv2 is not available on this image).  The crop warp is 
 restatement of cv2.warpAffine(INTER_LINEAR) (utils/transforms.py; default, the reference's data flow)
 or, with ``device_crop = True``, the HIP kernel scpose_crop_warp: then
 __getitem__ returns the whole frame and its affine, ``collate_device_crop`` keeps the frames of a batch
-as a list, and ``validate`` warps + normalises the batch on the GPU (bit-identical crops).
+as a list, and ``validate`` warps + normalises the batch on the GPU (bit-identical crops).  With ``device_decode = True`` as
+well, a baseline JPEG is not decoded here at all: __getitem__ returns the file's bytes and ``validate`` hands them to
+ops.decode_crop (same crops again); any other file takes the device_crop path, row by row.
 """
 import copy
 import logging
@@ -60,6 +62,8 @@ class JointsDataset(Dataset):
         self.transform = transform
         self.numpy_transform = numpy_transform
         self.device_crop = False   # True: hand whole frames to the GPU crop kernel instead of warping here
+        # True (needs device_crop): hand the bytes of baseline JPEG files to the GPU decoder instead of decoding here
+        self.device_decode = bool(getattr(cfg.DATASET, "DEVICE_DECODE", False))
         self.want_target = True    # False: skip generate_target (the maps feed only the loss / PCK that validate() logs)
         self.db = []
 
@@ -99,25 +103,32 @@ class JointsDataset(Dataset):
         image_file = db_rec["image"]
         if self.data_format == "zip":
             raise ValueError("DATA_FORMAT 'zip' is not supported (unused by the shipped configs)")
-        data_numpy = _imread(image_file, bool(self.color_rgb))      # BGR as cv2.imread gives it, or RGB when COLOR_RGB (:149-150)
-        if data_numpy is None:
-            logger.error("=> fail to read {}".format(image_file))
-            raise ValueError("Fail to read {}".format(image_file))
+        raw = self._read_compressed(image_file) if self.device_decode else None
+        if raw is None:
+            data_numpy = _imread(image_file, bool(self.color_rgb))      # BGR as cv2.imread gives it, or RGB when COLOR_RGB (:149-150)
+            if data_numpy is None:
+                logger.error("=> fail to read {}".format(image_file))
+                raise ValueError("Fail to read {}".format(image_file))
+            if self.numpy_transform:
+                data_numpy = self.numpy_transform(data_numpy)
+            fh, fw = int(data_numpy.shape[0]), int(data_numpy.shape[1])
+        else:
+            raw, fh, fw = raw
         joints = db_rec["joints_3d"]
         joints_vis = db_rec["joints_3d_vis"]
         c, s = db_rec["center"], db_rec["scale"]
         score = db_rec["score"] if "score" in db_rec else 1
         r = 0
-        if self.numpy_transform:
-            data_numpy = self.numpy_transform(data_numpy)
         trans = get_affine_transform(c, s, r, self.image_size)
         if self.device_crop:
             # only the window of the frame the warp can read travels (worker -> main process -> device): [x0, y0, w, h] in meta["roi"]
             from ..ops import warp_window
-            fh, fw = int(data_numpy.shape[0]), int(data_numpy.shape[1])
             roi = warp_window(trans, (int(self.image_size[0]), int(self.image_size[1])), (fh, fw))
-            win = np.ascontiguousarray(data_numpy[roi[1]:roi[1] + roi[3], roi[0]:roi[0] + roi[2]])
-            input = torch.from_numpy(win if win.flags.writeable else win.copy())   # uint8, final channel order (the decoder's array is read-only)
+            if raw is not None:
+                input = torch.frombuffer(bytearray(raw), dtype=torch.uint8)      # the file, still compressed: is_compressed() below
+            else:
+                win = np.ascontiguousarray(data_numpy[roi[1]:roi[1] + roi[3], roi[0]:roi[0] + roi[2]])
+                input = torch.from_numpy(win if win.flags.writeable else win.copy())   # uint8, final channel order (the decoder's array is read-only)
         else:
             input = warp_affine_bilinear(np.ascontiguousarray(data_numpy), trans, (int(self.image_size[0]), int(self.image_size[1])))
             if self.transform:
@@ -138,19 +149,55 @@ class JointsDataset(Dataset):
             meta["frame_hw"] = np.asarray([fh, fw], dtype=np.int32)
         return input, torch.from_numpy(target), torch.from_numpy(target_weight), meta
 
+    def _read_compressed(self, image_file):
+        """device_decode: (the file's bytes, frame height, frame width) when the device decodes it (jpeg_read.parse_jpeg accepts it:
+        a baseline JPEG), None when the file goes the way of device_crop (PIL here, the window travels)."""
+        from ..jpeg_read import JpegError, parse_jpeg
+        if not self.device_crop:
+            raise ValueError("device_decode needs device_crop: the device decodes a frame straight into its crop")
+        if self.numpy_transform:
+            raise ValueError("device_decode cannot be combined with numpy_transform: a host transform needs the decoded pixels")
+        try:
+            with open(image_file, "rb") as fh:
+                raw = fh.read()
+            head = parse_jpeg(raw)
+        except (OSError, JpegError):
+            return None
+        return raw, int(head.height), int(head.width)
+
+    @staticmethod
+    def is_compressed(input):
+        """What __getitem__ returned under device_crop: a file's bytes (uint8, one dimension; device_decode) or a frame window (H x W x 3)."""
+        return input.dim() == 1
+
     @staticmethod
     def collate_device_crop(batch):
         """DataLoader collate_fn for device_crop: the frame windows (sizes differ) are packed into one flat tensor + offsets + sizes
-        (ops.pack_frames: one object through the worker -> main-process queue instead of one per frame), the rest is default-collated."""
+        (ops.pack_frames: one object through the worker -> main-process queue instead of one per frame), the rest is default-collated.
+        With device_decode a batch that holds compressed files comes out as {"files": their bytes back to back, "file_offsets":
+        int64, one entry more than files, "file_rows": the batch row of each} and, only when some rows are frame windows (files the
+        device does not decode), pack_frames' three fields for those plus "window_rows"; a batch without a compressed file is the
+        plain form."""
         from torch.utils.data import default_collate
         from ..ops import pack_frames
-        frames = pack_frames([b[0] for b in batch])
+        inputs = [b[0] for b in batch]
+        files = [i for i, t in enumerate(inputs) if JointsDataset.is_compressed(t)]
+        if files:
+            windows = [i for i in range(len(inputs)) if i not in files]
+            sizes = [int(inputs[i].numel()) for i in files]
+            frames = {"files": torch.cat([inputs[i] for i in files]), "file_offsets": torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int64),
+                      "file_rows": torch.tensor(files, dtype=torch.int64)}
+            if windows:
+                frames.update(pack_frames([inputs[i] for i in windows]), window_rows=torch.tensor(windows, dtype=torch.int64))
+        else:
+            frames = pack_frames(inputs)
         rest = default_collate([(b[1], b[2], b[3]) for b in batch])
         return frames, rest[0], rest[1], rest[2]
 
     @staticmethod
     def collate_device_crop_packed(batch):
-        """collate_device_crop for the trip worker -> main process: TWO tensors per batch instead of fifteen.  Every tensor of a batch is
+        """collate_device_crop for the trip worker -> main process: TWO tensors per batch instead of fifteen (three when a device_decode
+        batch holds rows that fell back: the files, the windows, the blob).  Every tensor of a batch is
         its own shared-memory segment whose descriptor reaches the main process over an authenticated connection of its own
         (multiprocessing.resource_sharer): 0.7 ms each, 11 ms per batch of the reference's 16 frames, all in the one thread that feeds the
         GPU -- at 32 workers that thread, not JPEG decoding, set the pace (1 265 against 1 536 frames/s at loader batch 256, round 6).  Here
@@ -168,7 +215,10 @@ class JointsDataset(Dataset):
                 chunks.append(torch.zeros(pad, dtype=torch.uint8)); off += pad
             layout.append((path, str(t.dtype).replace("torch.", ""), tuple(t.shape), off, int(raw.numel())))
             chunks.append(raw); off += int(raw.numel())
-        put(("frames", "offsets"), frames["offsets"]); put(("frames", "hw"), frames["hw"])
+        big = [k for k in frames if k in JointsDataset._BIG]      # the bytes of the batch: tensors of their own, everything else joins the blob
+        for k in frames:
+            if k not in big:
+                put(("frames", k), frames[k])
         put(("target",), target); put(("weight",), weight)
         plain = {}
         for k, v in meta.items():
@@ -176,14 +226,16 @@ class JointsDataset(Dataset):
                 put(("meta", k), v)
             else:
                 plain[k] = v          # lists of strings / numbers: pickled inline
-        return {"flat": frames["flat"], "blob": torch.cat(chunks) if chunks else torch.zeros(0, dtype=torch.uint8), "layout": layout, "plain": plain}
+        return dict({k: frames[k] for k in big}, blob=torch.cat(chunks) if chunks else torch.zeros(0, dtype=torch.uint8), layout=layout, plain=plain)
+
+    _BIG = ("flat", "files")
 
     @staticmethod
     def unpack_device_crop_batch(packed):
         """The (frames, target, target_weight, meta) tuple collate_device_crop builds, from collate_device_crop_packed's dict: the tensors
         are views of the blob (no copy; pinned when the loader pinned the blob)."""
         blob = packed["blob"]
-        frames, meta, out = {"flat": packed["flat"]}, dict(packed["plain"]), {}
+        frames, meta, out = {k: packed[k] for k in JointsDataset._BIG if k in packed}, dict(packed["plain"]), {}
         for path, dt, shape, off, nbytes in packed["layout"]:
             t = blob[off:off + nbytes].view(getattr(torch, dt)).reshape(shape) if nbytes else torch.zeros(shape, dtype=getattr(torch, dt))
             if path[0] == "frames":

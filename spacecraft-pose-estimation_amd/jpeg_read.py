@@ -4,7 +4,8 @@ parse_jpeg(data) walks the markers of a baseline JPEG file with NumPy / bytes on
 sampling, the quantisation tables in natural order, the Huffman tables as libjpeg's bits[17] / huffval[256], the restart interval,
 the byte range of the entropy-coded data and the byte ranges of its restart segments.  Everything the device does not decode is
 refused by name with UnsupportedJpeg -- never a wrong picture.  descriptor(header) packs what the kernels read into DESC_BYTES
-bytes, pack_batch(headers, files) builds the three uploads of one scpose_jpeg_decode call.
+bytes, pack_batch(headers, files) builds the three uploads of one scpose_jpeg_decode call.  sample_span / idct_window state which
+samples and blocks of a frame scpose_jpeg_decode_crop needs for a window of it.
 
 Layout of a descriptor (little endian; include/scpose.h repeats it):
     int32 [16]   file_off lo, file_off hi (offset of the file in the concatenated bytes), seg_row0 (first row of the image in the
@@ -265,6 +266,31 @@ def parse_jpeg(data):
     h.seg_sub0 = np.concatenate([[0], np.cumsum(subs)]).astype(np.int64)
     h.nsub = int(h.seg_sub0[-1])
     return h
+
+
+def sample_span(p0, length, full, half):
+    """(lo, hi), inclusive: the samples of one axis of a component's plane that the pixels [p0, p0 + length) of that axis read;
+    hi < lo when there are none.  half False -- luma, and chroma at 4:4:4: the pixel's own sample.  half True -- chroma at 4:2:0:
+    libjpeg's fancy h2v2 upsampling takes sample p >> 1 and its neighbour on one side or the other, never one outside the plane of
+    ceil(full / 2) samples, so one sample more on each side, clamped at the plane's edge.  csrc/jpeg_decode.hip: sample_span."""
+    if length <= 0:
+        return 0, -1
+    if not half:
+        return p0, p0 + length - 1
+    return max((p0 >> 1) - 1, 0), min(((p0 + length - 1) >> 1) + 1, (full + 1) // 2 - 1)
+
+
+def idct_window(h, roi):
+    """Per component of JpegHeader h the blocks (bx0, bx1, by0, by1), inclusive and in the component's own plane, whose inverse
+    DCT scpose_jpeg_decode_crop runs for the window roi = [x0, y0, w, h] of the frame: those that hold a sample of sample_span.
+    None for a component (every component) when the window is empty."""
+    x0, y0, rw, rh = (int(v) for v in roi)
+    out = []
+    for c in range(h.ncomp):
+        half = c > 0 and h.mode == "420"
+        sx, sy = sample_span(x0, rw, h.width, half), sample_span(y0, rh, h.height, half)
+        out.append(None if sx[1] < sx[0] or sy[1] < sy[0] else (sx[0] >> 3, sx[1] >> 3, sy[0] >> 3, sy[1] >> 3))
+    return out
 
 
 def descriptor(h, file_off=0, seg_row0=0):

@@ -524,8 +524,9 @@ def _jpeg_workspace(dev, nbytes):
     return ws
 
 
-def _jpeg_decode_group(headers, files, rgb, max_rounds, dev, out=None, y_out=None):
-    """One scpose_jpeg_decode call on the current stream for images of one geometry; -> (frames, status list)."""
+def _jpeg_decode_group(headers, files, rgb, max_rounds, dev, out=None, y_out=None, crop=None):
+    """One device call on the current stream for images of one geometry; -> (frames, status list): scpose_jpeg_decode, or with
+    crop = (minv float64 (n, 6), roi int32 (n, 4), out_h, out_w) scpose_jpeg_decode_crop -> (crops, status list)."""
     from . import jpeg_read as jr
     h, w, mode = headers[0].geometry
     n = len(headers)
@@ -536,13 +537,21 @@ def _jpeg_decode_group(headers, files, rgb, max_rounds, dev, out=None, y_out=Non
         d_desc = torch.from_numpy(desc).to(dev, non_blocking=True)
         d_rows = torch.from_numpy(rows).to(dev, non_blocking=True)
         d_data = torch.from_numpy(data).to(dev, non_blocking=True)
-        if out is None:
-            out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
         status = torch.empty(n, dtype=torch.int32, device=dev)
         work = _jpeg_workspace(dev, ws)
-        nat.check(lib.scpose_jpeg_decode(_ptr(d_desc), _ptr(d_rows), int(rows.shape[0]), _ptr(d_data), int(data.size), n, h, w,
-                                         jr.MODES[mode], int(max_subs), 0 if rgb else 1, int(max_rounds), _ptr(out), _ptr(y_out),
-                                         _ptr(status), _ptr(work), ws, _stream()), "jpeg_decode")
+        front = (_ptr(d_desc), _ptr(d_rows), int(rows.shape[0]), _ptr(d_data), int(data.size), n, h, w, jr.MODES[mode], int(max_subs),
+                 0 if rgb else 1, int(max_rounds))
+        if crop is None:
+            if out is None:
+                out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+            nat.check(lib.scpose_jpeg_decode(*front, _ptr(out), _ptr(y_out), _ptr(status), _ptr(work), ws, _stream()), "jpeg_decode")
+        else:
+            minv, roi, oh, ow = crop
+            d_minv = torch.from_numpy(np.ascontiguousarray(minv, dtype=np.float64)).to(dev, non_blocking=True)
+            roi = np.ascontiguousarray(roi, dtype=np.int32)      # host memory: read before the call returns
+            out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=dev)
+            nat.check(lib.scpose_jpeg_decode_crop(*front, _ptr(d_minv), c_void_p(roi.ctypes.data), oh, ow, _ptr(out), _ptr(status),
+                                                  _ptr(work), ws, _stream()), "jpeg_decode_crop")
         return out, status.tolist()
 
 
@@ -558,20 +567,17 @@ def _jpeg_host_decode(data, rgb):
     return arr if rgb else arr[:, :, ::-1].copy()
 
 
-def decode_jpeg(files, rgb=True, device=None, max_rounds=None, fallback=True):
-    """Baseline JPEG files -> ((N, H, W, 3) uint8 frames on the device, info), decoded by csrc/jpeg_decode.hip bit for bit as
-    libjpeg (PIL, cv2.imread) decodes them.  files: a list of bytes or of paths; all frames must have one size.  rgb: R, G, B
-    order, else B, G, R (what cv2.imread returns).  Files are grouped by (height, width, sampling) and every group is one call.
-    info = {"rounds": per image the relaxation rounds used (0: not decoded on the device), "fallback": {index: reason}}.
-    A file jpeg_read.parse_jpeg refuses, or one whose entry states have not converged after max_rounds launches, is decoded by PIL
-    on the host when `fallback`, else raises UnsupportedJpeg / JpegError.  A corrupt or truncated stream always raises JpegError."""
-    from . import jpeg_read as jr
+def _jpeg_device(device, who):
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     if dev.type != "cuda":
-        raise nat.NativeError("decode_jpeg needs a ROCm device (got %s); there is no CPU path" % dev)
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    rounds_cap = JPEG_MAX_ROUNDS if max_rounds is None else int(max_rounds)
+        raise nat.NativeError("%s needs a ROCm device (got %s); there is no CPU path" % (who, dev))
+    return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def _jpeg_parse(files, fallback, who, key):
+    """files (bytes, uint8 arrays / tensors or paths) -> (blobs, headers, host, groups): the bytes of each file, its JpegHeader or
+    None, {index: reason} for the files jpeg_read.parse_jpeg refuses, and {key(header): [indices]}, one device call each."""
+    from . import jpeg_read as jr
     blobs = []
     for f in files:
         if isinstance(f, (bytes, bytearray, memoryview)):
@@ -583,34 +589,53 @@ def decode_jpeg(files, rgb=True, device=None, max_rounds=None, fallback=True):
         else:
             with open(f, "rb") as fh:
                 blobs.append(fh.read())
-    n = len(blobs)
-    if n == 0:
-        raise ValueError("decode_jpeg: no files")
-    headers, host, groups = [None] * n, {}, {}
+    if not blobs:
+        raise ValueError("%s: no files" % who)
+    headers, host, groups = [None] * len(blobs), {}, {}
     for i, b in enumerate(blobs):
         try:
             headers[i] = jr.parse_jpeg(b)
-            groups.setdefault(headers[i].geometry, []).append(i)
+            groups.setdefault(key(headers[i]), []).append(i)
         except jr.UnsupportedJpeg as e:
             if not fallback:
                 raise
             host[i] = str(e)
+    return blobs, headers, host, groups
+
+
+def _jpeg_status(who, i, st, rounds_cap, fallback, host):
+    """One image's status word: raises for a corrupt stream; a stream that has not converged goes to `host` (or raises); -> decoded on the device"""
+    from . import jpeg_read as jr
+    # not converged: the walk started from entries that are not the stream's, so CORRUPT says nothing; the host decides
+    if st & nat.JPEG_CORRUPT and not st & nat.JPEG_NOT_CONVERGED:
+        raise jr.JpegError("%s: file %d: corrupt or truncated entropy-coded data" % (who, i))
+    if st & nat.JPEG_NOT_CONVERGED:
+        reason = "entry states not converged after %d rounds" % rounds_cap
+        if not fallback:
+            raise jr.JpegError("%s: file %d: %s" % (who, i, reason))
+        host[i] = reason
+        return False
+    return True
+
+
+def decode_jpeg(files, rgb=True, device=None, max_rounds=None, fallback=True):
+    """Baseline JPEG files -> ((N, H, W, 3) uint8 frames on the device, info), decoded by csrc/jpeg_decode.hip bit for bit as
+    libjpeg (PIL, cv2.imread) decodes them.  files: a list of bytes or of paths; all frames must have one size.  rgb: R, G, B
+    order, else B, G, R (what cv2.imread returns).  Files are grouped by (height, width, sampling) and every group is one call.
+    info = {"rounds": per image the relaxation rounds used (0: not decoded on the device), "fallback": {index: reason}}.
+    A file jpeg_read.parse_jpeg refuses, or one whose entry states have not converged after max_rounds launches, is decoded by PIL
+    on the host when `fallback`, else raises UnsupportedJpeg / JpegError.  A corrupt or truncated stream always raises JpegError."""
+    from . import jpeg_read as jr
+    dev, rounds_cap = _jpeg_device(device, "decode_jpeg"), JPEG_MAX_ROUNDS if max_rounds is None else int(max_rounds)
+    blobs, headers, host, groups = _jpeg_parse(files, fallback, "decode_jpeg", lambda h: h.geometry)
+    n = len(blobs)
     rounds = [0] * n
     decoded = {}                    # index -> (group tensor, row)
     for geom, idx in groups.items():
         frames, status = _jpeg_decode_group([headers[i] for i in idx], [blobs[i] for i in idx], rgb, rounds_cap, dev)
         for row, i in enumerate(idx):
-            st = status[row]
-            rounds[i] = (st >> 8) & 255
-            # not converged: the walk started from entries that are not the stream's, so CORRUPT says nothing; the host decides
-            if st & nat.JPEG_CORRUPT and not st & nat.JPEG_NOT_CONVERGED:
-                raise jr.JpegError("decode_jpeg: file %d: corrupt or truncated entropy-coded data" % i)
-            if st & nat.JPEG_NOT_CONVERGED:
-                reason = "entry states not converged after %d rounds" % rounds_cap
-                if not fallback:
-                    raise jr.JpegError("decode_jpeg: file %d: %s" % (i, reason))
-                host[i] = reason
-            else:
+            rounds[i] = (status[row] >> 8) & 255
+            if _jpeg_status("decode_jpeg", i, status[row], rounds_cap, fallback, host):
                 decoded[i] = (frames, row)
     host_px = {i: _jpeg_host_decode(blobs[i], rgb) for i in host}
     sizes = {(h.height, h.width) for i, h in enumerate(headers) if i in decoded} | {a.shape[:2] for a in host_px.values()}
@@ -626,6 +651,44 @@ def decode_jpeg(files, rgb=True, device=None, max_rounds=None, fallback=True):
             out[i].copy_(frames[row])
         for i, arr in host_px.items():
             out[i].copy_(torch.from_numpy(np.ascontiguousarray(arr)))
+    return out, info
+
+
+def decode_crop(files, trans, out_wh, rgb=True, device=None, max_rounds=None, fallback=True):
+    """Image files -> ((N, H, W, 3) uint8 network crops on the device, info): row i is crop_warp(frame_i, trans[i], out_wh) of the frame
+    PIL decodes from files[i] -- for a baseline JPEG, of decode_jpeg's frame -- bit for bit, without that frame: after the entropy
+    decoding csrc/jpeg_decode.hip transforms only the blocks the warp's window (warp_window) can read and samples the planes.
+    files as for decode_jpeg (frame sizes may differ); trans (N, 2, 3) as for crop_warp; out_wh = (W, H); rgb: the channel order.
+    info as decode_jpeg's.  A file jpeg_read.parse_jpeg refuses (PNG, progressive JPEG, ...) and one whose entry states have not
+    converged is decoded by PIL on the host when `fallback` and its row filled by crop_warp; a corrupt stream raises JpegError."""
+    from .utils.transforms import invert_affine_cv
+    dev, rounds_cap = _jpeg_device(device, "decode_crop"), JPEG_MAX_ROUNDS if max_rounds is None else int(max_rounds)
+    blobs, headers, host, groups = _jpeg_parse(files, fallback, "decode_crop", lambda h: h.geometry)
+    n = len(blobs)
+    trans = np.asarray(trans, dtype=np.float64).reshape(n, 2, 3)
+    ow, oh = int(out_wh[0]), int(out_wh[1])
+    rounds, parts = [0] * n, []            # parts: (row indices, crops of those rows)
+    for geom, idx in groups.items():
+        minv = np.stack([np.asarray(invert_affine_cv(trans[i]), dtype=np.float64).reshape(6) for i in idx])
+        roi = np.array([warp_window(trans[i], (ow, oh), geom[:2]) for i in idx], dtype=np.int32)
+        crops, status = _jpeg_decode_group([headers[i] for i in idx], [blobs[i] for i in idx], rgb, rounds_cap, dev, crop=(minv, roi, oh, ow))
+        for row, i in enumerate(idx):
+            rounds[i] = (status[row] >> 8) & 255
+        keep = [row for row, i in enumerate(idx) if _jpeg_status("decode_crop", i, status[row], rounds_cap, fallback, host)]
+        if len(keep) < len(idx):
+            crops, idx = crops[torch.tensor(keep, dtype=torch.int64, device=dev)], [idx[row] for row in keep]
+        if idx:
+            parts.append((idx, crops))
+    if host:
+        idx = sorted(host)
+        parts.append((idx, crop_warp([_jpeg_host_decode(blobs[i], rgb) for i in idx], trans[idx], (ow, oh), device=dev)))
+    info = {"rounds": rounds, "fallback": host}
+    if len(parts) == 1 and parts[0][0] == list(range(n)):
+        return parts[0][1], info
+    with torch.cuda.device(dev):
+        out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=dev)
+        for idx, crops in parts:
+            out.index_copy_(0, torch.tensor(idx, dtype=torch.int64, device=dev), crops)
     return out, info
 
 

@@ -1,0 +1,127 @@
+"""ops.decode_crop (csrc/jpeg_decode.hip: jpeg_idct_window_kernel, jpeg_crop_kernel) on the device: every row equals the existing
+ops.crop_warp of the frame PIL decodes, and the NumPy restatement of the warp, bit for bit."""
+import io
+from importlib import import_module
+
+import numpy as np
+import pytest
+import torch
+
+import jpeg_crop_cases as C
+import jpeg_decode_restated as R
+import jpeg_stream_families as F
+
+pytestmark = pytest.mark.gpu
+J = R.J
+T = import_module("spacecraft-pose-estimation_amd.utils.transforms")
+
+
+def reference(ops, frames, trans):
+    """(ops.crop_warp of the frames, warp_affine_bilinear of the frames): the two things a row of decode_crop must equal"""
+    dev = ops.crop_warp([np.ascontiguousarray(f) for f in frames], trans, C.CROP_WH)
+    host = np.stack([T.warp_affine_bilinear(np.ascontiguousarray(f), t, C.CROP_WH) for f, t in zip(frames, trans)])
+    assert np.array_equal(dev.cpu().numpy(), host)
+    return dev
+
+
+@pytest.mark.parametrize("mode", C.MODES)
+@pytest.mark.parametrize("size", C.SIZES, ids=lambda s: "%dx%d" % (s[1], s[0]))
+def test_crop_equals_crop_warp_of_the_pil_frame(gpu_ops, mode, size):
+    data, frame = C.frame(mode, size)
+    cases = C.affines(size)
+    trans = np.stack(list(cases.values()))
+    got, info = gpu_ops.decode_crop([data] * len(cases), trans, C.CROP_WH, fallback=False)
+    assert got.dtype == torch.uint8 and tuple(got.shape) == (len(cases), C.CROP_WH[1], C.CROP_WH[0], 3) and got.is_cuda
+    want = reference(gpu_ops, [frame] * len(cases), trans)
+    bad = [name for i, name in enumerate(cases) if not torch.equal(got[i], want[i])]
+    assert not bad, bad
+    assert not info["fallback"] and info["rounds"] == [R.relax(R.Stream(data))[1]] * len(cases)
+    k = list(cases).index("outside")
+    assert not bool(got[k].any()) and all(bool(got[i].any()) for i in range(len(cases)) if i != k)
+    bgr, _ = gpu_ops.decode_crop([data] * len(cases), trans, C.CROP_WH, rgb=False, fallback=False)
+    assert torch.equal(bgr, reference(gpu_ops, [frame[:, :, ::-1]] * len(cases), trans)) and torch.equal(bgr, got.flip(3))
+    # the frame decode_jpeg returns is that frame too
+    full, _ = gpu_ops.decode_jpeg([data], fallback=False)
+    assert torch.equal(gpu_ops.crop_warp([full[0].cpu().numpy()] * len(cases), trans, C.CROP_WH), got)
+
+
+def mixed_batch():
+    files, frames, trans = [], [], []
+    for k, (mode, size) in enumerate((m, s) for s in C.SIZES for m in C.MODES):
+        data, frame = C.frame(mode, size, seed=k)
+        t = list(C.affines(size).values())
+        files += [data, data]; frames += [frame, frame]; trans += [t[k % 4], t[(k + 1) % 4]]
+    return files, frames, np.stack(trans)
+
+
+def test_all_modes_and_sizes_in_one_call(gpu_ops):
+    files, frames, trans = mixed_batch()
+    assert len({J.parse_jpeg(f).geometry for f in files}) == 6
+    got, info = gpu_ops.decode_crop(files, trans, C.CROP_WH, fallback=False)
+    assert torch.equal(got, reference(gpu_ops, frames, trans)) and not info["fallback"] and min(info["rounds"]) >= 1
+
+
+def test_refused_files_fall_back_row_by_row(gpu_ops):
+    from PIL import Image
+    size = C.SIZES[0]
+    rgb = R.content("noise", size[0], size[1], 3, seed=5)
+    prog, png = io.BytesIO(), io.BytesIO()
+    Image.fromarray(rgb, "RGB").save(prog, "JPEG", quality=90, progressive=True)
+    Image.fromarray(rgb, "RGB").save(png, "PNG")
+    files = [C.frame("420", size)[0], prog.getvalue(), png.getvalue(), C.frame("gray", size)[0]]
+    frames = [R.pil_decode(f) for f in files]
+    assert np.array_equal(frames[2], rgb)
+    trans = np.stack(list(C.affines(size).values())[:4])
+    got, info = gpu_ops.decode_crop(files, trans, C.CROP_WH)
+    assert sorted(info["fallback"]) == [1, 2] and "progressive" in info["fallback"][1] and "not a JPEG" in info["fallback"][2]
+    assert info["rounds"][1] == info["rounds"][2] == 0 and info["rounds"][0] >= 1 and info["rounds"][3] >= 1
+    assert torch.equal(got, reference(gpu_ops, frames, trans))
+    with pytest.raises(J.UnsupportedJpeg, match="progressive"):
+        gpu_ops.decode_crop(files, trans, C.CROP_WH, fallback=False)
+    only, info = gpu_ops.decode_crop(files[1:3], trans[1:3], C.CROP_WH)                     # nothing for the device at all
+    assert torch.equal(only, got[1:3]) and sorted(info["fallback"]) == [0, 1]
+
+
+def test_restart_intervals_and_written_tables(gpu_ops):
+    cases = [c for c in F.family_a() if c.name.endswith(("ri1", "ri3"))]
+    assert len(cases) == 6 and all(c.stream.h.restart_interval > 0 for c in cases)
+    m = lambda a, x0, y0: np.array([[a, 0.0, -a * x0], [0.0, a, -a * y0]])
+    trans = np.stack([m(1.0, -3.4, -5.7), m(0.5, -9.1, -6.2), m(2.5, 4.3, 2.2)] * 2)
+    got, info = gpu_ops.decode_crop([c.data for c in cases], trans, C.CROP_WH, fallback=False)
+    assert torch.equal(got, reference(gpu_ops, [c.pil for c in cases], trans))
+
+
+def test_max_rounds_1_goes_to_the_fallback_with_an_equal_row(gpu_ops):
+    data, easy = R.fixture("gray", 48, 40, 95, "noise"), R.fixture("gray", 48, 40, 75, "const")
+    assert R.relax(R.Stream(data), max_rounds=1)[2] is False and R.relax(R.Stream(easy))[1] == 1
+    trans = np.stack(list(C.affines((48, 40)).values())[:2])
+    got, info = gpu_ops.decode_crop([easy, data], trans, C.CROP_WH, max_rounds=1)
+    assert list(info["fallback"]) == [1] and "not converged" in info["fallback"][1] and info["rounds"] == [1, 1]
+    assert torch.equal(got, reference(gpu_ops, [R.pil_decode(easy), R.pil_decode(data)], trans))
+    with pytest.raises(J.JpegError, match="not converged"):
+        gpu_ops.decode_crop([easy, data], trans, C.CROP_WH, max_rounds=1, fallback=False)
+
+
+def test_no_skipped_sample_is_read(gpu_ops):
+    """the planes outside the IDCT window are never written: whatever the workspace held before, the crops are the same"""
+    files, frames, trans = mixed_batch()
+    dev = torch.cuda.current_device()
+    first, _ = gpu_ops.decode_crop(files, trans, C.CROP_WH, fallback=False)                   # sizes the cached workspace
+    got = []
+    for fill in (0x00, 0xFF):
+        gpu_ops._JPEG_WORKSPACE[dev].fill_(fill)
+        got.append(gpu_ops.decode_crop(files, trans, C.CROP_WH, fallback=False)[0])
+    assert torch.equal(got[0], got[1]) and torch.equal(got[0], first) and torch.equal(first, reference(gpu_ops, frames, trans))
+
+
+def test_batch_of_one_no_files_and_a_corrupt_stream(gpu_ops):
+    data, frame = C.frame("420", C.SIZES[1])
+    trans = C.affines(C.SIZES[1])["down_3"][None]
+    got, info = gpu_ops.decode_crop([data], trans, C.CROP_WH, fallback=False)
+    assert tuple(got.shape) == (1, 24, 32, 3) and torch.equal(got, reference(gpu_ops, [frame], trans)) and len(info["rounds"]) == 1
+    with pytest.raises(ValueError, match="no files"):
+        gpu_ops.decode_crop([], np.zeros((0, 2, 3)), C.CROP_WH)
+    h = J.parse_jpeg(data)
+    cut = data[:h.data_start + (h.data_end - h.data_start) // 2] + b"\xff\xd9"
+    with pytest.raises(J.JpegError, match="corrupt"):
+        gpu_ops.decode_crop([data, cut], np.repeat(trans, 2, 0), C.CROP_WH)
