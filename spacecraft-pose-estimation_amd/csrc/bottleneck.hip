@@ -526,13 +526,13 @@ static int32_t bneck_launch_one(const BneckLaunch& L, hipStream_t stream) {
 int32_t bottleneck_launch(const void* in, const void* w1, const void* w2, const void* w3, const float* bias, int N, int H, int W,
                           int cin, int dtype, void* out, uint32_t* sched, hipStream_t stream) {
   SCP_REQUIRE(sched, "bottleneck: null tile-queue words");
-  // the kernel addresses its tensors through 32-bit buffer descriptors: batches whose 256-channel tensor reaches 4 GiB
-  // (~900 frames at 96 x 96) run as several launches over frame ranges
+  // batches whose 256-channel tensor does not fit a buffer descriptor (~900 frames at 96 x 96) run as several launches over
+  // frame ranges (common.h: buf_max_frames)
   const bool proj = cin == 64;
   SCP_REQUIRE(cin == 64 || cin == 256, "bottleneck: Cin = %d (64 or 256)", cin);
-  const size_t in_frame = (size_t)(cin / 8) * H * W * 16, out_frame = (size_t)32 * H * W * 16;
-  SCP_REQUIRE(out_frame < 0xfffffff0ull, "bottleneck: one %dx%d frame does not fit a 32-bit buffer descriptor", H, W);
-  const int max_n = (int)(0xfffffff0ull / out_frame);
+  const size_t in_frame = blocked_bytes(1, cin / 8, H, W), out_frame = blocked_bytes(1, 32, H, W);
+  SCP_REQUIRE(fits_buf(out_frame), "bottleneck: one %dx%d frame does not fit a 32-bit buffer descriptor", H, W);
+  const int max_n = buf_max_frames(out_frame);
   for (int n0 = 0; n0 < N; n0 += max_n) {
     const int n = N - n0 < max_n ? N - n0 : max_n;
     BneckLaunch L{};

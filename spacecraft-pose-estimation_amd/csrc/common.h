@@ -87,6 +87,24 @@ struct Carve {
   size_t bytes() const { return off; }
 };
 
+// ---- 32-bit buffer descriptors ---------------------------------------------------------------
+// Most kernels address their tensors through raw buffer descriptors (conv_pipe_kernel.h: make_buf): base + 32-bit offset,
+// num_records = the tensor's bytes, which must stay below kBufLimit -- the offset given to padding lanes (BUF_OOB) has to
+// lie past every tensor.  A kernel without a 64-bit path takes a batch whose tensor is larger as several launches over
+// frame ranges (bottleneck, fuse_down, fused BasicBlock): the kernel a frame runs on never depends on the batch.
+constexpr size_t kBufLimit = 0xfffffff0ull;
+inline size_t blocked_bytes(int n, int planes, int h, int w) { return (size_t)n * planes * h * w * 16; }   // [N][C/8][H][W][8] x 16 bit
+inline bool fits_buf(size_t bytes) { return bytes < kBufLimit; }
+// num_records for a kernel that also has a 64-bit path: 0 selects that path -- the tensor does not fit, or the development
+// switch SCPOSE_M32_BUF=0 asks for it (util.cpp; the one place that switch is read)
+uint32_t buf_bytes_or_64bit(size_t bytes);
+// frames per launch of a kernel that splits the batch: the largest range whose largest tensor (frame_bytes per frame, itself
+// fits_buf) fits; cap > 0 = a smaller range, with which tests force the split on a small batch (a development switch's value)
+inline int buf_max_frames(size_t frame_bytes, int cap = 0) {
+  const int max_n = (int)(kBufLimit / frame_bytes);
+  return cap > 0 && cap < max_n ? cap : max_n;
+}
+
 // ---- 3x3 / 1x1 implicit-GEMM convolution ---------------------------------------------------
 // Device-side description of one convolution launch.  All tensors are "blocked":
 // [N][C/8][H][W][8] 16-bit elements.
@@ -109,7 +127,7 @@ struct ConvLaunch {
   int32_t n_mblk;        // Cout blocks of MT
   int32_t relu;
   int32_t out_nchw_f32;
-  int32_t total_blocks;
+  int32_t store_stages;  // conv_m32p: stages that store the previous tile, when SCPOSE_NST overrides the kernel's own count; else 0
   // pipelined (persistent) variant
   const void* zero16;    // >= 16 zero bytes in global memory (source of padding pixels for LDS-DMA)
   int32_t items_total;   // (tile, Cout block) work items
@@ -120,14 +138,14 @@ struct ConvLaunch {
   int32_t nbuf_w, nbuf_x;  // LDS buffers: weights 1 (resident) or 2, inputs 2 or 3
   int32_t tiles_total;   // N * tiles_x * tiles_y
   int32_t nt;            // pixel tiles per wave group processed one after the other on one staged weight chunk
-  int32_t groups;        // wave groups (256 threads each) working on different tiles in parallel (1 or 2)
+  int32_t wreg_chunks;   // conv_m32p: K-chunks of weights held in producer registers (6 or 1)
   FastDiv fd_npix, fd_tw, fd_hp, fd_halo_w, fd_tiles_img, fd_tiles_x, fd_nmblk;   // conv_m32: divisions by launch constants
   uint32_t in_bytes, out_bytes;   // sizes of the input / output (= residual) tensors when both are < 4 GiB
                                   // (buffer-addressed global traffic, conv_pipe_kernel.h: dma16_buf), else 0 (64-bit
                                   // addressing).  conv_pipe addresses only its input that way and leaves out_bytes 0.
   unsigned long long* dbg_buf;  // development build only (SCP_DBG_BUF): per-workgroup phase cycle sums (dbg & 8), else null
   int32_t dbg;           // development build only (SCP_DBG; the shipped library's kernels read neither field): bits 1 skip MFMA loop, 2 skip epilogue, 4 skip input DMA, 8 phase stamps
-                         // bit 32 is the one bit the shipped library honours: the host prints the m32 tile choice
+                         // bit 32 is the one bit the shipped library honours: the host prints the m32 tile choice (and block_launch its frame ranges)
   int32_t cu_share;      // host only: CUs to size the layer for (0 = the whole chip)
 };
 
@@ -152,7 +170,7 @@ struct PackedConv {
   void* d_w = nullptr;     // device packed weights
   float* d_bias = nullptr; // device bias (n_mblk*mt)
   int mrep;
-  int variant = 0;     // 0: 16x16x32 MFMA kernels (conv_pipe / conv_stag), 1: 32x32x16 kernel (conv_m32)
+  int variant = 0;     // 0: 16x16x32 MFMA kernel (conv_pipe), 1: 32x32x16 kernel (conv_m32)
   int wm = 1;          // variant 1: waves along Cout (mt = 32*mrep*wm)
   // streaming 1x1 kernel (conv1x1.hip): weights [k-step][k-group][cout_pad1][8] and bias in MFMA row order, when eligible
   void* d_w1 = nullptr;
@@ -194,8 +212,8 @@ int32_t conv_launch(const PackedConv& pc, const void* in, int N, int H, int W, c
 size_t conv_lds_bytes(const PackedConv& pc, int nrep, int th, int tw);
 int plane_stride_for(int stride, int halo_h, int halo_w);
 // software-pipelined persistent kernel (conv_pipe_kernel.h); nt = pixel tiles per work item
-int32_t conv_launch_pipe(const PackedConv& pc, ConvLaunch& L, int nrep, int nt, int occ, int groups, hipStream_t stream);
-size_t conv_pipe_lds_bytes(const PackedConv& pc, int plane_stride, int groups);
+int32_t conv_launch_pipe(const PackedConv& pc, ConvLaunch& L, int nrep, int nt, int occ, hipStream_t stream);
+size_t conv_pipe_lds_bytes(const PackedConv& pc, int plane_stride);
 const void* conv_zero_page();   // lazily allocated 256 zero bytes on the current device
 // fused BasicBlock (conv_block_kernel.h): out = relu(conv2(relu(conv1(x))) + x) for C -> C -> C 3x3 layers
 bool block_fusable(const PackedConv& c1, const PackedConv& c2);

@@ -1,8 +1,9 @@
 // Host side of the fused BasicBlock kernel (conv_block_kernel.h): eligibility and launch.
+#include <stdio.h>
 #include <stdlib.h>
 #include <type_traits>
 
-#include "conv_block2_kernel.h"
+#include "conv_block_kernel.h"
 
 namespace scpose {
 
@@ -20,41 +21,41 @@ int32_t block_launch(const PackedConv& c1, const PackedConv& c2, const void* in,
                      hipStream_t stream) {
   SCP_REQUIRE(block_fusable(c1, c2), "block: the two convolutions are not a fusable BasicBlock");
   SCP_REQUIRE(N > 0 && H > 0 && W > 0, "block: bad shape N=%d H=%d W=%d", N, H, W);
-  BlockLaunch L;
-  L.in = in; L.w1 = c1.d_w; L.w2 = c2.d_w; L.b1 = c1.d_bias; L.b2 = c2.d_bias; L.out = out;
-  L.zero16 = conv_zero_page();
-  SCP_REQUIRE(L.zero16, "block: cannot allocate the zero page");
-  {
-    static const char* e = dev_env("SCPOSE_M32_BUF");
-    const size_t bytes = (size_t)N * (c1.cin / 8) * H * W * 16;
-    L.bytes = (bytes < 0xfffffff0ull && !(e && atoi(e) == 0)) ? (uint32_t)bytes : 0;
-  }
-  L.N = N; L.H = H; L.W = W;
-  L.tiles_x = (W + kBlockTile - 1) / kBlockTile;
-  L.tiles_y = (H + kBlockTile - 1) / kBlockTile;
-  L.tiles_total = N * L.tiles_x * L.tiles_y;
-  L.fd_tiles_img = make_fastdiv(L.tiles_x * L.tiles_y);
-  L.fd_tiles_x = make_fastdiv(L.tiles_x);
-  int grid = conv_device_cus();
-  if (grid > L.tiles_total) grid = L.tiles_total;
-  L.tiles_per_wg = (L.tiles_total + grid - 1) / grid;
-  L.grid = (L.tiles_total + L.tiles_per_wg - 1) / L.tiles_per_wg;
-  { static const char* e = dev_env("SCPOSE_DBG"); const int dbg = (kDevBuild && e) ? atoi(e) : 0;
-    L.dbg_buf = (dbg & 8) ? conv_dbg_buffer(stream) : nullptr;
-    if (dbg & 8) conv_dbg_set_grid(L.grid); }
+  const size_t frame = blocked_bytes(1, c1.cin / 8, H, W);
+  SCP_REQUIRE(fits_buf(frame), "block: one %dx%d frame does not fit a 32-bit buffer descriptor", H, W);
+  // batches whose tensor does not fit a buffer descriptor run as several launches over frame ranges (common.h: buf_max_frames)
+  static const char* cap = dev_env("SCPOSE_BLOCK_MAXN");   // tests: force the split on a small batch
+  const int max_n = buf_max_frames(frame, cap ? atoi(cap) : 0);
+  static const char* dbg_env = dev_env("SCPOSE_DBG");
+  const int dbg = dbg_env ? atoi(dbg_env) : 0;   // bit 32, the host's line, also in the shipped library (common.h: ConvLaunch::dbg)
   const int mrep = c1.cin / 16;
-  // second form (conv_block2_kernel.h: one layer per wave, weights in registers) unless the tensor needs 64-bit addressing
-  static const char* v1 = dev_env("SCPOSE_BLOCK_V1");
-  if (L.bytes != 0 && !(v1 && atoi(v1))) {
-    if (c1.dtype == SCPOSE_DT_BF16) return mrep == 3 ? block2_launch_one<0, 3>(L, stream) : block2_launch_one<0, 2>(L, stream);
-    return mrep == 3 ? block2_launch_one<1, 3>(L, stream) : block2_launch_one<1, 2>(L, stream);
+  for (int n0 = 0; n0 < N; n0 += max_n) {
+    const int n = N - n0 < max_n ? N - n0 : max_n;
+    if (dbg & 32) fprintf(stderr, "block %d %dx%d N=%d: frames %d..%d\n", c1.cin, H, W, N, n0, n0 + n);
+    BlockLaunch L{};
+    L.in = static_cast<const char*>(in) + (size_t)n0 * frame;
+    L.out = static_cast<char*>(out) + (size_t)n0 * frame;
+    L.w1 = c1.d_w; L.w2 = c2.d_w; L.b1 = c1.d_bias; L.b2 = c2.d_bias;
+    L.zero16 = conv_zero_page();
+    SCP_REQUIRE(L.zero16, "block: cannot allocate the zero page");
+    L.bytes = (uint32_t)((size_t)n * frame);
+    L.N = n; L.H = H; L.W = W;
+    L.tiles_x = (W + kBlockTile - 1) / kBlockTile;
+    L.tiles_y = (H + kBlockTile - 1) / kBlockTile;
+    L.tiles_total = n * L.tiles_x * L.tiles_y;
+    L.fd_tiles_img = make_fastdiv(L.tiles_x * L.tiles_y);
+    L.fd_tiles_x = make_fastdiv(L.tiles_x);
+    int grid = conv_device_cus();
+    if (grid > L.tiles_total) grid = L.tiles_total;
+    L.tiles_per_wg = (L.tiles_total + grid - 1) / grid;
+    L.grid = (L.tiles_total + L.tiles_per_wg - 1) / L.tiles_per_wg;
+    if (kDevBuild && (dbg & 8)) { L.dbg_buf = conv_dbg_buffer(stream); conv_dbg_set_grid(L.grid); }
+    int32_t rc;
+    if (c1.dtype == SCPOSE_DT_BF16) rc = mrep == 3 ? block_launch_variant<0, 3>(L, stream) : block_launch_variant<0, 2>(L, stream);
+    else rc = mrep == 3 ? block_launch_variant<1, 3>(L, stream) : block_launch_variant<1, 2>(L, stream);
+    if (rc != SCPOSE_OK) return rc;
   }
-  if (c1.dtype == SCPOSE_DT_BF16) {
-    if (mrep == 3) return block_launch_one<0, 3>(L, stream);
-    return block_launch_one<0, 2>(L, stream);
-  }
-  if (mrep == 3) return block_launch_one<1, 3>(L, stream);
-  return block_launch_one<1, 2>(L, stream);
+  return SCPOSE_OK;
 }
 
 }  // namespace scpose

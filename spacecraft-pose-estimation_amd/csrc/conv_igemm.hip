@@ -246,7 +246,7 @@ int32_t conv_launch(const PackedConv& pc, const void* in, int N, int H, int W, c
                     int relu, int out_nchw_f32, void* out, hipStream_t stream, int cu_share) {
   SCP_REQUIRE(N > 0 && H > 0 && W > 0, "conv: bad shape N=%d H=%d W=%d", N, H, W);
   SCP_REQUIRE(out_nchw_f32 || pc.cout % 8 == 0, "conv: blocked output needs Cout%%8==0 (Cout=%d)", pc.cout);
-  ConvLaunch L;
+  ConvLaunch L{};
   L.in = in; L.wpk = pc.d_w; L.bias = pc.d_bias; L.res = res; L.out = out;
   L.N = N; L.H = H; L.W = W;
   L.Ho = (H - 1) / pc.stride + 1;  // k=3,p=1 or k=1,p=0
@@ -254,8 +254,8 @@ int32_t conv_launch(const PackedConv& pc, const void* in, int N, int H, int W, c
   L.cin_planes = pc.cin / 8;
   L.cout = pc.cout;
   L.cu_share = cu_share;
-  if (pc.d_ws2 && !res && !out_nchw_f32 && (size_t)N * L.cin_planes * H * W * 16 < 0xfffffff0ull &&
-      (size_t)N * (pc.cout / 8) * L.Ho * L.Wo * 16 < 0xfffffff0ull)
+  if (pc.d_ws2 && !res && !out_nchw_f32 && fits_buf(blocked_bytes(N, L.cin_planes, H, W)) &&
+      fits_buf(blocked_bytes(N, pc.cout / 8, L.Ho, L.Wo)))
     return conv_s2r_launch(pc, in, N, H, W, relu, out, stream);
   if (pc.variant == 1) {
     SCP_REQUIRE(!out_nchw_f32, "conv m32: float32 NCHW output unsupported");
@@ -264,8 +264,8 @@ int32_t conv_launch(const PackedConv& pc, const void* in, int N, int H, int W, c
   }
   {   // 1x1 layers whose weights fit LDS: barrier-free streaming kernel (needs buffer-addressable tensors)
     static const char* e1 = dev_env("SCPOSE_K1_STREAM");
-    const size_t ib = (size_t)N * L.cin_planes * H * W * 16, ob = (size_t)N * (pc.cout / 8) * H * W * 16;
-    if (pc.d_w1 && !out_nchw_f32 && ib < 0xfffffff0ull && ob < 0xfffffff0ull && !(e1 && atoi(e1) == 0))
+    if (pc.d_w1 && !out_nchw_f32 && fits_buf(blocked_bytes(N, L.cin_planes, H, W)) && fits_buf(blocked_bytes(N, pc.cout / 8, H, W)) &&
+        !(e1 && atoi(e1) == 0))
       return conv1x1_stream_launch(pc, in, N, H, W, res, relu, out, stream);
   }
   int nrep;
@@ -283,11 +283,11 @@ int32_t conv_launch(const PackedConv& pc, const void* in, int N, int H, int W, c
   const bool resident = pc.nchunks == 1 && pc.n_mblk == 1;
   // Weight-resident layers are bound by HBM, not MFMA: prefer a tile small enough for TWO resident
   // workgroups per CU (one streams while the other computes) over a big tile with one.
-  if (resident && 2 * conv_pipe_lds_bytes(pc, L.plane_stride, 1) > 160 * 1024 && L.th % 2 == 0 && L.th * L.tw >= 128) {
+  if (resident && 2 * conv_pipe_lds_bytes(pc, L.plane_stride) > 160 * 1024 && L.th % 2 == 0 && L.th * L.tw >= 128) {
     const int th0 = L.th;
     L.th /= 2;
     set_geometry();
-    if (2 * conv_pipe_lds_bytes(pc, L.plane_stride, 1) > 160 * 1024) { L.th = th0; set_geometry(); }
+    if (2 * conv_pipe_lds_bytes(pc, L.plane_stride) > 160 * 1024) { L.th = th0; set_geometry(); }
   }
   {   // development: SCPOSE_TILE="th,tw" overrides the tile of weight-resident 3x3 stride-1 layers
     static const char* e = dev_env("SCPOSE_TILE");
@@ -297,25 +297,15 @@ int32_t conv_launch(const PackedConv& pc, const void* in, int N, int H, int W, c
     }
   }
   // Weight-streaming 3x3 layers.  Measured on MI355X: a CU's LDS-DMA path moves ~16 B/clk and the
-  // issuing wave stalls for it.  So (a) the bytes staged per MFMA must be small: one staged weight
-  // chunk serves TWO pixel tiles; and (b) DMA issue must overlap MFMAs: the two tiles belong to two
-  // wave groups of one 512-thread workgroup (two waves per SIMD, <= 256 registers each).
-  int nt = 1, occ = 1, groups = 1;
-  if (!resident && pc.ks == 3 && pc.stride == 1 && pc.mrep >= 4) {
-    groups = 2;
-    if (pc.mrep * nrep > 24) {   // 256-register budget of the two-group variant: at most 6 x 4 MFMA tiles per wave
-      int th = L.th;
-      while (th > 1 && (pc.mrep * ((th * L.tw + 63) / 64) > 24 || L.Ho % th != 0)) --th;
-      if (pc.mrep * ((th * L.tw + 63) / 64) <= 24) { L.th = th; set_geometry(); }
-    }
-    if (conv_pipe_lds_bytes(pc, L.plane_stride, 2) > 160 * 1024 || pc.mrep * nrep > 24) groups = 1;
-    if (groups == 1 && 2 * pc.mrep * nrep * 4 <= 224) nt = 2;
-  }
+  // issuing wave stalls for it.  So the bytes staged per MFMA must be small: one staged weight
+  // chunk serves TWO pixel tiles, one after the other (two accumulator sets: 2 x mrep x nrep x 4 registers).
+  int nt = 1, occ = 1;
+  if (!resident && pc.ks == 3 && pc.stride == 1 && pc.mrep >= 4 && 2 * pc.mrep * nrep * 4 <= 224) nt = 2;
   if (!resident && pc.ks == 3 && pc.stride == 2 && pc.mrep >= 4 && nrep <= 2) {
     static const char* e = dev_env("SCPOSE_S2_NT");
     nt = e ? atoi(e) : 2;   // weight chunk shared by 2 sequential pixel tiles (measured: 3 is no better than 1)
   }
-  if (resident && 2 * conv_pipe_lds_bytes(pc, L.plane_stride, 1) <= 160 * 1024) occ = 2;
+  if (resident && 2 * conv_pipe_lds_bytes(pc, L.plane_stride) <= 160 * 1024) occ = 2;
   // 1x1 layers are bound by their memory instructions (K is tiny): two workgroups per CU double the waves that
   // keep loads and stores in flight; halve the pixel tile until two of them fit the LDS and the register budget
   static const char* e11 = dev_env("SCPOSE_K1_OCC");
@@ -324,27 +314,23 @@ int32_t conv_launch(const PackedConv& pc, const void* in, int N, int H, int W, c
   if (pc.ks == 1 && !out_nchw_f32 && L.Ho * L.Wo >= (e11p ? atoi(e11p) : 4096) && !(e11 && atoi(e11) == 1) &&
       (pc.ksteps_full >= 2 || (e11 && atoi(e11) == 2))) {   // high-resolution maps only: measured slower on the small ones
     while (L.th % 2 == 0 && L.th * L.tw > 64 &&
-           (2 * conv_pipe_lds_bytes(pc, L.plane_stride, 1) > 160 * 1024 || pc.mrep * nrep * 4 > 128)) {
+           (2 * conv_pipe_lds_bytes(pc, L.plane_stride) > 160 * 1024 || pc.mrep * nrep * 4 > 128)) {
       L.th /= 2;
       set_geometry();
     }
-    if (2 * conv_pipe_lds_bytes(pc, L.plane_stride, 1) <= 160 * 1024 && pc.mrep * nrep * 4 <= 128) occ = 2;
+    if (2 * conv_pipe_lds_bytes(pc, L.plane_stride) <= 160 * 1024 && pc.mrep * nrep * 4 <= 128) occ = 2;
   }
   {   // buffer-addressed input DMA when the input tensor fits a 32-bit descriptor
-    static const char* e = dev_env("SCPOSE_M32_BUF");
-    const size_t ib = (size_t)N * H * W * 16 * L.cin_planes;
-    const bool fits = ib < 0xfffffff0ull && !(e && atoi(e) == 0);
-    L.in_bytes = fits ? (uint32_t)ib : 0;
+    L.in_bytes = buf_bytes_or_64bit(blocked_bytes(N, L.cin_planes, H, W));
     L.out_bytes = 0;   // conv_pipe writes its output through 64-bit pointers
   }
   L.cp = pc.cp; L.nchunks = pc.nchunks; L.ksteps_full = pc.ksteps_full;
   L.n_mblk = pc.n_mblk;
   L.relu = relu; L.out_nchw_f32 = out_nchw_f32;
-  L.total_blocks = N * L.tiles_x * L.tiles_y * pc.n_mblk;
   SCP_REQUIRE(L.halo_h * L.halo_w <= (pc.stride == 1 ? 2 : 3) * 256, "conv: halo %dx%d too large",
               L.halo_h, L.halo_w);
   SCP_REQUIRE((pc.ksteps_full + 1) * 4 <= 64, "conv: k-offset table overflow (%d ksteps)", pc.ksteps_full);
-  return conv_launch_pipe(pc, L, nrep, nt, occ, groups, stream);
+  return conv_launch_pipe(pc, L, nrep, nt, occ, stream);
 }
 
 }  // namespace scpose

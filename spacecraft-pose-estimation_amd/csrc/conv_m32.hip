@@ -253,22 +253,20 @@ int32_t conv_launch_m32(const PackedConv& pc, ConvLaunch& L, hipStream_t stream)
   const int pxcap = m32_pxcap(wn, t.nr, t.nb16);
   L.nbuf_w = pcons ? m32p_wbufs(pc, ck, L.plane_stride, pxcap) : (pc.nchunks == 1 && pc.n_mblk == 1) ? 1 : 2;
   L.nbuf_x = 2;
-  L.groups = 1;
+  L.wreg_chunks = 1;
   const size_t lds = pcons ? m32p_lds_bytes(pc, ck, L.plane_stride, pxcap) : m32_lds_bytes(pc, L.plane_stride);
   L.zero16 = conv_zero_page();
   SCP_REQUIRE(L.zero16, "conv: cannot allocate the zero page");
   L.tiles_total = L.N * L.tiles_x * L.tiles_y;
   { static const char* e = dev_env("SCPOSE_NST"); const int v = e ? atoi(e) : 0;   // producer/consumer kernel: stages that store the previous tile
-    L.total_blocks = (pcons && v > 0 && v <= pc.nchunks - 2) ? v : 0; }
+    L.store_stages = (pcons && v > 0 && v <= pc.nchunks - 2) ? v : 0; }
   L.items_total = ((L.tiles_total + L.nt - 1) / L.nt) * pc.n_mblk;
   { static const char* e = dev_env("SCPOSE_DBG"); L.dbg = e ? atoi(e) : 0; }
   if (!kDevBuild) L.dbg &= 32;   // shipped library: only the host-side "print the tile choice" bit means anything (common.h: SCP_DBG)
   {   // producer/consumer kernel: buffer-addressed global traffic when both tensors fit a 32-bit descriptor
-    static const char* e = dev_env("SCPOSE_M32_BUF");
-    const size_t ib = (size_t)L.N * L.cin_planes * L.H * L.W * 16, ob = (size_t)L.N * ((pc.cout + 7) / 8) * L.Ho * L.Wo * 16;
-    const bool fits = ib < 0xfffffff0ull && ob < 0xfffffff0ull && !(e && atoi(e) == 0);
-    L.in_bytes = fits ? (uint32_t)ib : 0;
-    L.out_bytes = fits ? (uint32_t)ob : 0;
+    L.in_bytes = buf_bytes_or_64bit(blocked_bytes(L.N, L.cin_planes, L.H, L.W));
+    L.out_bytes = buf_bytes_or_64bit(blocked_bytes(L.N, (pc.cout + 7) / 8, L.Ho, L.Wo));
+    if (!L.in_bytes || !L.out_bytes) L.in_bytes = L.out_bytes = 0;   // one addressing mode for both
   }
   L.dbg_buf = nullptr;
   if (L.dbg & 8) L.dbg_buf = conv_dbg_buffer(stream);
@@ -285,9 +283,8 @@ int32_t conv_launch_m32(const PackedConv& pc, ConvLaunch& L, hipStream_t stream)
   L.grid = (L.items_total + L.items_per_wg - 1) / L.items_per_wg;
   conv_dbg_set_grid(L.grid);
   if (pcons) {
-    // L.groups doubles as "K-chunks of weights held in producer registers" for the producer/consumer kernel
     static const char* wr_env = dev_env("SCPOSE_M32_WREG");
-    L.groups = (pc.n_mblk == 1 && ck.nchunks == 6 && ck.cp == 2 && pc.stride == 1 && pc.mrep == 3 && (t.nb16 > 0 ? t.nb16 == 6 : t.nr == 3) && !(wr_env && atoi(wr_env) == 0)) ? 6 : 1;
+    L.wreg_chunks = (pc.n_mblk == 1 && ck.nchunks == 6 && ck.cp == 2 && pc.stride == 1 && pc.mrep == 3 && (t.nb16 > 0 ? t.nb16 == 6 : t.nr == 3) && !(wr_env && atoi(wr_env) == 0)) ? 6 : 1;
     // t.nb16 > 0: 16x16x32 consumers (conv_m32p_kernel.h, C16; round 4) -- see conv_m16_eligible
     if (pc.dtype == SCPOSE_DT_BF16) return conv_m32p_dispatch_bf16(pc.stride, pc.mrep, t.nr, t.nb16, L, lds, stream);
     return conv_m32p_dispatch_f16(pc.stride, pc.mrep, t.nr, t.nb16, L, lds, stream);

@@ -151,8 +151,7 @@ __global__ __launch_bounds__(512, 2) void conv_m32p_kernel(const ConvLaunch p) {
     oy0 = ty * p.th; ox0 = (rem - ty * p.tiles_x) * p.tw;
   };
   // number of stages at the head of a tile in which the previous tile's results are stored
-  // (total_blocks doubles as a host-side override of the store-stage count for this kernel)
-  const int n_st = p.total_blocks > 0 ? p.total_blocks : (p.nchunks >= 6 ? 2 : 1);
+  const int n_st = p.store_stages > 0 ? p.store_stages : (p.nchunks >= 6 ? 2 : 1);
 
   if (producer) {
     // =====================================================================================
@@ -1017,7 +1016,7 @@ template <int DT>
 int32_t m32p_dispatch(int stride, int mr, int nr, int c16, const ConvLaunch& L, size_t lds, hipStream_t st) {
   if (c16) {   // 16x16x32 consumers, c16 = 16-pixel columns per consumer wave (conv_launch_m32 routes only stride 1 and 96-row blocks here)
     if (stride == 1 && mr == 3) {
-      if (c16 == 6) return L.groups == 6 ? m32p_launch_one<DT, 1, 3, 3, 6, 6>(L, lds, st) : m32p_launch_one<DT, 1, 3, 3, 0, 6>(L, lds, st);
+      if (c16 == 6) return L.wreg_chunks == 6 ? m32p_launch_one<DT, 1, 3, 3, 6, 6>(L, lds, st) : m32p_launch_one<DT, 1, 3, 3, 0, 6>(L, lds, st);
       if (c16 == 5) return m32p_launch_one<DT, 1, 3, 3, 0, 5>(L, lds, st);
       if (c16 == 4) return m32p_launch_one<DT, 1, 3, 2, 0, 4>(L, lds, st);
       if (c16 == 2) return m32p_launch_one<DT, 1, 3, 1, 0, 2>(L, lds, st);
@@ -1036,7 +1035,7 @@ int32_t m32p_dispatch(int stride, int mr, int nr, int c16, const ConvLaunch& L, 
   }
   if (mr == 3 && nr == 1) return m32p_launch_one<DT, 1, 3, 1>(L, lds, st);
   if (mr == 3 && nr == 2) return m32p_launch_one<DT, 1, 3, 2>(L, lds, st);
-  if (mr == 3 && nr == 3 && L.groups == 6) return m32p_launch_one<DT, 1, 3, 3, 6>(L, lds, st);   // weights in producer registers
+  if (mr == 3 && nr == 3 && L.wreg_chunks == 6) return m32p_launch_one<DT, 1, 3, 3, 6>(L, lds, st);   // weights in producer registers
   if (mr == 3 && nr == 3) return m32p_launch_one<DT, 1, 3, 3>(L, lds, st);
   if (mr == 2 && nr == 1) return m32p_launch_one<DT, 1, 2, 1>(L, lds, st);
   if (mr == 2 && nr == 2) return m32p_launch_one<DT, 1, 2, 2>(L, lds, st);

@@ -12,9 +12,6 @@ namespace scpose {
 int32_t conv_pipe_dispatch_bf16(int ks, int stride, int mrep, int nrep, int nt, int occ, const ConvLaunch& L, size_t lds, hipStream_t st);
 int32_t conv_pipe_dispatch_f16(int ks, int stride, int mrep, int nrep, int nt, int occ, const ConvLaunch& L, size_t lds, hipStream_t st);
 
-int32_t conv_stag_dispatch_bf16(int mrep, int nrep, const ConvLaunch& L, size_t lds, hipStream_t st);
-int32_t conv_stag_dispatch_f16(int mrep, int nrep, const ConvLaunch& L, size_t lds, hipStream_t st);
-
 static void* g_zero_page[16] = {nullptr};
 static unsigned long long* g_dbg_buf = nullptr;
 static int g_dbg_grid = 0;
@@ -53,22 +50,20 @@ int conv_device_cus() {
   return cus[dev];
 }
 
-size_t conv_pipe_lds_bytes(const PackedConv& pc, int plane_stride, int groups) {
+size_t conv_pipe_lds_bytes(const PackedConv& pc, int plane_stride) {
   const bool resident = pc.nchunks == 1 && pc.n_mblk == 1;
   const size_t lds_w = (size_t)pc.ksteps_full * 4 * pc.mt * 16;
   const size_t lds_bias = (((size_t)pc.n_mblk * pc.mt * 4) + 511) & ~(size_t)511;
-  if (groups == 2) return 512 + lds_bias + 3 * lds_w + 4 * (size_t)pc.cp * plane_stride;   // staggered two-group schedule
   return 512 + lds_bias + (resident ? 1 : 2) * lds_w + 2 * (size_t)pc.cp * plane_stride;
 }
 
-int32_t conv_launch_pipe(const PackedConv& pc, ConvLaunch& L, int nrep, int nt, int occ, int groups, hipStream_t stream) {
+int32_t conv_launch_pipe(const PackedConv& pc, ConvLaunch& L, int nrep, int nt, int occ, hipStream_t stream) {
   L.lds_w = pc.ksteps_full * 4 * pc.mt * 16;
   L.lds_x = pc.cp * L.plane_stride;
   L.lds_bias = ((pc.n_mblk * pc.mt * 4) + 511) & ~511;
   L.nbuf_w = (pc.nchunks == 1 && pc.n_mblk == 1) ? 1 : 2;
   L.nbuf_x = 2;
-  const size_t lds = conv_pipe_lds_bytes(pc, L.plane_stride, groups);
-  L.groups = groups;
+  const size_t lds = conv_pipe_lds_bytes(pc, L.plane_stride);
   SCP_REQUIRE(lds <= 160 * 1024, "conv: LDS image of %d->%d k%d s%d (%zu B) does not fit 160 KiB", pc.cin, pc.cout, pc.ks, pc.stride, lds);
   L.zero16 = conv_zero_page();
   SCP_REQUIRE(L.zero16, "conv: cannot allocate the zero page");
@@ -76,23 +71,19 @@ int32_t conv_launch_pipe(const PackedConv& pc, ConvLaunch& L, int nrep, int nt, 
   L.fd_tiles_img = make_fastdiv(L.tiles_x * L.tiles_y); L.fd_tiles_x = make_fastdiv(L.tiles_x);
   L.fd_nmblk = make_fastdiv(pc.n_mblk);
   L.nt = nt;
-  L.items_total = ((L.tiles_total + nt * groups - 1) / (nt * groups)) * pc.n_mblk;
+  L.items_total = ((L.tiles_total + nt - 1) / nt) * pc.n_mblk;
   { static const char* e = dev_env("SCPOSE_DBG"); L.dbg = (kDevBuild && e) ? atoi(e) : 0; }
   L.dbg_buf = nullptr;
   if (L.dbg & 8) L.dbg_buf = conv_dbg_buffer(stream);
   const int cus = conv_device_cus();
   int per_cu = (int)((160 * 1024) / lds);
   { static const char* e = dev_env("SCPOSE_K1_WGS"); const int cap = (pc.ks == 1 && e) ? atoi(e) : 2; per_cu = per_cu < 1 ? 1 : (per_cu > cap ? cap : per_cu); }
-  if (occ < 2 || groups > 1) per_cu = 1;   // the variant's register budget assumes one workgroup per CU
+  if (occ < 2) per_cu = 1;   // the variant's register budget assumes one workgroup per CU
   int grid = cus * per_cu;
   if (grid > L.items_total) grid = L.items_total;
   L.items_per_wg = (L.items_total + grid - 1) / grid;
   L.grid = (L.items_total + L.items_per_wg - 1) / L.items_per_wg;
   g_dbg_grid = L.grid;
-  if (groups == 2) {
-    if (pc.dtype == SCPOSE_DT_BF16) return conv_stag_dispatch_bf16(pc.mrep, nrep, L, lds, stream);
-    return conv_stag_dispatch_f16(pc.mrep, nrep, L, lds, stream);
-  }
   if (pc.dtype == SCPOSE_DT_BF16) return conv_pipe_dispatch_bf16(pc.ks, pc.stride, pc.mrep, nrep, nt, occ, L, lds, stream);
   return conv_pipe_dispatch_f16(pc.ks, pc.stride, pc.mrep, nrep, nt, occ, L, lds, stream);
 }

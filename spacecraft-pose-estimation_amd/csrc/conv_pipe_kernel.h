@@ -33,8 +33,7 @@
 //   * measured: the LDS-DMA path of a CU accepts ~16 B/clk and a wave that issues into a full queue
 //     stalls, MFMAs included (feeding the pieces from inside the MFMA loop made the loop 2.8x
 //     slower), so a stage's pieces go out in one burst before the MFMA loop; the overlap comes from
-//     the second resident workgroup (weight-resident layers) or from the staggered two-group
-//     schedule of conv_stag_kernel.h (weight-streaming layers);
+//     the second resident workgroup (weight-resident layers);
 //   * zero padding comes from a zero page (an out-of-image halo pixel's DMA source is redirected
 //     to 16 zero bytes); lanes past the halo tile are masked off (EXEC);
 //   * residual slots are prefetched (inline-asm loads, issued before the stage's DMA) and the
@@ -75,7 +74,7 @@ __device__ __forceinline__ void dma16_buf(buf_rsrc_t r, uint32_t voff, uint32_t 
 }
 // The s_nop behind the store: a 16-byte buffer store reads its four data VGPRs over a few cycles after issue, and hipcc (ROCm 7.2,
 // gfx950) puts NO wait state between such a store and a VALU instruction that overwrites one of them.  Round 4 hit it in
-// conv_block2_kernel: `buffer_store_dwordx4 v[82:85], ..., s42 offen` directly followed by `v_mov_b32 v82, v0` (the next pass's
+// conv_block_kernel: `buffer_store_dwordx4 v[82:85], ..., s42 offen` directly followed by `v_mov_b32 v82, v0` (the next pass's
 // thread id) stored the thread id in the first dword of the vector for lanes 12-15 of every 16 -- only in a workgroup's first tile,
 // only in the product build (tools_dev/where_block_differs.py; the guide prescribes the same pad for asm stores: cdna_hip_programming.md
 // 5.7).  Two wait states here cost nothing next to the store's issue and protect every kernel that stores through this helper.
@@ -100,14 +99,8 @@ __device__ inline void store4_buf(buf_rsrc_t, uint32_t, uint32_t) {}
 
 // OCC = resident workgroups per CU the variant is built for: 2 caps the wave at 256 registers
 // (two waves per SIMD, which also hide LDS latency, so the explicit fragment prefetch is dropped).
-// G = wave groups per workgroup (1 or 2; 256 threads each).  With G = 2 the two groups work on
-// two DIFFERENT pixel tiles in parallel from ONE staged copy of the weight chunk: the weight
-// bytes per MFMA halve like NT = 2, but with two waves per SIMD one group's DMA-issue stalls
-// (the LDS-DMA path accepts ~16 B/clk per CU and the issuing wave waits for it) overlap the
-// other group's MFMAs.
-template <int DT, int KS, int STRIDE, int MREP, int NREP, int NT, int OCC, int G>
-__global__ __launch_bounds__(256 * G, (G == 2) ? 2 : OCC) void conv_pipe_kernel(const ConvLaunch p) {
-  static_assert(G == 1 || NT == 1, "parallel tile groups and sequential tile groups are exclusive");
+template <int DT, int KS, int STRIDE, int MREP, int NREP, int NT, int OCC>
+__global__ __launch_bounds__(256, OCC) void conv_pipe_kernel(const ConvLaunch p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef typename DtOf<DT>::type T;
   typedef typename FragOf<T>::type frag_t;
@@ -123,9 +116,12 @@ __global__ __launch_bounds__(256 * G, (G == 2) ? 2 : OCC) void conv_pipe_kernel(
   char* xl0 = wl0 + p.nbuf_w * p.lds_w;
 
   const int lane = threadIdx.x & 63;
-  const int wave_all = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // 0 .. 4G-1 (scalar): weight-chunk DMA is spread over all waves
-  const int grp = wave_all >> 2;                     // this wave's tile group
-  const int wave = wave_all & 3, tid = threadIdx.x & 255;   // position inside the group
+  const int wave_all = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // 0 .. 3 (scalar)
+  // 0 in a 256-thread workgroup.  The compiler cannot see that through readfirstlane, and replacing the term by a literal 0 changes
+  // the code of 303 of the 304 instantiations (registers +-4, code bytes -11 .. +18 %): it stays until a change that re-measures
+  // them all (profiles/retire_stag_block_v1_grp0.txt, both builds row by row)
+  const int grp = wave_all >> 2;
+  const int wave = wave_all & 3, tid = threadIdx.x & 255;
   const int q = lane >> 4, r = lane & 15;
   const int HW = p.H * p.W;
   const int HP = p.halo_h * p.halo_w;
@@ -143,7 +139,7 @@ __global__ __launch_bounds__(256 * G, (G == 2) ? 2 : OCC) void conv_pipe_kernel(
     const int ky = tap / KS, kx = tap - ky * KS;
     koff[threadIdx.x] = pt < npt ? (2 * pp + (qq & 1)) * p.plane_stride + (ky * p.halo_w + kx) * 16 : 0;
   }
-  for (int i = threadIdx.x; i < p.n_mblk * MT; i += 256 * G) bias_l[i] = p.bias[i];
+  for (int i = threadIdx.x; i < p.n_mblk * MT; i += 256) bias_l[i] = p.bias[i];
 
   // tile-independent geometry of this thread's halo pixels and this lane's output pixels
   int hy[MAXP], hx[MAXP];
@@ -185,7 +181,7 @@ __global__ __launch_bounds__(256 * G, (G == 2) ? 2 : OCC) void conv_pipe_kernel(
   // item -> (Cout block, first tile of the group); tile -> (image, tile origin); img < 0 = no tile
   auto item_mb = [&](int it) { return it - pipe_fdiv(it, p.fd_nmblk) * p.n_mblk; };
   auto decode_tile = [&](int it, int j, int& img, int& oy0, int& ox0) {
-    const int t = pipe_fdiv(it, p.fd_nmblk) * (NT * G) + j + grp * NT;
+    const int t = pipe_fdiv(it, p.fd_nmblk) * NT + j + grp * NT;
     if (t >= p.tiles_total) { img = -1; oy0 = ox0 = 0; return; }
     img = pipe_fdiv(t, p.fd_tiles_img);
     const int rem = t - img * tiles_per_img;
@@ -234,12 +230,12 @@ __global__ __launch_bounds__(256 * G, (G == 2) ? 2 : OCC) void conv_pipe_kernel(
     const int planes = c == p.nchunks - 1 ? planes_last : p.cp;
     const int ksteps = (((planes >> 1) * KK) + 1) >> 1;
     const int nbytes = ksteps * (4 * MT * 16);
-    const int slice = (((nbytes + nparts - 1) / nparts) + 4096 * G - 1) / (4096 * G) * (4096 * G);   // whole rounds of the workgroup
+    const int slice = (((nbytes + nparts - 1) / nparts) + 4095) / 4096 * 4096;   // whole rounds of the workgroup
     const int lo = part * slice, hi = min(nbytes, lo + slice);
     const buf_rsrc_t rs_w = make_buf(p.wpk, (uint32_t)(p.n_mblk * p.nchunks * (int)chunk_wbytes));   // packed weights: far below 4 GiB
     const uint32_t wchunk = (uint32_t)((item_mb(it) * p.nchunks + c) * (int)chunk_wbytes);
     char* wl = wl0 + wb * p.lds_w;
-    for (int o = lo; o < hi; o += 4096 * G) {
+    for (int o = lo; o < hi; o += 4096) {
       const int mine = o + (int)threadIdx.x * 16;
       if (mine < hi) dma16_buf(rs_w, threadIdx.x * 16u, wchunk + (uint32_t)o, wl + o + wave_all * 1024);
     }
@@ -247,7 +243,7 @@ __global__ __launch_bounds__(256 * G, (G == 2) ? 2 : OCC) void conv_pipe_kernel(
 
   // weight-resident single-chunk 3x3 layers (the HBM-bound high-resolution branch): the k-step offsets are
   // tile-invariant, so they live in registers and the k-loop below is fully unrolled, hand-scheduled asm
-  constexpr bool ASM_LOOP = KS == 3 && STRIDE == 1 && NT == 1 && G == 1 && MREP * NREP <= 8 && MT <= 64;
+  constexpr bool ASM_LOOP = KS == 3 && STRIDE == 1 && NT == 1 && MREP * NREP <= 8 && MT <= 64;
   constexpr int ASM_STEPS = 14;
   int koffv[ASM_LOOP ? ASM_STEPS : 1];
   float4 bsv[MREP];   // bias of the (single) Cout block stays in registers; several blocks: re-read per item
@@ -323,7 +319,7 @@ __global__ __launch_bounds__(256 * G, (G == 2) ? 2 : OCC) void conv_pipe_kernel(
         // (2) DMA for the next stage: its input tile, plus this sub-stage's slice of the next weight chunk
         // single-chunk layers with several Cout blocks (1x1 64->256): consecutive items are the Cout
         // blocks of ONE pixel tile, whose staged input is reused instead of being fetched again
-        const bool same_x = NT == 1 && G == 1 && p.nchunks == 1 && have_next_chunk &&
+        const bool same_x = NT == 1 && p.nchunks == 1 && have_next_chunk &&
                             pipe_fdiv(nit, p.fd_nmblk) == pipe_fdiv(it, p.fd_nmblk);
         if (J + 1 < NT) issue_x(it, J + 1, c, xb ^ 1);
         else if (have_next_chunk && !same_x) issue_x(nit, 0, nc, xb ^ 1);
@@ -534,12 +530,12 @@ __global__ __launch_bounds__(256 * G, (G == 2) ? 2 : OCC) void conv_pipe_kernel(
 }
 
 // ---- launch dispatch (instantiated per dtype in conv_pipe_bf16.hip / conv_pipe_f16.hip) ----
-template <int DT, int KS, int STRIDE, int MREP, int NREP, int NT, int OCC, int G = 1>
+template <int DT, int KS, int STRIDE, int MREP, int NREP, int NT, int OCC>
 int32_t pipe_launch_one(const ConvLaunch& L, size_t lds, hipStream_t st) {
-  auto kern = conv_pipe_kernel<DT, KS, STRIDE, MREP, NREP, NT, OCC, G>;
+  auto kern = conv_pipe_kernel<DT, KS, STRIDE, MREP, NREP, NT, OCC>;
   static LdsOptIn big_lds;   // per device (common.h)
   { const int32_t rc = lds_opt_in(reinterpret_cast<const void*>(kern), 160 * 1024, &big_lds); if (rc != SCPOSE_OK) return rc; }
-  hipLaunchKernelGGL(kern, dim3(L.grid), dim3(256 * G), lds, st, L);
+  hipLaunchKernelGGL(kern, dim3(L.grid), dim3(256), lds, st, L);
   SCP_CHECK_HIP(hipGetLastError());
   return SCPOSE_OK;
 }

@@ -277,7 +277,7 @@ __global__ __launch_bounds__(NW * 64, 2) void fuse_down_kernel(const FdLaunch p)
     // flight (the DMA was issued first) measured the same here and 1-2 % SLOWER in the fused BasicBlock and the producer/consumer
     // kernels (round 4), and round 2 saw sporadic wrong results with it in the stride-2 kernels
     // (one asm statement with a memory clobber: the builtin barrier is IntrNoMem to the compiler, which may then hoist the next
-    // tile's ordinary LDS loads above it, into a buffer other waves' LDS-DMA is still filling -- conv_block2_kernel.h)
+    // tile's ordinary LDS loads above it, into a buffer other waves' LDS-DMA is still filling -- conv_block_kernel.h)
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");                          // ... and everybody is done with this buffer (LDS reads are consumed)
   }
 }
@@ -342,11 +342,11 @@ int32_t fuse_down_launch(const FuseDownPacked& fd, const void* x0, int N, int H,
   SCP_REQUIRE(fuse_down_supported(nb, c0, 2 * c0) && fd.d_w, "fuse_down: %d branches of %d channels not eligible", nb, c0);
   SCP_REQUIRE(H % 8 == 0 && W % 8 == 0, "fuse_down: branch 0 is %dx%d (multiples of 8: the coarsest term is 1/8 of it)", H, W);
   const int Ho = H / 2, Wo = W / 2;
-  const size_t in_frame = (size_t)planes * H * W * 16;
-  SCP_REQUIRE(in_frame < 0xfffffff0ull, "fuse_down: one %dx%d frame does not fit a 32-bit buffer descriptor", H, W);
-  // tensors are addressed through 32-bit buffer descriptors: batches whose branch-0 tensor reaches 4 GiB run as several launches
-  int max_n = (int)(0xfffffff0ull / in_frame);
-  { static const char* e = dev_env("SCPOSE_FD_MAXN"); if (e && atoi(e) > 0 && atoi(e) < max_n) max_n = atoi(e); }   // tests: force the split on a small batch
+  const size_t in_frame = blocked_bytes(1, planes, H, W);
+  SCP_REQUIRE(fits_buf(in_frame), "fuse_down: one %dx%d frame does not fit a 32-bit buffer descriptor", H, W);
+  // batches whose branch-0 tensor (the largest) does not fit a buffer descriptor run as several launches (common.h: buf_max_frames)
+  static const char* cap = dev_env("SCPOSE_FD_MAXN");   // tests: force the split on a small batch
+  const int max_n = buf_max_frames(in_frame, cap ? atoi(cap) : 0);
   for (int n0 = 0; n0 < N; n0 += max_n) {
     const int n = N - n0 < max_n ? N - n0 : max_n;
     FdLaunch L{};
@@ -357,7 +357,7 @@ int32_t fuse_down_launch(const FuseDownPacked& fd, const void* x0, int N, int H,
     for (int gidx = 0; gidx < nb; ++gidx) {
       const int o = gidx < 2 ? 0 : gidx - 1;            // groups 0, 1: the two halves of row 1's 2 c0 channels
       const int op = (o == 0 ? 2 : 1) * planes;
-      const size_t out_frame = (size_t)op * Ho * Wo * 16;
+      const size_t out_frame = blocked_bytes(1, op, Ho, Wo);
       L.out[gidx] = static_cast<char*>(outs[o]) + (size_t)n0 * out_frame;
       L.out_bytes[gidx] = (uint32_t)((size_t)n * out_frame);
       L.out_planes[gidx] = op;
@@ -366,7 +366,7 @@ int32_t fuse_down_launch(const FuseDownPacked& fd, const void* x0, int N, int H,
     }
     L.nlow = nb - 1;
     for (int k = 0; k < nb - 1; ++k) {
-      const size_t t_frame = (size_t)planes * (H >> (k + 1)) * (W >> (k + 1)) * 16;
+      const size_t t_frame = blocked_bytes(1, planes, H >> (k + 1), W >> (k + 1));
       L.term[k] = static_cast<const char*>(terms[k]) + (size_t)n0 * t_frame;
       L.term_bytes[k] = (uint32_t)((size_t)n * t_frame);
       L.shift[k] = k + 1;

@@ -286,7 +286,7 @@ size_t head_fused_part_bytes(int n) { return (size_t)n * kMaxStrips * 16 * 4; } 
 
 bool head_fused_supported(int nterms, int C, int J, int N, int H, int W) {
   if (nterms < 1 || nterms > 4 || C % 8 != 0 || C > 64 || J < 1 || J > 16) return false;
-  return (size_t)N * (C / 8) * H * W * 16 < 0xfffffff0ull && (size_t)N * J * H * W * 4 < 0xfffffff0ull && (size_t)H * W < (1u << 24);   // 32-bit buffer offsets; float32 pixel indices
+  return fits_buf(blocked_bytes(N, C / 8, H, W)) && fits_buf((size_t)N * J * H * W * 4) && (size_t)H * W < (1u << 24);   // 32-bit buffer offsets; float32 pixel indices
 }
 
 template <int DT, int NT>

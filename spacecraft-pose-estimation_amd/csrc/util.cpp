@@ -32,6 +32,11 @@ const char* dev_env(const char* name) {
   return enabled ? getenv(name) : nullptr;
 }
 
+uint32_t buf_bytes_or_64bit(size_t bytes) {
+  static const char* e = dev_env("SCPOSE_M32_BUF");
+  return (fits_buf(bytes) && !(e && atoi(e) == 0)) ? (uint32_t)bytes : 0;
+}
+
 int32_t lds_opt_in(const void* kernel, int bytes, LdsOptIn* memo) {
   int dev = 0;
   SCP_CHECK_HIP(hipGetDevice(&dev));

@@ -401,7 +401,7 @@ def test_fused_bottleneck_matches_oracle(gpu_ops, h, w, n, dt):
 def test_layer1_is_batch_invariant_under_the_xcd_local_tile_queue(gpu_ops, n):
     """The Bottleneck kernels take their tiles from per-XCD queues (conv_device.h: tile_claim_xcd: XCD k owns the tiles of images
     k, k + 8, ...; empty lists steal from the next XCD's) and the fused BasicBlock runs conv1 of tile i beside conv2 of tile
-    i - 1 (conv_block2_kernel.h): a frame's result must not depend on how many frames share the launch -- batches that leave
+    i - 1 (conv_block_kernel.h): a frame's result must not depend on how many frames share the launch -- batches that leave
     XCD lists empty (n < 8), uneven (9, 17) or single -- nor on the run."""
     cfg = R.w32_cfg()
     sd = R.make_state_dict(cfg, seed=31)

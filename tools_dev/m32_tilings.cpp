@@ -16,15 +16,19 @@ const char* dev_env(const char* name) {   // as util.cpp, except that SCPOSE_DBG
   const char* e = getenv("SCPOSE_DEV");
   return e && atoi(e) != 0 ? getenv(name) : nullptr;
 }
+uint32_t buf_bytes_or_64bit(size_t bytes) {   // as util.cpp
+  const char* e = dev_env("SCPOSE_M32_BUF");
+  return (fits_buf(bytes) && !(e && atoi(e) == 0)) ? (uint32_t)bytes : 0;
+}
 int conv_device_cus() { return 256; }
 const void* conv_zero_page() { static const char z[256] = {0}; return z; }
 unsigned long long* conv_dbg_buffer(hipStream_t) { return nullptr; }
 void conv_dbg_set_grid(int) {}
 uint16_t host_f32_to_16(float, int) { return 0; }
 static int32_t show(const char* k, int a, int b, int c, int d, const ConvLaunch& L, size_t lds) {
-  printf("  -> %s(%d,%d,%d,%d) lds=%zu grid=%d items_per_wg=%d ps=%d cp=%d nchunks=%d ksteps=%d lds_w=%d lds_x=%d lds_bias=%d nbuf_w=%d groups=%d nst=%d buf=%u/%u\n",
-         k, a, b, c, d, lds, L.grid, L.items_per_wg, L.plane_stride, L.cp, L.nchunks, L.ksteps_full, L.lds_w, L.lds_x, L.lds_bias, L.nbuf_w, L.groups,
-         L.total_blocks, L.in_bytes, L.out_bytes);
+  printf("  -> %s(%d,%d,%d,%d) lds=%zu grid=%d items_per_wg=%d ps=%d cp=%d nchunks=%d ksteps=%d lds_w=%d lds_x=%d lds_bias=%d nbuf_w=%d wreg_chunks=%d store_stages=%d buf=%u/%u\n",
+         k, a, b, c, d, lds, L.grid, L.items_per_wg, L.plane_stride, L.cp, L.nchunks, L.ksteps_full, L.lds_w, L.lds_x, L.lds_bias, L.nbuf_w, L.wreg_chunks,
+         L.store_stages, L.in_bytes, L.out_bytes);
   return 0;
 }
 int32_t conv_m32_dispatch_bf16(int mr, int wm, int nr, int occ, const ConvLaunch& L, size_t lds, hipStream_t) { return show("m32", mr, wm, nr, occ, L, lds); }
