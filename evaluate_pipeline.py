@@ -13,7 +13,7 @@ levels up (:66) although it is one level below the root, and stage 3 reads pred.
 pred_test.mat (both are written here).
 
 Extensions (all optional): --cfg, --regression_opts KEY VAL ..., --nproc_per_node N (frames of a scene sharded over N
-GPUs, one process each), --no_overlay, --device_overlay, --device_decode.
+GPUs, one process each), --no_overlay, --device_overlay, --device_decode, --device_decode_png.
 """
 import argparse
 import os
@@ -52,6 +52,8 @@ def parse_args(argv=None):
                    help="stage 3: passed to export_predicted_poses_real.py (overlay JPEGs drawn and encoded on the device)")
     p.add_argument("--device_decode", action="store_true",
                    help="stage 2: passed to tools/test.py (baseline JPEG frames decoded on the device, straight into the crops)")
+    p.add_argument("--device_decode_png", action="store_true",
+                   help="stage 2: passed to tools/test.py (PNG frames decoded on the device, straight into the crops)")
     p.add_argument("--pnp_refine", choices=("none", "lm"), default="none",
                    help="stage 3: passed to export_predicted_poses_real.py (lm: Levenberg-Marquardt refinement of the poses)")
     return p.parse_args(argv)
@@ -110,7 +112,7 @@ def main(argv=None):
                      "pose_out": os.path.join(under("pose", a.pose_estimation_base), scene)})
     for j in jobs:       # :62-79
         os.makedirs(j["reg_out"], exist_ok=True)
-        run(launcher + ["tools/test.py"] + (["--device_decode"] if a.device_decode else []) + ["--cfg", cfg, "DATA_DIR", j["frames"], "OUTPUT_DIR", j["reg_out"],
+        run(launcher + ["tools/test.py"] + (["--device_decode"] if a.device_decode else []) + (["--device_decode_png"] if a.device_decode_png else []) + ["--cfg", cfg, "DATA_DIR", j["frames"], "OUTPUT_DIR", j["reg_out"],
                         "DATASET.ROOT", j["det_dir"], "DATASET.TEST_SET", "test", "DATASET.TRAIN_SET", "synthetic_train",
                         "DATASET.IMAGE_WIDTH", str(a.image_width), "DATASET.IMAGE_HEIGHT", str(a.image_height),
                         "MODEL.NUM_JOINTS", str(a.joints_count), "TEST.MODEL_FILE", under("regression", a.regression_model_file)]

@@ -486,6 +486,56 @@ int32_t scpose_jpeg_decode_crop(const uint8_t* desc, const int32_t* segs, int64_
                                 const double* minv, const int32_t* roi_xywh, int32_t out_h, int32_t out_w, uint8_t* crops,
                                 int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* (ABI 7, additive) PNG files on the device (csrc/png_decode.hip): the image data of N files of one geometry -> (N, H, W, 3) uint8
+ * frames, bit for bit what PIL's Image.open(..).convert("RGB") returns.  Decoded: bit depth 8, not interlaced, colour types 0 (gray,
+ * replicated into three channels), 2 (RGB), 3 (palette; an index the PLTE chunk does not define is 0, 0, 0), 4 and 6 (alpha dropped,
+ * not blended); tRNS is ignored.  The host walks the chunks (png_read.py): the IDAT payloads of an image are joined into one zlib
+ * stream, so no chunk boundary reaches the device, and everything else -- Adam7, other bit depths, APNG -- is refused there.
+ * The device inflates (stored, fixed and dynamic blocks), sums the Adler-32, undoes the filters 0 .. 4 and expands.  It DETECTS a
+ * damaged stream and never interprets one: an image whose status is not 0 is the host decoder's to judge.
+ *   desc         HOST u8 [n][SCPOSE_PNG_DESC_BYTES].  Per image: int64 offset of its zlib stream in `data` (a multiple of 4); int64
+ *                length of the stream (header bytes, blocks, Adler-32 and whatever follows it); int32 h, w, colour type, channels
+ *                (they must be the call's h, w, channels); 8 x int32 0; then the palette, u8 [256][3], zero-padded.  Checked before
+ *                anything is launched -- a stream that does not lie inside `data` is an argument error -- and uploaded into the
+ *                workspace on `stream`: keep it unchanged until the stream has passed the call
+ *   data         device u8 [n_bytes], 4-byte aligned: the streams
+ *   n, h, w      images of the call and their size, h and w 1 .. 65535; n = 0: nothing to do
+ *   channels     bytes per pixel of a scan line, 1 .. 4 (colour types 0 and 3: 1, 4: 2, 2: 3, 6: 4)
+ *   bgr          0: R, G, B; else B, G, R
+ *   out          device u8 [n][h][w][3] <- the frames.  The frame of an image with a status bit set is unspecified.
+ *   status       device i32 [n] <- 0 or SCPOSE_PNG_CORRUPT (a reserved block type, LEN != ~NLEN, an over-subscribed or incomplete
+ *                code set, a repeat code with nothing to repeat or running past HLIT + HDIST, no end-of-block code, bits that are
+ *                no code, an invalid length or distance symbol, a distance before the first byte, input that ends before the final
+ *                block, fewer bytes than h x (1 + w channels)) | SCPOSE_PNG_CHECKSUM (the Adler-32 of every byte the stream
+ *                produced differs from the four bytes behind the final block; not checked when the stream ends inside them) |
+ *                SCPOSE_PNG_FILTER (a filter byte above 4; not judged for an image that is CORRUPT, whose scan lines are
+ *                incomplete).  More bytes than the image needs is no error: they are decoded and summed, not stored.
+ *   workspace    caller-owned, 256-byte aligned, scpose_png_decode_workspace_bytes(n, h, w, channels)
+ * No allocation, no synchronisation, no atomics, no floating point; two calls on the same bytes give bitwise equal outputs whatever
+ * the workspace held.  No kernel writes outside its image's plane of the workspace, its frame and its status word.  Argument
+ * errors return -1 with a message before anything is launched and need no device. */
+enum { SCPOSE_PNG_CORRUPT = 1, SCPOSE_PNG_CHECKSUM = 2, SCPOSE_PNG_FILTER = 4 };
+#define SCPOSE_PNG_DESC_BYTES 832
+int32_t scpose_png_decode_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t channels, size_t* bytes);
+int32_t scpose_png_decode(const uint8_t* desc, const uint8_t* data, int64_t n_bytes, int32_t n, int32_t h, int32_t w, int32_t channels,
+                          int32_t bgr, uint8_t* out, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
+/* (ABI 7, additive) PNG files -> network crops on the device (csrc/png_decode.hip): crops[i] is, bit for bit, what
+ * scpose_crop_warp_roi returns for the window roi_xywh[i] of the frame scpose_png_decode returns for file i -- without that frame.
+ * The whole stream is inflated and summed (it has no entry points); the filters are undone only down to the window's last row;
+ * every one of the four bilinear taps of a crop pixel is fetched from the scan lines through the same expansion.  A tap outside the
+ * frame or outside the window counts as 0, as in scpose_crop_warp_roi.
+ *   desc, data, n_bytes, n, h, w, channels, bgr, status, workspace   as for scpose_png_decode, the same workspace size
+ *   minv         device f64 [n][6], 8-byte aligned: the inverse affine (crop -> frame) of each image, what scpose_crop_warp_roi takes
+ *   roi_xywh     HOST i32 [n][4]: [x0, y0, w, h], a window of the frame that holds every pixel the warp reads.  Read before the
+ *                call returns: each is checked to lie inside the frame and travels to the kernels in their arguments
+ *   out_h, out_w 1 .. 65535 each
+ *   crops        device u8 [n][out_h][out_w][3] <- the crops.  The crop of an image with a status bit set is unspecified.
+ * Floating point only in the source position of a crop pixel (contraction off, as in scpose_crop_warp). */
+int32_t scpose_png_decode_crop(const uint8_t* desc, const uint8_t* data, int64_t n_bytes, int32_t n, int32_t h, int32_t w,
+                               int32_t channels, int32_t bgr, const double* minv, const int32_t* roi_xywh, int32_t out_h, int32_t out_w,
+                               uint8_t* crops, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 /* (ABI 7, additive) Baseline JPEG encoder on the device (csrc/jpeg_encode.hip): (N, H, W, 3) uint8 RGB frames of one size ->
  * N baseline JPEG byte streams, byte for byte what libjpeg's baseline encoder writes with the standard Huffman tables (PIL's
  * save(quality=q, subsampling=..) with its other defaults): jccolor.c, jcsample.c's h2v2 downsampling, jfdctint.c's forward

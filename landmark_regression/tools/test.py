@@ -54,6 +54,10 @@ def parse_args():
                         help="(extension) decode baseline JPEG frames on the GPU, straight into the crops (ops.decode_crop): the loader only reads "
                              "the files; any other file is decoded by the loader as usual.  Same pred .mat, bit for bit; not with --host_crop.  "
                              "The same as the override DATASET.DEVICE_DECODE True, which tools/test_cv_ensemble.py takes as well")
+    parser.add_argument("--device_decode_png", action="store_true",
+                        help="(extension) decode PNG frames (8-bit, not interlaced) on the GPU, straight into the crops (ops.decode_crop, png=True): "
+                             "the loader only reads the files; any other file is decoded by the loader as usual.  Same pred .mat, bit for bit; "
+                             "with or without --device_decode, not with --host_crop.  The same as the override DATASET.DEVICE_DECODE_PNG True")
     parser.add_argument("--no_auto_workers", action="store_true",
                         help="(extension) keep cfg.WORKERS = 0 as 'decode in this process'.  By default a data set of 512 frames or more is decoded by "
                              "min(32, cores / 4) worker processes even when the YAML says WORKERS: 0 (the reference's events-config.yaml does): same "
@@ -68,6 +72,8 @@ def parse_args():
     args = parser.parse_args()
     if args.device_decode and not args.device_crop:
         parser.error("--device_decode cannot be combined with --host_crop: the device decodes a frame straight into its crop")
+    if args.device_decode_png and not args.device_crop:
+        parser.error("--device_decode_png cannot be combined with --host_crop: the device decodes a frame straight into its crop")
     return args
 
 
@@ -101,6 +107,7 @@ def main():
     lo, hi = parallel.shard_range(len(valid_dataset), rank, ws)
     valid_dataset.device_crop = bool(args.device_crop)
     valid_dataset.device_decode = bool(args.device_decode or cfg.DATASET.DEVICE_DECODE)      # the flag, or the config key every CLI takes
+    valid_dataset.device_decode_png = bool(args.device_decode_png or cfg.DATASET.DEVICE_DECODE_PNG)
     valid_dataset.want_target = bool(args.log_metrics)     # gaussian targets feed the logged loss / PCK only
     workers = parallel.auto_workers(hi - lo, cfg.WORKERS, keep=args.no_auto_workers)
     if workers != int(cfg.WORKERS):

@@ -31,6 +31,8 @@ JPEG_GRAY, JPEG_444, JPEG_420 = 0, 1, 2
 JPEG_NOT_CONVERGED, JPEG_CORRUPT = 1, 2
 JPEG_SUBSEQ_BYTES, JPEG_DESC_BYTES = 128, 9216
 JPEG_ENC_CAPACITY, JPEG_ENC_TABLES = 1, 2
+PNG_CORRUPT, PNG_CHECKSUM, PNG_FILTER = 1, 2, 4
+PNG_DESC_BYTES = 832
 ABI_VERSION = 7
 
 
@@ -139,6 +141,11 @@ SYMBOLS = {
                                      c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "scpose_jpeg_decode_crop": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                           c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "scpose_png_decode_workspace_bytes": (c_int32, [c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
+    "scpose_png_decode": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                    c_size_t, c_void_p]),
+    "scpose_png_decode_crop": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                         c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "scpose_jpeg_encode_workspace_bytes": (c_int32, [c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
     "scpose_jpeg_encode_capacity_bytes": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int64)]),
     "scpose_jpeg_encode": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p,

@@ -173,6 +173,9 @@ def _defaults():
     # extension (not in the reference's tree): decode baseline JPEG frames on the device (dataset/JointsDataset.py: device_decode).  A
     # config key, so that every CLI that takes KEY VAL overrides takes it: tools/test_cv_ensemble.py DATASET.DEVICE_DECODE True
     c.DATASET.DEVICE_DECODE = False
+    # extension: the same for PNG frames (8-bit, not interlaced; csrc/png_decode.hip).  With or without DEVICE_DECODE: alone, JPEGs take
+    # the loader's path and PNGs travel compressed
+    c.DATASET.DEVICE_DECODE_PNG = False
     c.TRAIN = CN({"LR_FACTOR": 0.1, "LR_STEP": [90, 110], "LR": 0.001, "OPTIMIZER": "adam", "MOMENTUM": 0.9,
                   "WD": 0.0001, "NESTEROV": False, "GAMMA1": 0.99, "GAMMA2": 0.0, "BEGIN_EPOCH": 0,
                   "END_EPOCH": 140, "RESUME": False, "CHECKPOINT": "", "BATCH_SIZE_PER_GPU": 32,

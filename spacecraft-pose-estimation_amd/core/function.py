@@ -103,13 +103,14 @@ class _Coalescer:
         return out
 
 
-def _decode_crops(config, frames, meta, dev):
+def _decode_crops(config, frames, meta, dev, png=False):
     """A device_decode batch (dataset.collate_device_crop) -> its crops in loader order: ops.decode_crop for the compressed files,
-    in the channel order _imread gives for COLOR_RGB, ops.crop_warp for the windows of the rows the loader decoded itself."""
+    in the channel order _imread gives for COLOR_RGB, ops.crop_warp for the windows of the rows the loader decoded itself.
+    png: the data set's device_decode_png -- PNG files are among the compressed ones."""
     size_wh = (int(config.MODEL.IMAGE_SIZE[0]), int(config.MODEL.IMAGE_SIZE[1]))
     trans, rows, offs = meta["trans"].numpy(), frames["file_rows"], frames["file_offsets"].tolist()
     files = [frames["files"][offs[k]:offs[k + 1]] for k in range(len(offs) - 1)]
-    crops, _ = ops.decode_crop(files, trans[rows.numpy()], size_wh, rgb=bool(config.DATASET.COLOR_RGB), device=dev)
+    crops, _ = ops.decode_crop(files, trans[rows.numpy()], size_wh, rgb=bool(config.DATASET.COLOR_RGB), device=dev, png=png)
     if "window_rows" not in frames:
         return crops                # collate keeps the files in row order
     wrows = frames["window_rows"]
@@ -168,9 +169,12 @@ def _run(config, val_loader, val_dataset, models, criterion, output_dir, pred_fi
         end = time.time()
         for i, (input, target, target_weight, meta) in enumerate(val_loader):
             if isinstance(input, dict) and "files" in input:   # dataset.device_decode: compressed files -> uint8 NHWC crops on the GPU
-                if i == 0:
+                png = bool(getattr(val_dataset, "device_decode_png", False))
+                if i == 0 and getattr(val_dataset, "device_decode", True):
                     logger.info("validate: baseline JPEG frames are decoded on the device, straight into the crops (ops.decode_crop)")
-                input = _decode_crops(config, input, meta, dev)
+                if i == 0 and png:
+                    logger.info("validate: PNG frames are decoded on the device, straight into the crops (ops.decode_crop, png=True)")
+                input = _decode_crops(config, input, meta, dev, png=png)
             elif isinstance(input, (list, tuple, dict)):   # dataset.device_crop: frame windows -> uint8 NHWC crops on the GPU
                 size_wh = config.MODEL.IMAGE_SIZE
                 input = ops.crop_warp(input, meta["trans"].numpy(), (int(size_wh[0]), int(size_wh[1])), device=dev,

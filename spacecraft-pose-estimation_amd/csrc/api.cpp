@@ -335,6 +335,73 @@ extern "C" int32_t scpose_jpeg_decode_crop(const uint8_t* desc, const int32_t* s
                                  out_w, crops, status, static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
 }
 
+static int32_t png_check_shape(const char* who, int32_t n, int32_t h, int32_t w, int32_t channels) {
+  SCP_REQUIRE(n >= 0 && n <= 65535, "%s: n=%d (0 .. 65535)", who, n);
+  SCP_REQUIRE(h >= 1 && h <= 65535 && w >= 1 && w <= 65535, "%s: frame %dx%d (HxW), each 1 .. 65535", who, h, w);
+  SCP_REQUIRE(channels >= 1 && channels <= 4, "%s: channels=%d (1 .. 4)", who, channels);
+  return SCPOSE_OK;
+}
+
+// the descriptors are host memory: every stream must lie inside `data` and every image must have the call's geometry
+static int32_t png_check_desc(const char* who, const uint8_t* desc, int64_t n_bytes, int32_t n, int32_t h, int32_t w, int32_t channels) {
+  for (int32_t i = 0; i < n; ++i) {
+    int64_t q[2];
+    int32_t v[4];
+    memcpy(q, desc + (size_t)i * SCPOSE_PNG_DESC_BYTES, sizeof q);
+    memcpy(v, desc + (size_t)i * SCPOSE_PNG_DESC_BYTES + 16, sizeof v);
+    SCP_REQUIRE(q[0] >= 0 && q[1] >= 0 && (q[0] & 3) == 0 && q[0] <= n_bytes && q[1] <= n_bytes - q[0],
+                "%s: descriptor %d: the stream [%lld, +%lld) does not lie inside the %lld bytes of data on a 4-byte boundary", who, i,
+                (long long)q[0], (long long)q[1], (long long)n_bytes);
+    SCP_REQUIRE(v[0] == h && v[1] == w && v[3] == channels, "%s: descriptor %d is of a %dx%d frame with %d channels, the call of %dx%d with %d",
+                who, i, v[0], v[1], v[3], h, w, channels);
+    SCP_REQUIRE(v[2] == 0 || v[2] == 2 || v[2] == 3 || v[2] == 4 || v[2] == 6, "%s: descriptor %d: colour type %d", who, i, v[2]);
+  }
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_png_decode_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t channels, size_t* bytes) {
+  SCP_REQUIRE(bytes, "png_decode_workspace_bytes: null argument");
+  if (int32_t rc = png_check_shape("png_decode_workspace_bytes", n, h, w, channels)) return rc;
+  *bytes = png_decode_workspace_bytes(n, h, w, channels);
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_png_decode(const uint8_t* desc, const uint8_t* data, int64_t n_bytes, int32_t n, int32_t h, int32_t w,
+                                     int32_t channels, int32_t bgr, uint8_t* out, int32_t* status, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+  if (n == 0) return SCPOSE_OK;
+  if (int32_t rc = png_check_shape("png_decode", n, h, w, channels)) return rc;
+  SCP_REQUIRE(desc && (data || n_bytes == 0) && out && status && n_bytes >= 0, "png_decode: null argument");
+  SCP_REQUIRE(aligned(data, 4) && aligned(status, 4), "png_decode: data and status must be 4-byte aligned");
+  if (int32_t rc = png_check_desc("png_decode", desc, n_bytes, n, h, w, channels)) return rc;
+  if (int32_t rc = workspace_ok("png_decode", workspace, workspace_bytes, png_decode_workspace_bytes(n, h, w, channels), 256)) return rc;
+  return png_decode_launch(desc, data, n, h, w, channels, bgr != 0, out, status, static_cast<uint8_t*>(workspace),
+                           static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t scpose_png_decode_crop(const uint8_t* desc, const uint8_t* data, int64_t n_bytes, int32_t n, int32_t h, int32_t w,
+                                          int32_t channels, int32_t bgr, const double* minv, const int32_t* roi_xywh, int32_t out_h,
+                                          int32_t out_w, uint8_t* crops, int32_t* status, void* workspace, size_t workspace_bytes,
+                                          void* stream) {
+  if (n == 0) return SCPOSE_OK;
+  if (int32_t rc = png_check_shape("png_decode_crop", n, h, w, channels)) return rc;
+  SCP_REQUIRE(out_h >= 1 && out_w >= 1 && out_h <= 65535 && out_w <= 65535, "png_decode_crop: bad output size %dx%d (each 1 .. 65535)", out_h,
+              out_w);
+  SCP_REQUIRE(desc && (data || n_bytes == 0) && minv && roi_xywh && crops && status && n_bytes >= 0, "png_decode_crop: null argument");
+  SCP_REQUIRE(aligned(data, 4) && aligned(status, 4) && aligned(minv, 8),
+              "png_decode_crop: data and status must be 4-byte aligned, minv 8-byte aligned");
+  if (int32_t rc = png_check_desc("png_decode_crop", desc, n_bytes, n, h, w, channels)) return rc;
+  for (int32_t i = 0; i < n; ++i) {      // roi_xywh is host memory: the window bounds the rows the crop kernel reads
+    const int32_t* r = roi_xywh + 4 * (size_t)i;
+    SCP_REQUIRE(r[0] >= 0 && r[1] >= 0 && r[2] >= 0 && r[3] >= 0 && (int64_t)r[0] + r[2] <= w && (int64_t)r[1] + r[3] <= h,
+                "png_decode_crop: roi %d = [%d, %d, %d, %d] (x, y, w, h) is not inside the %dx%d (HxW) frame", i, r[0], r[1], r[2], r[3], h, w);
+  }
+  if (int32_t rc = workspace_ok("png_decode_crop", workspace, workspace_bytes, png_decode_workspace_bytes(n, h, w, channels), 256))
+    return rc;
+  return png_decode_crop_launch(desc, data, n, h, w, channels, bgr != 0, minv, roi_xywh, out_h, out_w, crops, status,
+                                static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
 static int32_t jpeg_encode_check_shape(int32_t n, int32_t h, int32_t w, int32_t mode, const char* who) {
   if (int32_t rc = jpeg_frame_ok(who, n, h, w, mode)) return rc;
   SCP_REQUIRE(jpeg_blocks(h, w, mode) * 2800 < ((int64_t)1 << 31),

@@ -310,6 +310,13 @@ int32_t jpeg_decode_crop_launch(const uint8_t* desc, const int32_t* segs, int64_
 // jpeg_encode.hip: (N, H, W, 3) uint8 frames -> baseline JPEG byte streams; the overlay draw in front of it
 size_t jpeg_encode_workspace_bytes(int n, int h, int w, int mode);
 int64_t jpeg_encode_capacity_bytes(int n, int h, int w, int mode, int header_bytes);
+// png_decode.hip: desc_host is host memory (n descriptors of SCPOSE_PNG_DESC_BYTES), uploaded into the workspace on `stream`
+size_t png_decode_workspace_bytes(int n, int h, int w, int channels);
+int32_t png_decode_launch(const uint8_t* desc_host, const uint8_t* data, int n, int h, int w, int channels, int bgr, uint8_t* out,
+                          int32_t* status, uint8_t* ws, hipStream_t stream);
+int32_t png_decode_crop_launch(const uint8_t* desc_host, const uint8_t* data, int n, int h, int w, int channels, int bgr, const double* minv,
+                               const int32_t* roi_host, int out_h, int out_w, uint8_t* crops, int32_t* status, uint8_t* ws,
+                               hipStream_t stream);
 int32_t jpeg_encode_launch(const uint8_t* frames, int n, int h, int w, int mode, int quality, const uint32_t* huff, const uint8_t* header,
                            int header_bytes, uint8_t* out, int64_t capacity, int64_t* offsets, int32_t* status, uint8_t* ws,
                            hipStream_t stream);

@@ -64,6 +64,8 @@ class JointsDataset(Dataset):
         self.device_crop = False   # True: hand whole frames to the GPU crop kernel instead of warping here
         # True (needs device_crop): hand the bytes of baseline JPEG files to the GPU decoder instead of decoding here
         self.device_decode = bool(getattr(cfg.DATASET, "DEVICE_DECODE", False))
+        # True (needs device_crop, with or without device_decode): the same for PNG files (8-bit, not interlaced) and the GPU PNG decoder
+        self.device_decode_png = bool(getattr(cfg.DATASET, "DEVICE_DECODE_PNG", False))
         self.want_target = True    # False: skip generate_target (the maps feed only the loss / PCK that validate() logs)
         self.db = []
 
@@ -103,7 +105,7 @@ class JointsDataset(Dataset):
         image_file = db_rec["image"]
         if self.data_format == "zip":
             raise ValueError("DATA_FORMAT 'zip' is not supported (unused by the shipped configs)")
-        raw = self._read_compressed(image_file) if self.device_decode else None
+        raw = self._read_compressed(image_file) if (self.device_decode or self.device_decode_png) else None
         if raw is None:
             data_numpy = _imread(image_file, bool(self.color_rgb))      # BGR as cv2.imread gives it, or RGB when COLOR_RGB (:149-150)
             if data_numpy is None:
@@ -150,9 +152,12 @@ class JointsDataset(Dataset):
         return input, torch.from_numpy(target), torch.from_numpy(target_weight), meta
 
     def _read_compressed(self, image_file):
-        """device_decode: (the file's bytes, frame height, frame width) when the device decodes it (jpeg_read.parse_jpeg accepts it:
-        a baseline JPEG), None when the file goes the way of device_crop (PIL here, the window travels)."""
+        """device_decode / device_decode_png: (the file's bytes, frame height, frame width) when the device decodes it -- a baseline
+        JPEG under device_decode (jpeg_read.parse_jpeg accepts it), a PNG of the decoded subset under device_decode_png
+        (png_read.parse_png accepts it and its chunks pass their CRCs) --, None when the file goes the way of device_crop (PIL here,
+        the window travels)."""
         from ..jpeg_read import JpegError, parse_jpeg
+        from ..png_read import UnsupportedPng, parse_png
         if not self.device_crop:
             raise ValueError("device_decode needs device_crop: the device decodes a frame straight into its crop")
         if self.numpy_transform:
@@ -160,8 +165,22 @@ class JointsDataset(Dataset):
         try:
             with open(image_file, "rb") as fh:
                 raw = fh.read()
-            head = parse_jpeg(raw)
-        except (OSError, JpegError):
+        except OSError:
+            return None
+        head = None
+        if self.device_decode:
+            try:
+                head = parse_jpeg(raw)
+            except JpegError:
+                pass
+        if head is None and self.device_decode_png:
+            try:
+                head = parse_png(raw)
+                if not head.crc_ok:
+                    head = None
+            except UnsupportedPng:
+                pass
+        if head is None:
             return None
         return raw, int(head.height), int(head.width)
 

@@ -555,16 +555,21 @@ def _jpeg_decode_group(headers, files, rgb, max_rounds, dev, out=None, y_out=Non
         return out, status.tolist()
 
 
-def _jpeg_host_decode(data, rgb):
+def _pil_decode(data, rgb):
+    """The host decoder of every image format: PIL's pixels as (H, W, 3) uint8, or whatever PIL raises."""
     import io
     from PIL import Image
+    with Image.open(io.BytesIO(data)) as im:
+        arr = np.array(im.convert("RGB"))              # a copy: the decoder's own array is read-only
+    return arr if rgb else arr[:, :, ::-1].copy()
+
+
+def _jpeg_host_decode(data, rgb):
     from . import jpeg_read as jr
     try:
-        with Image.open(io.BytesIO(data)) as im:
-            arr = np.array(im.convert("RGB"))          # a copy: the decoder's own array is read-only
+        return _pil_decode(data, rgb)
     except Exception as e:
         raise jr.JpegError("decode_jpeg: the host decoder cannot read the file either: %s" % e)
-    return arr if rgb else arr[:, :, ::-1].copy()
 
 
 def _jpeg_device(device, who):
@@ -574,10 +579,8 @@ def _jpeg_device(device, who):
     return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
 
 
-def _jpeg_parse(files, fallback, who, key):
-    """files (bytes, uint8 arrays / tensors or paths) -> (blobs, headers, host, groups): the bytes of each file, its JpegHeader or
-    None, {index: reason} for the files jpeg_read.parse_jpeg refuses, and {key(header): [indices]}, one device call each."""
-    from . import jpeg_read as jr
+def _file_blobs(files, who):
+    """files (bytes, uint8 arrays / tensors or paths) -> the bytes of each"""
     blobs = []
     for f in files:
         if isinstance(f, (bytes, bytearray, memoryview)):
@@ -591,6 +594,14 @@ def _jpeg_parse(files, fallback, who, key):
                 blobs.append(fh.read())
     if not blobs:
         raise ValueError("%s: no files" % who)
+    return blobs
+
+
+def _jpeg_parse(files, fallback, who, key):
+    """files (bytes, uint8 arrays / tensors or paths) -> (blobs, headers, host, groups): the bytes of each file, its JpegHeader or
+    None, {index: reason} for the files jpeg_read.parse_jpeg refuses, and {key(header): [indices]}, one device call each."""
+    from . import jpeg_read as jr
+    blobs = _file_blobs(files, who)
     headers, host, groups = [None] * len(blobs), {}, {}
     for i, b in enumerate(blobs):
         try:
@@ -654,20 +665,67 @@ def decode_jpeg(files, rgb=True, device=None, max_rounds=None, fallback=True):
     return out, info
 
 
-def decode_crop(files, trans, out_wh, rgb=True, device=None, max_rounds=None, fallback=True):
+def decode_crop(files, trans, out_wh, rgb=True, device=None, max_rounds=None, fallback=True, png=False):
     """Image files -> ((N, H, W, 3) uint8 network crops on the device, info): row i is crop_warp(frame_i, trans[i], out_wh) of the frame
     PIL decodes from files[i] -- for a baseline JPEG, of decode_jpeg's frame -- bit for bit, without that frame: after the entropy
     decoding csrc/jpeg_decode.hip transforms only the blocks the warp's window (warp_window) can read and samples the planes.
     files as for decode_jpeg (frame sizes may differ); trans (N, 2, 3) as for crop_warp; out_wh = (W, H); rgb: the channel order.
     info as decode_jpeg's.  A file jpeg_read.parse_jpeg refuses (PNG, progressive JPEG, ...) and one whose entry states have not
-    converged is decoded by PIL on the host when `fallback` and its row filled by crop_warp; a corrupt stream raises JpegError."""
+    converged is decoded by PIL on the host when `fallback` and its row filled by crop_warp; a corrupt stream raises JpegError.
+    png=True: a file parse_jpeg refuses is offered to png_read.parse_png; one it accepts is inflated, unfiltered and sampled by
+    csrc/png_decode.hip (rounds 0), info gains "png": the indices decoded that way; a PNG whose status word is not 0 takes the PIL row
+    (PngError when PIL raises, or at once without `fallback`).  png=False: a PNG is just a file parse_jpeg refuses."""
     from .utils.transforms import invert_affine_cv
     dev, rounds_cap = _jpeg_device(device, "decode_crop"), JPEG_MAX_ROUNDS if max_rounds is None else int(max_rounds)
-    blobs, headers, host, groups = _jpeg_parse(files, fallback, "decode_crop", lambda h: h.geometry)
+    blobs, headers, host, groups = _jpeg_parse(files, fallback or png, "decode_crop", lambda h: h.geometry)
     n = len(blobs)
     trans = np.asarray(trans, dtype=np.float64).reshape(n, 2, 3)
     ow, oh = int(out_wh[0]), int(out_wh[1])
     rounds, parts = [0] * n, []            # parts: (row indices, crops of those rows)
+    png_rows, png_host = [], set()         # decoded by png_decode.hip; PNGs the host decodes after all
+    if png:
+        from . import jpeg_read as jr, png_read as pr
+        png_headers, png_groups = {}, {}
+        for i in sorted(host):
+            try:
+                hd = pr.parse_png(blobs[i])
+            except pr.UnsupportedPng as e:
+                is_png = blobs[i][:8] == pr.SIGNATURE
+                if is_png:
+                    host[i] = str(e)                   # a PNG outside the subset: its own reason, not "not a JPEG"
+                    png_host.add(i)                    # ... and PngError, not JpegError, should PIL not read it either
+                if not fallback:
+                    if is_png:
+                        raise
+                    raise jr.UnsupportedJpeg(host[i])  # neither format: what png=False raises for the file
+                continue
+            if not hd.crc_ok:
+                if not fallback:
+                    raise pr.PngError("decode_crop: file %d: a chunk fails its CRC" % i)
+                host[i] = "a chunk fails its CRC"
+                png_host.add(i)
+                continue
+            png_headers[i] = hd
+            png_groups.setdefault(hd.geometry, []).append(i)
+            del host[i]
+        for geom, idx in png_groups.items():
+            minv = np.stack([np.asarray(invert_affine_cv(trans[i]), dtype=np.float64).reshape(6) for i in idx])
+            roi = np.array([warp_window(trans[i], (ow, oh), geom[:2]) for i in idx], dtype=np.int32)
+            crops, status = _png_decode_group([png_headers[i] for i in idx], [blobs[i] for i in idx], rgb, dev, crop=(minv, roi, oh, ow))
+            keep = []
+            for row, i in enumerate(idx):
+                if status[row] == 0:
+                    keep.append(row)
+                    continue
+                if not fallback:
+                    raise pr.PngError("decode_crop: file %d: %s" % (i, _png_status_words(status[row])))
+                host[i] = _png_status_words(status[row])
+                png_host.add(i)
+            if len(keep) < len(idx):
+                crops, idx = crops[torch.tensor(keep, dtype=torch.int64, device=dev)], [idx[row] for row in keep]
+            if idx:
+                parts.append((idx, crops))
+                png_rows += idx
     for geom, idx in groups.items():
         minv = np.stack([np.asarray(invert_affine_cv(trans[i]), dtype=np.float64).reshape(6) for i in idx])
         roi = np.array([warp_window(trans[i], (ow, oh), geom[:2]) for i in idx], dtype=np.int32)
@@ -681,14 +739,113 @@ def decode_crop(files, trans, out_wh, rgb=True, device=None, max_rounds=None, fa
             parts.append((idx, crops))
     if host:
         idx = sorted(host)
-        parts.append((idx, crop_warp([_jpeg_host_decode(blobs[i], rgb) for i in idx], trans[idx], (ow, oh), device=dev)))
+        parts.append((idx, crop_warp([_png_host_decode(blobs[i], rgb, "decode_crop", i) if i in png_host else _jpeg_host_decode(blobs[i], rgb)
+                                      for i in idx], trans[idx], (ow, oh), device=dev)))
     info = {"rounds": rounds, "fallback": host}
+    if png:
+        info["png"] = sorted(png_rows)
     if len(parts) == 1 and parts[0][0] == list(range(n)):
         return parts[0][1], info
     with torch.cuda.device(dev):
         out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=dev)
         for idx, crops in parts:
             out.index_copy_(0, torch.tensor(idx, dtype=torch.int64, device=dev), crops)
+    return out, info
+
+
+# ------------------------------------------------------------------ PNG files -> frames
+def _png_status_words(st):
+    names = [w for bit, w in ((nat.PNG_CORRUPT, "corrupt deflate stream"), (nat.PNG_CHECKSUM, "Adler-32 mismatch"),
+                              (nat.PNG_FILTER, "filter type above 4")) if st & bit]
+    return "device status %d (%s)" % (st, ", ".join(names))
+
+
+def _png_host_decode(data, rgb, who, i):
+    from . import png_read as pr
+    try:
+        return _pil_decode(data, rgb)
+    except Exception as e:
+        raise pr.PngError("%s: file %d: %s" % (who, i, e))
+
+
+def _png_decode_group(headers, files, rgb, dev, crop=None):
+    """One device call on the current stream for PNGs of one geometry; -> (frames, status list): scpose_png_decode, or with
+    crop = (minv float64 (n, 6), roi int32 (n, 4), out_h, out_w) scpose_png_decode_crop -> (crops, status list)."""
+    from . import png_read as pr
+    h, w, channels = headers[0].geometry
+    n = len(headers)
+    desc, data = pr.pack_batch(headers, files)         # desc stays on the host: the library checks and uploads it
+    lib = nat.lib()
+    ws = _query_bytes("png_decode_workspace_bytes", n, h, w, channels)
+    with torch.cuda.device(dev):
+        d_data = torch.from_numpy(data).to(dev, non_blocking=True)
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        work = _jpeg_workspace(dev, ws)
+        front = (c_void_p(desc.ctypes.data), _ptr(d_data), int(data.size), n, h, w, channels, 0 if rgb else 1)
+        if crop is None:
+            out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+            nat.check(lib.scpose_png_decode(*front, _ptr(out), _ptr(status), _ptr(work), ws, _stream()), "png_decode")
+        else:
+            minv, roi, oh, ow = crop
+            d_minv = torch.from_numpy(np.ascontiguousarray(minv, dtype=np.float64)).to(dev, non_blocking=True)
+            roi = np.ascontiguousarray(roi, dtype=np.int32)      # host memory: read before the call returns
+            out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=dev)
+            nat.check(lib.scpose_png_decode_crop(*front, _ptr(d_minv), c_void_p(roi.ctypes.data), oh, ow, _ptr(out), _ptr(status),
+                                                 _ptr(work), ws, _stream()), "png_decode_crop")
+        return out, status.tolist()                    # the copy back waits for the stream: desc has been read by then
+
+
+def decode_png(files, rgb=True, device=None, fallback=True):
+    """PNG files -> ((N, H, W, 3) uint8 frames on the device, info), decoded by csrc/png_decode.hip bit for bit as PIL's
+    Image.open(f).convert("RGB") decodes them.  files: a list of bytes or of paths; all frames must have one size.  rgb: R, G, B order,
+    else B, G, R.  Files are grouped by (height, width, channels) and every group is one call.
+    info = {"device": per file whether the device decoded it, "fallback": {index: reason}}.
+    A file png_read.parse_png refuses (interlaced, 1/2/4/16-bit, APNG, not a PNG), one that fails a chunk CRC and one whose status word
+    is not 0 are the host decoder's: PIL returns pixels (bytes after the stream, say) or raises, and a raise becomes PngError with PIL's
+    message -- the device never decides what a damaged file means.  fallback=False: UnsupportedPng / PngError at once."""
+    from . import png_read as pr
+    dev = _jpeg_device(device, "decode_png")
+    blobs = _file_blobs(files, "decode_png")
+    n = len(blobs)
+    headers, host, groups = [None] * n, {}, {}
+    for i, b in enumerate(blobs):
+        try:
+            headers[i] = pr.parse_png(b)
+        except pr.UnsupportedPng as e:
+            if not fallback:
+                raise
+            host[i] = str(e)
+            continue
+        if not headers[i].crc_ok:
+            if not fallback:
+                raise pr.PngError("decode_png: file %d: a chunk fails its CRC" % i)
+            host[i] = "a chunk fails its CRC"
+            continue
+        groups.setdefault(headers[i].geometry, []).append(i)
+    decoded = {}                    # index -> (group tensor, row)
+    for geom, idx in groups.items():
+        frames, status = _png_decode_group([headers[i] for i in idx], [blobs[i] for i in idx], rgb, dev)
+        for row, i in enumerate(idx):
+            if status[row] == 0:
+                decoded[i] = (frames, row)
+            elif not fallback:
+                raise pr.PngError("decode_png: file %d: %s" % (i, _png_status_words(status[row])))
+            else:
+                host[i] = _png_status_words(status[row])
+    host_px = {i: _png_host_decode(blobs[i], rgb, "decode_png", i) for i in host}
+    sizes = {(headers[i].height, headers[i].width) for i in decoded} | {a.shape[:2] for a in host_px.values()}
+    if len(sizes) != 1:
+        raise ValueError("decode_png: the frames have different sizes %s: decode them in separate calls" % sorted(sizes))
+    info = {"device": [i in decoded for i in range(n)], "fallback": host}
+    if len(groups) == 1 and not host:
+        return next(iter(decoded.values()))[0], info
+    (hh, ww), = sizes
+    with torch.cuda.device(dev):
+        out = torch.empty((n, hh, ww, 3), dtype=torch.uint8, device=dev)
+        for i, (frames, row) in decoded.items():
+            out[i].copy_(frames[row])
+        for i, arr in host_px.items():
+            out[i].copy_(torch.from_numpy(np.ascontiguousarray(arr)))
     return out, info
 
 

@@ -1,0 +1,130 @@
+"""ops.decode_crop(png=True) / scpose_png_decode_crop: the crop of a PNG equals crop_warp of PIL's frame, PNGs and JPEGs share a batch,
+and png=False is today's decode_crop."""
+import io
+
+import numpy as np
+import pytest
+import torch
+from PIL import Image
+
+import jpeg_crop_cases as C
+import png_stream_writer as W
+
+pytestmark = pytest.mark.gpu
+
+
+def pil_rgb(data):
+    with Image.open(io.BytesIO(data)) as im:
+        return np.array(im.convert("RGB"))
+
+
+def png_frame(size, color_type, seed):
+    rng = np.random.default_rng(seed)
+    shape = size if W.CHANNELS[color_type] == 1 else size + (W.CHANNELS[color_type],)
+    px = rng.integers(0, 256, shape, dtype=np.uint8)
+    return W.write_png(px, color_type, "random", palette=rng.integers(0, 256, (200, 3), dtype=np.uint8) if color_type == 3 else None, rng=rng)[0]
+
+
+def reference(gpu_ops, frames, trans):
+    return gpu_ops.crop_warp([np.ascontiguousarray(f) for f in frames], trans, C.CROP_WH)
+
+
+@pytest.mark.parametrize("color_type", W.COLOR_TYPES)
+@pytest.mark.parametrize("size", C.SIZES)
+def test_crop_equals_crop_warp_of_the_pil_frame(gpu_ops, color_type, size):
+    data = png_frame(size, color_type, 7)
+    frame = pil_rgb(data)
+    cases = C.affines(size)
+    trans = np.stack(list(cases.values()))
+    got, info = gpu_ops.decode_crop([data] * len(cases), trans, C.CROP_WH, fallback=False, png=True)
+    assert got.dtype == torch.uint8 and tuple(got.shape) == (len(cases), C.CROP_WH[1], C.CROP_WH[0], 3) and got.is_cuda
+    assert info["png"] == list(range(len(cases))) and info["fallback"] == {} and info["rounds"] == [0] * len(cases)
+    want = reference(gpu_ops, [frame] * len(cases), trans)
+    bad = [name for i, name in enumerate(cases) if not torch.equal(got[i], want[i])]
+    assert not bad, bad
+    assert not bool(got[list(cases).index("outside")].any())
+    bgr, _ = gpu_ops.decode_crop([data] * len(cases), trans, C.CROP_WH, rgb=False, fallback=False, png=True)
+    assert torch.equal(bgr, got.flip(3))
+
+
+def mixed_batch():
+    size = C.SIZES[0]
+    jpeg, jpeg_frame = C.frame("420", size)
+    buf = io.BytesIO()
+    Image.fromarray(jpeg_frame).save(buf, format="JPEG", quality=90, progressive=True)
+    progressive = buf.getvalue()
+    png = png_frame(size, 2, 11)
+    # 1 x 1 has a single Adam7 pass, whose data is the non-interlaced data: a valid interlaced file without an Adam7 writer
+    interlaced = W.assemble(1, 1, 0, W.deflate(b"\x00\x9c"), interlace=1)
+    files = [jpeg, png, progressive, interlaced, png_frame(C.SIZES[1], 3, 12)]
+    frames = [pil_rgb(f) for f in files]
+    names = list(C.affines(size))
+    trans = np.stack([C.affines(f.shape[:2])[names[i % 4]] for i, f in enumerate(frames)])
+    trans[3] = np.array([[1.0, 0.0, 2.0], [0.0, 1.0, 3.0]])               # the one pixel lands inside the crop
+    return files, frames, trans
+
+
+def test_pngs_jpegs_and_refused_files_in_one_batch(gpu_ops):
+    files, frames, trans = mixed_batch()
+    assert frames[3].shape == (1, 1, 3) and int(frames[3][0, 0, 0]) == 0x9c
+    want = reference(gpu_ops, frames, trans)
+    got, info = gpu_ops.decode_crop(files, trans, C.CROP_WH, png=True)
+    assert torch.equal(got, want)
+    assert info["png"] == [1, 4] and sorted(info["fallback"]) == [2, 3]
+    assert "progressive" in info["fallback"][2] and "interlac" in info["fallback"][3]
+    assert info["rounds"][0] >= 1 and info["rounds"][1:] == [0, 0, 0, 0]
+    # png=False: today's treatment, field for field
+    old, old_info = gpu_ops.decode_crop(files, trans, C.CROP_WH)
+    assert torch.equal(old, want) and sorted(old_info) == ["fallback", "rounds"] and old_info["rounds"] == info["rounds"]
+    assert sorted(old_info["fallback"]) == [1, 2, 3, 4] and "progressive" in old_info["fallback"][2]
+    assert all("not a JPEG" in old_info["fallback"][i] for i in (1, 3, 4))
+    with pytest.raises(ValueError, match="progressive"):
+        gpu_ops.decode_crop(files, trans, C.CROP_WH, fallback=False, png=True)
+
+
+def test_a_damaged_png_takes_the_pil_row(gpu_ops):
+    d = W.damaged_cases()
+    files = [d["long_raw"], d["garbage_after_stream"], d["idat_crc"]]
+    frames = [pil_rgb(f) for f in files]
+    trans = np.stack([C.affines(frames[0].shape[:2])["scale_1_fractional"]] * 3)
+    trans[:, :, 2] = 0.0
+    got, info = gpu_ops.decode_crop(files, trans, C.CROP_WH, png=True)
+    assert torch.equal(got, reference(gpu_ops, frames, trans))
+    assert info["png"] == [0, 1] and list(info["fallback"]) == [2] and "CRC" in info["fallback"][2]
+    bad = [d["long_raw"], d["filter_5"]]
+    import importlib
+    pr = importlib.import_module("spacecraft-pose-estimation_amd.png_read")
+    with pytest.raises(pr.PngError, match="file 1"):
+        gpu_ops.decode_crop(bad, trans[:2], C.CROP_WH, png=True)
+    with pytest.raises(pr.PngError, match="filter"):
+        gpu_ops.decode_crop(bad, trans[:2], C.CROP_WH, png=True, fallback=False)
+
+
+def test_a_refused_png_pil_cannot_read_raises_png_error(gpu_ops):
+    """an interlaced header over plain data: parse_png refuses it, PIL cannot read it -- the error is a PNG error, not a JPEG one"""
+    import importlib
+    pr = importlib.import_module("spacecraft-pose-estimation_amd.png_read")
+    broken = W.refused_cases()["interlaced"][0]
+    with pytest.raises(OSError):
+        pil_rgb(broken)
+    trans = np.array([[[1.0, 0.0, 0.0], [0.0, 1.0, 0.0]]] * 2)
+    with pytest.raises(pr.PngError, match="decode_crop: file 1"):
+        gpu_ops.decode_crop([W.accepted_cases()["type0"], broken], trans, C.CROP_WH, png=True)
+    jr = importlib.import_module("spacecraft-pose-estimation_amd.jpeg_read")
+    with pytest.raises(jr.JpegError, match="decode_jpeg"):                                   # png=False: today's error
+        gpu_ops.decode_crop([W.accepted_cases()["type0"], broken], trans, C.CROP_WH)
+
+
+def test_whatever_the_workspace_held(gpu_ops):
+    size = C.SIZES[0]
+    files = [png_frame(size, ct, 20 + ct) for ct in W.COLOR_TYPES]
+    names = list(C.affines(size))
+    trans = np.stack([C.affines(size)[names[i % 4]] for i in range(len(files))])
+    dev = torch.cuda.current_device()
+    first, _ = gpu_ops.decode_crop(files, trans, C.CROP_WH, fallback=False, png=True)
+    got = []
+    for fill in (0x00, 0xFF):
+        gpu_ops._JPEG_WORKSPACE[dev].fill_(fill)
+        got.append(gpu_ops.decode_crop(files, trans, C.CROP_WH, fallback=False, png=True)[0])
+    assert torch.equal(got[0], got[1]) and torch.equal(got[0], first)
+    assert torch.equal(first, reference(gpu_ops, [pil_rgb(f) for f in files], trans))
