@@ -426,6 +426,46 @@ int32_t scpose_events_aedat2_unpack(const uint8_t* records, int64_t n_records, i
                                     int64_t* t, int32_t* x, int32_t* y, int8_t* p, int64_t capacity,
                                     int64_t* count_status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* (ABI 7, additive) The event packets of an AEDAT-4.0 recording on the device (csrc/events_aedat4_read.hip, which states the format):
+ * the whole file and one descriptor per event packet -> the four columns, events in file order.  The host reads the IOHeader and
+ * walks the packet headers (event_read.parse_aedat4).  Four calls on one workspace, in this order; _measure and _decode only when
+ * the payloads are LZ4 frames (compression LZ4 / LZ4_HIGH), and two small read-backs size the buffers between them:
+ *   _measure   one wavefront per packet walks the frame without copying; total_status device i64 [2] <- [staging bytes, status].
+ *              Read back; allocate `staging` of that many bytes (a multiple of 16, 0 included).
+ *   _decode    one wavefront per packet decodes its frame into its piece of `staging` (staging_bytes long: a packet whose piece
+ *              does not lie inside it is not decoded and reported CORRUPT); verify != 0 checks the block and content
+ *              checksums the frame carries.  What it finds joins the packets' status words, reported by _count.
+ *   _count     staged != 0: `src` is the staging buffer of _decode; 0: `src` is the file and the payloads are raw flatbuffers.
+ *              Walks each payload's flatbuffer down to the event vector's count.  count_status device i64 [6] <- [n_events, status,
+ *              t of the first event, 0, 0, 0]; n_events = 0 unless status is 0.  Read back; allocate the columns.
+ *   _unpack    src as given to _count.  The structs -> t (minus the first t when rebase != 0), x, y, p = (on != 0).  Adds to
+ *              count_status [3] n_backward (events whose t is below their predecessor's) and [4] n_out_of_range (x outside [0, w)
+ *              or y outside [0, h); sets SCPOSE_AEDAT4_RANGE).  Writes nothing unless status was 0 and n_events <= capacity
+ *              (else SCPOSE_AEDAT4_CAPACITY).  Read count_status back once more for the counters.
+ *   file       device u8, the recording; packets: device i64 [n_packets][2], (payload offset in file, payload size), each payload
+ *              inside the file -- the caller's duty, the kernels check every read against the payload only
+ *   status     SCPOSE_AEDAT4_CORRUPT: a frame with a wrong magic, version, reserved bit, block maximum or HC, a dictionary id, a
+ *              block or sequence that overruns its input, an offset of 0 or before the start of the output (of the block, when
+ *              blocks are independent), a block that decodes past its maximum, a content size that differs, a packet that decodes
+ *              to more than 2^23 - 16 bytes (the sizes are rounded up to 16 and 256 of them summed in an int32).  _CHECKSUM: a block or content checksum differs.  _FLATBUFFER: no "EVTS" identifier, or a step of
+ *              the walk leaves the payload, or 2^23 events or more in one packet.  The kernels detect and never interpret.
+ *   workspace  caller-owned, 16-byte aligned, scpose_events_aedat4_workspace_bytes(n_packets) (never 0), the SAME for all four calls
+ * Argument errors (null pointers, n_packets < 0 or above 2^31 - 1, h or w outside 1 .. 32767, a misaligned or short workspace)
+ * return -1 with a message before anything is launched.  No allocation, no synchronisation, no atomics on the columns, integer
+ * work only; two runs on the same bytes give bitwise equal outputs. */
+enum { SCPOSE_AEDAT4_CORRUPT = 1, SCPOSE_AEDAT4_CHECKSUM = 2, SCPOSE_AEDAT4_FLATBUFFER = 4, SCPOSE_AEDAT4_RANGE = 8,
+       SCPOSE_AEDAT4_CAPACITY = 16 };
+int32_t scpose_events_aedat4_workspace_bytes(int64_t n_packets, size_t* bytes);
+int32_t scpose_events_aedat4_measure(const uint8_t* file, const int64_t* packets, int64_t n_packets, int64_t* total_status,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+int32_t scpose_events_aedat4_decode(const uint8_t* file, const int64_t* packets, int64_t n_packets, uint8_t* staging,
+                                    int64_t staging_bytes, int32_t verify, void* workspace, size_t workspace_bytes, void* stream);
+int32_t scpose_events_aedat4_count(const uint8_t* src, const int64_t* packets, int64_t n_packets, int32_t staged,
+                                   int64_t* count_status, void* workspace, size_t workspace_bytes, void* stream);
+int32_t scpose_events_aedat4_unpack(const uint8_t* src, int64_t n_packets, int32_t h, int32_t w, int32_t rebase, int64_t* t, int32_t* x,
+                                    int32_t* y, int8_t* p, int64_t capacity, int64_t* count_status, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+
 /* (ABI 7, additive) Baseline JPEG files on the device (csrc/jpeg_decode.hip): the bytes of N files of one geometry -> (N, H, W, 3)
  * uint8 frames, bit for bit what libjpeg's baseline decoder returns (Huffman decoding, jidctint.c's ISLOW inverse DCT, jdsample.c's
  * fancy h2v2 upsampling, jdcolor.c's YCbCr -> RGB).  Decoded: SOF0, 8 bits, one interleaved scan, one component (SCPOSE_JPEG_GRAY)

@@ -266,6 +266,64 @@ extern "C" int32_t scpose_events_aedat2_unpack(const uint8_t* records, int64_t n
                                      capacity, count_status, static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
 }
 
+// n_packets in range, the workspace, then the pointers: `a` and `b` are needed when there are packets, `result` always
+static int32_t aedat4_args_ok(const char* who, int64_t n_packets, const void* a, const void* b, const void* result,
+                              const void* workspace, size_t workspace_bytes) {
+  SCP_REQUIRE(n_packets >= 0 && n_packets <= 0x7fffffff, "%s: n_packets=%lld (0 .. 2^31 - 1)", who, (long long)n_packets);
+  if (int32_t rc = workspace_ok(who, workspace, workspace_bytes, events_aedat4_workspace_bytes(n_packets), 16)) return rc;
+  SCP_REQUIRE(result && (n_packets == 0 || (a && b)), "%s: null argument", who);
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_events_aedat4_workspace_bytes(int64_t n_packets, size_t* bytes) {
+  SCP_REQUIRE(bytes, "events_aedat4_workspace_bytes: null argument");
+  SCP_REQUIRE(n_packets >= 0 && n_packets <= 0x7fffffff, "events_aedat4_workspace_bytes: n_packets=%lld (0 .. 2^31 - 1)",
+              (long long)n_packets);
+  *bytes = events_aedat4_workspace_bytes(n_packets);
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_events_aedat4_measure(const uint8_t* file, const int64_t* packets, int64_t n_packets, int64_t* total_status,
+                                                void* workspace, size_t workspace_bytes, void* stream) {
+  if (int32_t rc = aedat4_args_ok("events_aedat4_measure", n_packets, file, packets, total_status, workspace, workspace_bytes)) return rc;
+  return events_aedat4_measure_launch(file, packets, n_packets, total_status, static_cast<uint8_t*>(workspace),
+                                      static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t scpose_events_aedat4_decode(const uint8_t* file, const int64_t* packets, int64_t n_packets, uint8_t* staging,
+                                               int64_t staging_bytes, int32_t verify, void* workspace, size_t workspace_bytes,
+                                               void* stream) {
+  // the kernel stores nothing past a packet's measured size and nothing outside staging_bytes
+  if (int32_t rc = aedat4_args_ok("events_aedat4_decode", n_packets, file, packets, workspace, workspace, workspace_bytes)) return rc;
+  SCP_REQUIRE(staging_bytes >= 0 && (staging || staging_bytes == 0), "events_aedat4_decode: staging of %lld bytes%s",
+              (long long)staging_bytes, staging ? "" : " is null");
+  SCP_REQUIRE(aligned(staging, 16), "events_aedat4_decode: staging must be 16-byte aligned");
+  return events_aedat4_decode_launch(file, packets, n_packets, staging, staging_bytes, verify != 0, static_cast<uint8_t*>(workspace),
+                                     static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t scpose_events_aedat4_count(const uint8_t* src, const int64_t* packets, int64_t n_packets, int32_t staged,
+                                              int64_t* count_status, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int32_t rc = aedat4_args_ok("events_aedat4_count", n_packets, src, staged ? static_cast<const void*>(src) : packets, count_status,
+                                  workspace, workspace_bytes))
+    return rc;
+  return events_aedat4_count_launch(src, packets, n_packets, staged != 0, count_status, static_cast<uint8_t*>(workspace),
+                                    static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t scpose_events_aedat4_unpack(const uint8_t* src, int64_t n_packets, int32_t h, int32_t w, int32_t rebase, int64_t* t,
+                                               int32_t* x, int32_t* y, int8_t* p, int64_t capacity, int64_t* count_status,
+                                               void* workspace, size_t workspace_bytes, void* stream) {
+  SCP_REQUIRE(h >= 1 && h <= 32767 && w >= 1 && w <= 32767, "events_aedat4_unpack: sensor %dx%d (HxW) not supported: each 1 .. 32767",
+              h, w);
+  SCP_REQUIRE(capacity >= 0, "events_aedat4_unpack: capacity=%lld", (long long)capacity);
+  SCP_REQUIRE((t && x && y && p) || capacity == 0, "events_aedat4_unpack: null argument");
+  if (int32_t rc = aedat4_args_ok("events_aedat4_unpack", n_packets, src, src, count_status, workspace, workspace_bytes))
+    return rc;
+  return events_aedat4_unpack_launch(src, n_packets, h, w, rebase != 0, t, x, y, p, capacity, count_status,
+                                     static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
 // what the decoder, the encoder and the overlay draw ask of a batch of frames
 static int32_t frames_ok(const char* who, int32_t n, int32_t h, int32_t w) {
   SCP_REQUIRE(n >= 1 && n <= 65535, "%s: n=%d (1 .. 65535)", who, n);

@@ -297,6 +297,16 @@ size_t events_aedat2_unpack_workspace_bytes(int64_t n);
 int32_t events_aedat2_unpack_launch(const uint8_t* records, int64_t n, int h, int w, int layout, int flip_x, int flip_y, int unwrap,
                                     double t_div, int64_t* t, int32_t* x, int32_t* y, int8_t* p, int64_t capacity, int64_t* count_status,
                                     uint8_t* ws, hipStream_t stream);
+// events_aedat4_read.hip: the event packets of an AEDAT-4.0 file -> (t, x, y, p)
+size_t events_aedat4_workspace_bytes(int64_t n_packets);
+int32_t events_aedat4_measure_launch(const uint8_t* file, const int64_t* packets, int64_t n, int64_t* total_status, uint8_t* ws,
+                                     hipStream_t stream);
+int32_t events_aedat4_decode_launch(const uint8_t* file, const int64_t* packets, int64_t n, uint8_t* staging, int64_t staging_bytes,
+                                    int verify, uint8_t* ws, hipStream_t stream);
+int32_t events_aedat4_count_launch(const uint8_t* src, const int64_t* packets, int64_t n, int staged, int64_t* count_status, uint8_t* ws,
+                                   hipStream_t stream);
+int32_t events_aedat4_unpack_launch(const uint8_t* src, int64_t n, int h, int w, int rebase, int64_t* t, int32_t* x, int32_t* y,
+                                    int8_t* p, int64_t capacity, int64_t* count_status, uint8_t* ws, hipStream_t stream);
 // jpeg_decode.hip: baseline JPEG files -> (N, H, W, 3) uint8 frames (jpeg_common.h: jpeg_blocks(h, w, mode), the blocks of one frame)
 size_t jpeg_decode_workspace_bytes(int n, int h, int w, int mode, int max_subs);
 int32_t jpeg_decode_launch(const uint8_t* desc, const int32_t* segs, int64_t n_rows, const uint8_t* data, int64_t n_bytes, int n, int h,

@@ -1,12 +1,20 @@
-"""Device columns from AEDAT-2.0 event files: the mirror of event_write.py.
+"""Device columns from AEDAT-2.0 and AEDAT-4.0 event files: the mirror of event_write.py.
 
 An AEDAT-2.0 file is a text header, the run of lines that start with '#' and end with '\\n', whose first line is
 `#!AER-DAT2.0`, followed by 8-byte records of two big-endian 32-bit words (address, time stamp).  The header is split off on the
 host (a few lines); the records are uploaded in one piece and decoded on the device (csrc/events_aedat2_read.hip through
 ops.unpack_events_aedat2).  Both jAER's DAVIS recordings (layout 'davis') and the files event_write.write_events_aedat2 and the
-reference's AEDat2Output write (layout 'v2e') are read.  AEDAT-1.0, 3.x and 4.0 are other formats and are refused by name.
+reference's AEDat2Output write (layout 'v2e') are read.  AEDAT-1.0 and 3.x are other formats and are refused by name; so is 4.0 by
+the AEDAT-2.0 entry points: callers sniff the first 14 bytes (is_aedat4_path) and dispatch before them.
+
+An AEDAT-4.0 file (a DVXplorer / DV recording) is `#!AER-DAT4.0\r\n`, a length-prefixed IOHeader flatbuffer (compression, the
+position of the file data table, an XML node that names the streams), then packets: int32 stream id, int32 size, the payload, a
+flatbuffer that is raw or one LZ4 frame.  parse_aedat4 reads the header and walks the packet headers on the host (eight bytes
+per packet); read_events_aedat4 uploads the file in one piece and the payloads of the event streams are decompressed and
+unpacked on the device (csrc/events_aedat4_read.hip, which states the format, through ops.unpack_events_aedat4).
 """
 import re
+import struct
 
 import numpy as np
 
@@ -76,4 +84,176 @@ def read_events_aedat2(path_or_bytes, hw, device=None, **unpack_kwargs):
     buf = torch.from_numpy(body.copy()).to(dev)                      # the copy starts the records on an aligned address
     t, x, y, p, info = ops.unpack_events_aedat2(buf, hw, **unpack_kwargs)
     info["trailing_bytes"] = int(len(host) - off - 8 * n)
+    return t, x, y, p, info
+
+
+# ------------------------------------------------------------------ AEDAT-4.0
+AEDAT4_MAGIC = b"#!AER-DAT4.0\r\n"
+AEDAT4_COMPRESSION = {0: "NONE", 1: "LZ4", 2: "LZ4_HIGH", 3: "ZSTD", 4: "ZSTD_HIGH"}
+
+
+class UnsupportedAedat4(ValueError):
+    """An AEDAT-4.0 file this reader does not take: ZSTD packets, an unknown compression, no IOHeader, no event stream."""
+
+
+class Aedat4Header:
+    """What parse_aedat4 found: compression (the IOHeader's value), streams {id: (type, sizeX, sizeY)}, data_table_position,
+    the packet table as NumPy arrays (packet_offset: payload offset in the file, packet_size, packet_stream), trailing_bytes."""
+
+    def __init__(self, compression, streams, data_table_position, packet_offset, packet_size, packet_stream, trailing_bytes):
+        self.compression = compression
+        self.streams = streams
+        self.data_table_position = data_table_position
+        self.packet_offset = packet_offset
+        self.packet_size = packet_size
+        self.packet_stream = packet_stream
+        self.trailing_bytes = trailing_bytes
+
+    def event_streams(self):
+        """The ids of the EVTS streams, in the header's order."""
+        return [sid for sid, s in self.streams.items() if s[0] == "EVTS"]
+
+
+def is_aedat4_path(path):
+    """True for a path that ends in .aedat4 or a file whose first 14 bytes are the AEDAT-4.0 version line."""
+    if str(path).lower().endswith(".aedat4"):
+        return True
+    try:
+        with open(path, "rb") as f:
+            return f.read(len(AEDAT4_MAGIC)) == AEDAT4_MAGIC
+    except OSError:
+        return False
+
+
+def _fb_field(buf, table, index):
+    """Position of field `index` of the flatbuffer table at `table`, None when it is absent; every step inside buf."""
+    if table < 0 or table + 4 > len(buf):
+        raise UnsupportedAedat4("the IOHeader flatbuffer is damaged: table at %d of %d bytes" % (table, len(buf)))
+    vt = table - struct.unpack_from("<i", buf, table)[0]
+    if vt < 0 or vt + 4 > len(buf):
+        raise UnsupportedAedat4("the IOHeader flatbuffer is damaged: vtable at %d of %d bytes" % (vt, len(buf)))
+    vsize = struct.unpack_from("<H", buf, vt)[0]
+    if vt + vsize > len(buf):
+        raise UnsupportedAedat4("the IOHeader flatbuffer is damaged: vtable of %d bytes at %d" % (vsize, vt))
+    if 4 + 2 * index + 2 > vsize:
+        return None
+    slot = struct.unpack_from("<H", buf, vt + 4 + 2 * index)[0]
+    return table + slot if slot else None
+
+
+def _aedat4_streams(xml):
+    """{id: (typeIdentifier, sizeX, sizeY)} of the nodes under <node name="outInfo"> of the IOHeader's infoNode."""
+    import xml.etree.ElementTree as ET
+    streams = {}
+    try:
+        root = ET.fromstring(xml)
+    except ET.ParseError as e:
+        raise UnsupportedAedat4("the IOHeader's infoNode is not XML: %s" % e)
+    for out in root.iter("node"):
+        if out.get("name") != "outInfo":
+            continue
+        for node in out.findall("node"):
+            try:
+                sid = int(node.get("name"))
+            except (TypeError, ValueError):
+                continue
+            kind = next((a.text for a in node.findall("attr") if a.get("key") == "typeIdentifier"), None)
+            size = {}
+            for info in node.findall("node"):
+                if info.get("name") == "info":
+                    for a in info.findall("attr"):
+                        if a.get("key") in ("sizeX", "sizeY"):
+                            try:
+                                size[a.get("key")] = int(a.text)
+                            except (TypeError, ValueError):
+                                raise UnsupportedAedat4("stream %d: %s is %r in the IOHeader, not an integer" % (sid, a.get("key"), a.text))
+            streams[sid] = (kind, size.get("sizeX"), size.get("sizeY"))
+    return streams
+
+
+def parse_aedat4(data):
+    """The header and packet table of an AEDAT-4.0 file (its bytes) -> Aedat4Header.  Packets run to dataTablePosition when that is
+    >= 0, else to the end; a last packet whose header or payload is cut off is dropped and reported as trailing_bytes, as the
+    AEDAT-2.0 reader reports a partial record.  Raises UnsupportedAedat4 for ZSTD / ZSTD_HIGH (there is no host fallback: no zstd
+    module is at hand), an unknown compression value, a missing IOHE identifier and a file without an event stream."""
+    buf = data if isinstance(data, (bytes, bytearray, memoryview)) else bytes(data)       # a memoryview is walked, not copied
+    if buf[:len(AEDAT4_MAGIC)] != AEDAT4_MAGIC:
+        raise UnsupportedAedat4("not an AEDAT-4.0 file: the first 14 bytes are %r" % bytes(buf[:14]))
+    at = len(AEDAT4_MAGIC)
+    if at + 4 > len(buf):
+        raise UnsupportedAedat4("the file ends before the IOHeader")
+    n = struct.unpack_from("<I", buf, at)[0]
+    head = bytes(buf[at + 4:at + 4 + n])
+    if len(head) < n or n < 8 or head[4:8] != b"IOHE":
+        raise UnsupportedAedat4("no IOHE identifier: the %d bytes after the version line are not an IOHeader" % n)
+    root = struct.unpack_from("<I", head, 0)[0]
+    f = _fb_field(head, root, 0)
+    compression = struct.unpack_from("<i", head, f)[0] if f is not None and f + 4 <= n else 0
+    f = _fb_field(head, root, 1)
+    table_at = struct.unpack_from("<q", head, f)[0] if f is not None and f + 8 <= n else -1
+    f = _fb_field(head, root, 2)
+    xml = b""
+    if f is not None and f + 4 <= n:
+        spos = f + struct.unpack_from("<I", head, f)[0]
+        if spos + 4 <= n:
+            xml = head[spos + 4:spos + 4 + struct.unpack_from("<I", head, spos)[0]]
+    if compression in (3, 4):
+        raise UnsupportedAedat4("the packets are %s compressed: only NONE, LZ4 and LZ4_HIGH are read, and there is no host "
+                                "fallback (no zstd module)" % AEDAT4_COMPRESSION[compression])
+    if compression not in AEDAT4_COMPRESSION:
+        raise UnsupportedAedat4("unknown compression value %d in the IOHeader (0 NONE, 1 LZ4, 2 LZ4_HIGH)" % compression)
+    streams = _aedat4_streams(xml) if xml else {}
+    if not any(s[0] == "EVTS" for s in streams.values()):
+        raise UnsupportedAedat4("no event stream: the IOHeader names %s" % (sorted((k, v[0]) for k, v in streams.items()) or "no streams"))
+    pos = at + 4 + n
+    end = min(table_at, len(buf)) if table_at >= 0 else len(buf)
+    offs, sizes, sids, trailing = [], [], [], 0
+    while pos < end:
+        if pos + 8 > end:
+            trailing = end - pos
+            break
+        sid, size = struct.unpack_from("<ii", buf, pos)
+        if size < 0 or pos + 8 + size > end:
+            trailing = end - pos
+            break
+        offs.append(pos + 8)
+        sizes.append(size)
+        sids.append(sid)
+        pos += 8 + size
+    return Aedat4Header(compression, streams, table_at, np.asarray(offs, dtype=np.int64), np.asarray(sizes, dtype=np.int64),
+                        np.asarray(sids, dtype=np.int32), int(trailing))
+
+
+def read_events_aedat4(path_or_bytes, hw=None, stream=None, rebase=True, verify=True, device=None):
+    """An AEDAT-4.0 file (a path, or its bytes) -> (t int64, x int32, y int32, p int8, info) on `device` (default: the current
+    one), the events of the file's EVTS streams in file order -- what the reference's aedat_to_csv.py loop collects.  hw defaults
+    to the stream's (sizeY, sizeX); stream: one stream id, default every EVTS stream; rebase: subtract the first event's time
+    stamp, as the reference does; verify: check the LZ4 block and content checksums the file carries.  The file is uploaded
+    once, as ops.parse_events_csv uploads its text.  info: n_events, n_packets, t0, n_backward, n_out_of_range, compression, hw,
+    streams, trailing_bytes.  Raises UnsupportedAedat4 (parse_aedat4) and ValueError (ops.unpack_events_aedat4)."""
+    import torch
+    from . import ops
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        host = np.frombuffer(path_or_bytes, dtype=np.uint8)
+    else:
+        host = np.fromfile(path_or_bytes, dtype=np.uint8)
+    head = parse_aedat4(memoryview(host))
+    if stream is None:
+        ids = head.event_streams()
+    else:
+        ids = [int(stream)]
+        if ids[0] not in head.streams or head.streams[ids[0]][0] != "EVTS":
+            raise UnsupportedAedat4("no event stream %r: the IOHeader names %s" % (stream, sorted((k, v[0]) for k, v in head.streams.items())))
+    if hw is None:
+        _, sx, sy = head.streams[ids[0]]
+        if sx is None or sy is None:
+            raise UnsupportedAedat4("stream %d has no sizeX / sizeY in the IOHeader: give hw" % ids[0])
+        hw = (sy, sx)
+    keep = np.isin(head.packet_stream, ids)
+    packets = np.stack([head.packet_offset[keep], head.packet_size[keep]], axis=1)
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    buf = torch.from_numpy(host.copy() if not host.flags.writeable else host).to(dev)
+    t, x, y, p, info = ops.unpack_events_aedat4(buf, packets, head.compression, hw, rebase=rebase, verify=verify)
+    info.update(compression=int(head.compression), hw=(int(hw[0]), int(hw[1])), streams=tuple(ids),
+                trailing_bytes=int(head.trailing_bytes))
     return t, x, y, p, info

@@ -85,10 +85,22 @@ def read_events_device(path, device=None, host_csv=False, hw=None, aedat_layout=
     event_read.read_events_aedat2 instead: hw = (height, width) of the sensor is then required, aedat_layout is 'davis' or
     'v2e', aedat_flip_x / aedat_flip_y undo the writers' flips, and the two time-stamp flags become the decoder's divisor.  The
     flags that describe text (delim_whitespace, swap_xy, host_csv) are refused by name, and a stream with backward time steps
-    raises ValueError("the event stream must be sorted by time")."""
+    raises ValueError("the event stream must be sorted by time").
+
+    A path that ends in .aedat4, or a file whose first 14 bytes are the AEDAT-4.0 version line, is looked at first and goes
+    through event_read.read_events_aedat4 (rebased time stamps in microseconds): hw defaults to the size the file states, and
+    every flag that describes text or a time-stamp unit is refused by name."""
     import torch
     from . import event_read, ops
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if event_read.is_aedat4_path(path):
+        for name, on in [("host_csv", host_csv)] + sorted(csv_flags.items()):
+            if on:
+                raise ValueError("%s describes a text file and cannot be used with the AEDAT-4.0 input %s" % (name, path))
+        t, x, y, _, info = event_read.read_events_aedat4(path, hw=hw, device=dev)
+        if info["n_backward"] > 0:
+            raise ValueError("the event stream must be sorted by time")
+        return t, x, y
     if event_read.is_aedat_path(path):
         for name, on in (("host_csv", host_csv), ("delim_whitespace", csv_flags.get("delim_whitespace")),
                          ("swap_xy", csv_flags.get("swap_xy"))):
@@ -178,6 +190,12 @@ def frame_times_text(dvs_vid, times):
         "{}\t{:10.6f}\n".format(k, float(tk)) for k, tk in enumerate(times))
 
 
+def scene_aedat4(scene_dir):
+    """The scene's one *.aedat4 file, None when it has none or several."""
+    found = sorted(f for f in os.listdir(scene_dir) if f.lower().endswith(".aedat4"))
+    return os.path.join(scene_dir, found[0]) if len(found) == 1 else None
+
+
 def render_scene(scene_dir, hw, K=None, dist=None, interval=10000.0, full_scale=2, write_distorted=True, device=None,
                  chunk_frames=256, exposure=None, host_csv=False, aedat_layout="davis", **csv_flags):
     """scene_dir/events.csv -> scene_dir/event-frames/<t>.bmp (undistorted when K / dist are given) and, with
@@ -186,13 +204,16 @@ def render_scene(scene_dir, hw, K=None, dist=None, interval=10000.0, full_scale=
     chunk_frames at a time.  host_csv: read the file with the pandas reader instead (the device parser's fallback).
     exposure: None (DURATION over `interval`) or ops.render_events keyword arguments (exposure_kwargs) that replace it.
     A scene that holds events.aedat (AEDAT-2.0, address layout aedat_layout, sensor size hw) and no events.csv is rendered from
-    that file; when both exist, events.csv wins.  Returns the list of frame names."""
+    that file; when both exist, events.csv wins.  A scene with neither, but exactly one *.aedat4 file (an AEDAT-4.0 recording), is
+    rendered from that file.  Returns the list of frame names."""
     import torch
     from . import ops
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     src = os.path.join(scene_dir, "events.csv")
     if not os.path.exists(src) and os.path.exists(os.path.join(scene_dir, "events.aedat")):
         src = os.path.join(scene_dir, "events.aedat")
+    elif not os.path.exists(src) and scene_aedat4(scene_dir) is not None:
+        src = scene_aedat4(scene_dir)
     t, x, y = read_events_device(src, dev, host_csv=host_csv, hw=hw, aedat_layout=aedat_layout, **csv_flags)
     out_dir = os.path.join(scene_dir, "event-frames"); dis_dir = os.path.join(scene_dir, "event-frames-distorted")
     os.makedirs(out_dir, exist_ok=True)

@@ -509,6 +509,72 @@ def unpack_events_aedat2(records, hw, layout="davis", flip_x=True, flip_y=True, 
     return t[:rows].clone(), x[:rows].clone(), y[:rows].clone(), p[:rows].clone(), info
 
 
+def unpack_events_aedat4(buf, packets, compression, hw, rebase=True, verify=True):
+    """The event packets of an AEDAT-4.0 file -> (t int64, x int32, y int32, p int8, info), events in file order, decompressed
+    and unpacked on the device (csrc/events_aedat4_read.hip), in the dtypes render_events takes.  buf: a uint8 device tensor, the
+    whole file.  packets: (n, 2) int64, payload offset and size of each EVENT packet (event_read.parse_aedat4 finds them).
+    compression: the IOHeader's value, 0 NONE or 1 / 2 LZ4.  hw = (height, width) of the sensor.  rebase: t minus the first
+    event's t.  verify: check the checksums the LZ4 frames carry.  Two small read-backs size the staging buffer and the columns,
+    a third brings the counters.  info: n_events, n_packets, t0, n_backward, n_out_of_range.  Raises ValueError for a damaged
+    frame, a checksum that differs, a damaged flatbuffer and an event outside the sensor."""
+    if not torch.is_tensor(buf) or buf.dtype != torch.uint8:
+        raise ValueError("unpack_events_aedat4: the file must be a uint8 device tensor")
+    _need_cuda(buf)
+    if compression not in (0, 1, 2):
+        raise ValueError("unpack_events_aedat4: compression %r (0 NONE, 1 LZ4, 2 LZ4_HIGH)" % (compression,))
+    buf = buf.contiguous().view(-1)
+    pk = np.ascontiguousarray(packets, dtype=np.int64).reshape(-1, 2)
+    n = int(pk.shape[0])
+    if n and (pk.min() < 0 or int((pk[:, 0] + pk[:, 1]).max()) > buf.numel()):
+        raise ValueError("unpack_events_aedat4: a packet does not lie inside the %d bytes of the file" % buf.numel())
+    h, w = int(hw[0]), int(hw[1])
+    dev = buf.device
+    lib = nat.lib()
+    ws = _query_bytes("events_aedat4_workspace_bytes", n)
+    with torch.cuda.device(dev):
+        work = torch.empty(ws, dtype=torch.uint8, device=dev)
+        cs = torch.empty(6, dtype=torch.int64, device=dev)
+        pkd = torch.from_numpy(pk).to(dev)
+        src = buf
+        if compression:
+            nat.check(lib.scpose_events_aedat4_measure(_ptr(buf), _ptr(pkd), n, _ptr(cs), _ptr(work), ws, _stream()),
+                      "events_aedat4_measure")
+            total, status = cs.tolist()[:2]                         # small read-back: the staging buffer's size
+            _aedat4_raise(status, hw)
+            if total < 0 or total % 16 or total > n * (1 << 23):
+                raise nat.NativeError("unpack_events_aedat4: events_aedat4_measure reports %d staging bytes for %d packets" % (total, n))
+            src = torch.empty(max(int(total), 16), dtype=torch.uint8, device=dev)
+            nat.check(lib.scpose_events_aedat4_decode(_ptr(buf), _ptr(pkd), n, _ptr(src), int(total), int(bool(verify)), _ptr(work), ws,
+                                                      _stream()),
+                      "events_aedat4_decode")
+        nat.check(lib.scpose_events_aedat4_count(_ptr(src), _ptr(pkd), n, int(bool(compression)), _ptr(cs), _ptr(work), ws, _stream()),
+                  "events_aedat4_count")
+        rows, status, t0 = cs.tolist()[:3]                          # small read-back: the columns' size
+        _aedat4_raise(status, hw)
+        t, x, y, p = _empty_event_columns(int(rows), dev)
+        nat.check(lib.scpose_events_aedat4_unpack(_ptr(src), n, h, w, int(bool(rebase)), _ptr(t), _ptr(x), _ptr(y), _ptr(p), int(rows),
+                                                  _ptr(cs), _ptr(work), ws, _stream()), "events_aedat4_unpack")
+        got = cs.tolist()                                           # the counters
+    _aedat4_raise(got[1], hw)
+    return t, x, y, p, {"n_events": int(rows), "n_packets": n, "t0": int(t0) if rows else 0, "n_backward": int(got[3]),
+                        "n_out_of_range": int(got[4])}
+
+
+def _aedat4_raise(status, hw):
+    """ValueError for the status bits of the AEDAT-4.0 kernels."""
+    if status & nat.AEDAT4_CORRUPT:
+        raise ValueError("unpack_events_aedat4: a packet is not a valid LZ4 frame (status CORRUPT: a bad magic, version or header "
+                         "checksum, an offset of 0 or before the output's start, an input overrun, a size that differs)")
+    if status & nat.AEDAT4_CHECKSUM:
+        raise ValueError("unpack_events_aedat4: an LZ4 block or content checksum differs (status CHECKSUM)")
+    if status & nat.AEDAT4_FLATBUFFER:
+        raise ValueError("unpack_events_aedat4: an event packet's flatbuffer is damaged (status FLATBUFFER)")
+    if status & nat.AEDAT4_RANGE:
+        raise ValueError("unpack_events_aedat4: an event lies outside the %d x %d sensor (status RANGE)" % (int(hw[1]), int(hw[0])))
+    if status != 0:
+        raise nat.NativeError("unpack_events_aedat4: status %d" % status)
+
+
 # ------------------------------------------------------------------ baseline JPEG files -> frames
 JPEG_MAX_ROUNDS = 96          # launches of the relaxation (DESIGN.md section 5b: measured distribution and head-room)
 _JPEG_WORKSPACE = {}          # device index -> uint8 tensor, grown on demand (2 bytes per coefficient: too large to allocate per call)

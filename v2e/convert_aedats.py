@@ -15,8 +15,9 @@ Extensions (optional): --no_distorted skips event-frames-distorted/; the CSV fla
 --microseconds_timestamp, --milliseconds_timestamp); --host_csv reads events.csv with the pandas reader, which is also what a
 file outside the device parser's grammar (an exponent, a quoted field, ...) falls back to by itself; a scene's events.aedat
 is decoded on the device (csrc/events_aedat2_read.hip) with --image_height x --image_width as the sensor size and --aedat_layout
-as the address word, and events.csv wins when both exist.  Not reproduced: the AVI video and frame-times file e2v.py also
-writes, AEDAT-3/4 parsing (aedat_to_csv.py)."""
+as the address word, and events.csv wins when both exist; a scene with neither but exactly one *.aedat4 file (an AEDAT-4.0
+recording) is rendered from that file, decompressed and unpacked on the device (csrc/events_aedat4_read.hip).  Not reproduced:
+the AVI video and frame-times file e2v.py also writes, AEDAT-3 parsing."""
 import argparse
 import json
 import os
@@ -57,7 +58,7 @@ def main(argv=None):
     for scene in sorted(os.listdir(args.scenes_dir)):
         full = os.path.join(args.scenes_dir, scene)
         if os.path.isdir(full) and (os.path.exists(os.path.join(full, "events.csv")) or
-                                    os.path.exists(os.path.join(full, "events.aedat"))):
+                                    os.path.exists(os.path.join(full, "events.aedat")) or er.scene_aedat4(full) is not None):
             names = er.render_scene(full, (args.image_height, args.image_width), K=K, dist=dist,
                                     write_distorted=not args.no_distorted, delim_whitespace=args.delim_whitespace,
                                     swap_xy=args.swap_xy, microseconds_timestamp=args.microseconds_timestamp,

@@ -16,7 +16,10 @@ The text forms write x before y whatever --swap_xy says: the flag describes IN.
 
 An IN that ends in .aedat / .aedat2 is an AEDAT-2.0 file and is read by event_read.read_events_aedat2
 (csrc/events_aedat2_read.hip): it needs --width and --height, the sensor size, and --aedat_layout names its address word (jAER's
-DAVIS word, the default, or the word this tool and v2e.py --events_aedat2 write); the two text flags are refused.  With a .csv or
+DAVIS word, the default, or the word this tool and v2e.py --events_aedat2 write); the two text flags are refused.  An IN that
+ends in .aedat4 (or starts with the AEDAT-4.0 version line) is a DV recording and is read by event_read.read_events_aedat4
+(csrc/events_aedat4_read.hip): the sensor size comes from the file unless --width and --height say otherwise, and the text flags
+and --aedat_layout are refused.  With a .csv or
 .txt OUT this is the device counterpart of the reference's aedat_to_csv.py for AEDAT-2.0 files.
 """
 import argparse
@@ -31,14 +34,17 @@ FORMATS = (".csv", ".txt", ".aedat")
 
 
 def convert_args(parser):
+    """The arguments of events_convert.py.  --aedat_layout defaults to None here so that main() can refuse it for an AEDAT-4.0
+    input; main() fills in the documented default, 'davis', for every other input.  A caller that parses with this helper alone
+    has to do the same."""
     parser.add_argument("--events_file", type=str, required=True, help="event text file: t, x, y, p per line, '#' comments")
     parser.add_argument("--delim_whitespace", action="store_true", default=False, help="fields are separated by blanks, not commas")
     parser.add_argument("--swap_xy", action="store_true", default=False, help="the second column of the input is y, the third x")
     parser.add_argument("--output", type=str, required=True, help="file to write; the extension picks the format: %s" % ", ".join(FORMATS))
     parser.add_argument("--width", type=int, default=None, help="sensor width in pixels (.aedat input or output only)")
     parser.add_argument("--height", type=int, default=None, help="sensor height in pixels (.aedat input or output only)")
-    parser.add_argument("--aedat_layout", choices=("davis", "v2e"), default="davis",
-                        help="address word of an .aedat input: jAER's DAVIS word, or the word the .aedat output here has")
+    parser.add_argument("--aedat_layout", choices=("davis", "v2e"), default=None,
+                        help="address word of an .aedat input: jAER's DAVIS word (the default), or the word the .aedat output here has")
     return parser
 
 
@@ -49,7 +55,17 @@ def main(argv=None):
         sys.exit("events_convert: --output %s: the extension must be one of %s" % (args.output, ", ".join(FORMATS)))
     if ext == ".aedat" and (args.width is None or args.height is None):
         sys.exit("events_convert: an .aedat output needs --width and --height")
-    aedat_in = args.events_file.lower().endswith((".aedat", ".aedat2"))
+    aedat4_in = args.events_file.lower().endswith(".aedat4")
+    if not aedat4_in and os.path.isfile(args.events_file):
+        with open(args.events_file, "rb") as f:
+            aedat4_in = f.read(14) == b"#!AER-DAT4.0\r\n"
+    if aedat4_in and (args.delim_whitespace or args.swap_xy or args.aedat_layout):
+        sys.exit("events_convert: --delim_whitespace, --swap_xy and --aedat_layout cannot be used with the AEDAT-4.0 input %s"
+                 % args.events_file)
+    if aedat4_in and (args.width is None) != (args.height is None):
+        sys.exit("events_convert: give --width and --height together, or neither (the AEDAT-4.0 file states its sensor size)")
+    args.aedat_layout = args.aedat_layout or "davis"
+    aedat_in = args.events_file.lower().endswith((".aedat", ".aedat2")) and not aedat4_in
     if aedat_in and (args.width is None or args.height is None):
         sys.exit("events_convert: an .aedat input needs --width and --height, the sensor size")
     if aedat_in and (args.delim_whitespace or args.swap_xy):
@@ -66,7 +82,14 @@ def main(argv=None):
         except ValueError as e:
             sys.exit("events_convert: %s" % e)
     ops = import_module("spacecraft-pose-estimation_amd.ops")
-    if aedat_in:
+    if aedat4_in:
+        er = import_module("spacecraft-pose-estimation_amd.event_read")
+        try:
+            t, x, y, p, info = er.read_events_aedat4(args.events_file, hw=None if args.width is None else (args.height, args.width))
+        except ValueError as e:
+            sys.exit("events_convert: %s" % e)
+        print("events_convert: %s: %s" % (args.events_file, ", ".join("%s=%s" % kv for kv in sorted(info.items()))))
+    elif aedat_in:
         er = import_module("spacecraft-pose-estimation_amd.event_read")
         try:
             t, x, y, p, info = er.read_events_aedat2(args.events_file, (args.height, args.width), layout=args.aedat_layout)
