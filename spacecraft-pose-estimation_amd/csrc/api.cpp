@@ -345,6 +345,20 @@ static int32_t jpeg_check_shape(int32_t n, int32_t h, int32_t w, int32_t mode, i
   return SCPOSE_OK;
 }
 
+// What both *_decode_crop entry points ask of the crops and of the windows; each one's own sentences fire between the two checks.
+static int32_t crop_size_ok(const char* who, int32_t out_h, int32_t out_w) {
+  SCP_REQUIRE(out_h >= 1 && out_w >= 1 && out_h <= 65535 && out_w <= 65535, "%s: bad output size %dx%d (each 1 .. 65535)", who, out_h, out_w);
+  return SCPOSE_OK;
+}
+static int32_t crop_rois_ok(const char* who, int32_t n, int32_t h, int32_t w, const int32_t* roi_xywh) {
+  for (int32_t i = 0; i < n; ++i) {      // roi_xywh is host memory: the window bounds everything the crop kernel reads
+    const int32_t* r = roi_xywh + 4 * (size_t)i;
+    SCP_REQUIRE(r[0] >= 0 && r[1] >= 0 && r[2] >= 0 && r[3] >= 0 && (int64_t)r[0] + r[2] <= w && (int64_t)r[1] + r[3] <= h,
+                "%s: roi %d = [%d, %d, %d, %d] (x, y, w, h) is not inside the %dx%d (HxW) frame", who, i, r[0], r[1], r[2], r[3], h, w);
+  }
+  return SCPOSE_OK;
+}
+
 extern "C" int32_t scpose_jpeg_decode_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t mode, int32_t max_subs, size_t* bytes) {
   SCP_REQUIRE(bytes, "jpeg_decode_workspace_bytes: null argument");
   if (int32_t rc = jpeg_check_shape(n, h, w, mode, max_subs, "jpeg_decode_workspace_bytes")) return rc;
@@ -377,16 +391,11 @@ extern "C" int32_t scpose_jpeg_decode_crop(const uint8_t* desc, const int32_t* s
   SCP_REQUIRE(max_rounds >= 1 && max_rounds <= 250, "jpeg_decode_crop: max_rounds=%d (1 .. 250)", max_rounds);
   SCP_REQUIRE(n_seg_rows >= 2 * (int64_t)n && n_seg_rows < ((int64_t)1 << 31) && n_bytes >= 0, "jpeg_decode_crop: n_seg_rows=%lld n_bytes=%lld",
               (long long)n_seg_rows, (long long)n_bytes);
-  SCP_REQUIRE(out_h >= 1 && out_w >= 1 && out_h <= 65535 && out_w <= 65535, "jpeg_decode_crop: bad output size %dx%d (each 1 .. 65535)", out_h,
-              out_w);
+  if (int32_t rc = crop_size_ok("jpeg_decode_crop", out_h, out_w)) return rc;
   SCP_REQUIRE(desc && segs && (data || n_bytes == 0) && minv && roi_xywh && crops && status, "jpeg_decode_crop: null argument");
   SCP_REQUIRE(aligned(desc, 8) && aligned(minv, 8) && aligned(segs, 4) && aligned(status, 4),
               "jpeg_decode_crop: desc and minv must be 8-byte aligned, segs and status 4-byte aligned");
-  for (int32_t i = 0; i < n; ++i) {      // roi_xywh is host memory: the window bounds every sample the crop kernel reads
-    const int32_t* r = roi_xywh + 4 * (size_t)i;
-    SCP_REQUIRE(r[0] >= 0 && r[1] >= 0 && r[2] >= 0 && r[3] >= 0 && (int64_t)r[0] + r[2] <= w && (int64_t)r[1] + r[3] <= h,
-                "jpeg_decode_crop: roi %d = [%d, %d, %d, %d] (x, y, w, h) is not inside the %dx%d (HxW) frame", i, r[0], r[1], r[2], r[3], h, w);
-  }
+  if (int32_t rc = crop_rois_ok("jpeg_decode_crop", n, h, w, roi_xywh)) return rc;
   if (int32_t rc = workspace_ok("jpeg_decode_crop", workspace, workspace_bytes, jpeg_decode_workspace_bytes(n, h, w, mode, max_subs), 256))
     return rc;
   return jpeg_decode_crop_launch(desc, segs, n_seg_rows, data, n_bytes, n, h, w, mode, max_subs, bgr != 0, max_rounds, minv, roi_xywh, out_h,
@@ -394,8 +403,8 @@ extern "C" int32_t scpose_jpeg_decode_crop(const uint8_t* desc, const int32_t* s
 }
 
 static int32_t png_check_shape(const char* who, int32_t n, int32_t h, int32_t w, int32_t channels) {
-  SCP_REQUIRE(n >= 0 && n <= 65535, "%s: n=%d (0 .. 65535)", who, n);
-  SCP_REQUIRE(h >= 1 && h <= 65535 && w >= 1 && w <= 65535, "%s: frame %dx%d (HxW), each 1 .. 65535", who, h, w);
+  SCP_REQUIRE(n >= 0 && n <= 65535, "%s: n=%d (0 .. 65535)", who, n);      // an empty batch has a workspace size too
+  if (int32_t rc = frames_ok(who, n ? n : 1, h, w)) return rc;
   SCP_REQUIRE(channels >= 1 && channels <= 4, "%s: channels=%d (1 .. 4)", who, channels);
   return SCPOSE_OK;
 }
@@ -443,17 +452,12 @@ extern "C" int32_t scpose_png_decode_crop(const uint8_t* desc, const uint8_t* da
                                           void* stream) {
   if (n == 0) return SCPOSE_OK;
   if (int32_t rc = png_check_shape("png_decode_crop", n, h, w, channels)) return rc;
-  SCP_REQUIRE(out_h >= 1 && out_w >= 1 && out_h <= 65535 && out_w <= 65535, "png_decode_crop: bad output size %dx%d (each 1 .. 65535)", out_h,
-              out_w);
+  if (int32_t rc = crop_size_ok("png_decode_crop", out_h, out_w)) return rc;
   SCP_REQUIRE(desc && (data || n_bytes == 0) && minv && roi_xywh && crops && status && n_bytes >= 0, "png_decode_crop: null argument");
   SCP_REQUIRE(aligned(data, 4) && aligned(status, 4) && aligned(minv, 8),
               "png_decode_crop: data and status must be 4-byte aligned, minv 8-byte aligned");
   if (int32_t rc = png_check_desc("png_decode_crop", desc, n_bytes, n, h, w, channels)) return rc;
-  for (int32_t i = 0; i < n; ++i) {      // roi_xywh is host memory: the window bounds the rows the crop kernel reads
-    const int32_t* r = roi_xywh + 4 * (size_t)i;
-    SCP_REQUIRE(r[0] >= 0 && r[1] >= 0 && r[2] >= 0 && r[3] >= 0 && (int64_t)r[0] + r[2] <= w && (int64_t)r[1] + r[3] <= h,
-                "png_decode_crop: roi %d = [%d, %d, %d, %d] (x, y, w, h) is not inside the %dx%d (HxW) frame", i, r[0], r[1], r[2], r[3], h, w);
-  }
+  if (int32_t rc = crop_rois_ok("png_decode_crop", n, h, w, roi_xywh)) return rc;
   if (int32_t rc = workspace_ok("png_decode_crop", workspace, workspace_bytes, png_decode_workspace_bytes(n, h, w, channels), 256))
     return rc;
   return png_decode_crop_launch(desc, data, n, h, w, channels, bgr != 0, minv, roi_xywh, out_h, out_w, crops, status,

@@ -2,7 +2,7 @@
 // FixedPtCast<int, uchar, 15>): a source position in 1/32 px (INTER_BITS = 5) splits into the pixel (X >> 5, saturated
 // to int16 as OpenCV stores it) and the 5-bit fraction X & 31; the four integer weights (32-a)(32-b)*32 ... a*b*32 sum to
 // 2^15; the pixel is (sum of taps * weights + 2^14) >> 15.  How a kernel arrives at the 1/32-px coordinates is its own
-// business (affine_source below, for crop.hip and jpeg_decode.hip: an affine map in 1/1024 px; events.hip: a float64 distortion map); the tap is shared.
+// business (affine_source below, for crop.hip and crop_tail.h: an affine map in 1/1024 px; events.hip: a float64 distortion map); the tap is shared.
 // utils/transforms.py:warp_affine_bilinear is the NumPy restatement.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -21,7 +21,7 @@ __device__ __forceinline__ long long sat_int16(long long v) { return v < -32768 
 
 // cv::warpAffine's source position of output pixel (x, y) under the inverse map m[6] (3.4 imgwarp.cpp: WarpAffineInvoker): the
 // map in 1/1024 px, the two roundings kept apart, then 1/32 px; the pixel (x0, y0) of the first tap and the fractions (a, b).
-// crop.hip and jpeg_decode.hip's crop tail sample at exactly these positions.
+// crop.hip and crop_tail.h sample at exactly these positions.
 struct AffineSource {
   long long x0, y0;
   int a, b;

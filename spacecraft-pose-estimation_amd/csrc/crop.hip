@@ -13,7 +13,7 @@
 // One thread per output pixel; the 3 channels of a tap are 3 adjacent bytes; output is the uint8
 // NHWC tensor the stem kernel consumes (its ToTensor/Normalize is fused there).
 #include "common.h"
-#include "bilinear_fixed.h"
+#include "crop_tail.h"
 
 #pragma clang fp contract(off)
 
@@ -37,15 +37,14 @@ __global__ __launch_bounds__(256) void crop_warp_kernel(const uint8_t* __restric
     // roi != null: only the window [ry, ry + rh) x [rx, rx + rw) of frame n is stored (the loader ships the part of the frame the
     // warp can touch instead of 1920 x 1200 x 3 bytes per frame); coordinates, weights and the frame border stay those of the whole frame
     const int rx = roi ? roi[4 * n] : 0, ry = roi ? roi[4 * n + 1] : 0, rw = roi ? roi[4 * n + 2] : sw, rh = roi ? roi[4 * n + 3] : sh;
-    const AffineSource p = affine_source(m, x, y);            // bilinear_fixed.h: the position shared with jpeg_decode.hip's crop tail
+    const AffineSource p = affine_source(m, x, y);            // bilinear_fixed.h: the position shared with the decoders' crop tail (crop_tail.h)
     const long long x0 = p.x0, y0 = p.y0;
     const BilinearTap bil(p.a, p.b);                          // bilinear_fixed.h: the tap shared with events.hip
     uint8_t res[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       auto tap = [&](long long yy, long long xx) -> int {
-        const bool ok = yy >= 0 && yy < sh && xx >= 0 && xx < sw && yy >= ry && yy < ry + rh && xx >= rx && xx < rx + rw;
-        return ok ? (int)src[((size_t)(yy - ry) * rw + (size_t)(xx - rx)) * 3 + c] : 0;
+        return in_window(xx, yy, sh, sw, rx, ry, rw, rh) ? (int)src[((size_t)(yy - ry) * rw + (size_t)(xx - rx)) * 3 + c] : 0;
       };
       res[c] = bil(tap(y0, x0), tap(y0, x0 + 1), tap(y0 + 1, x0), tap(y0 + 1, x0 + 1));
     }

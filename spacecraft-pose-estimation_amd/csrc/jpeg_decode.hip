@@ -26,16 +26,15 @@
 // DC sums run on the whole frame as above -- the entropy-coded bytes have no entry points and a DC value needs every block before
 // it -- and then
 //   jpeg_idct_window_kernel  the same inverse DCT, for the blocks that hold a sample the crop can read (sample_span below)
-//   jpeg_crop_kernel         one thread per crop pixel: crop.hip's source position and bilinear tap (bilinear_fixed.h), each of the
-//       four taps computed from the sample planes by jpeg_pixel(), the arithmetic of jpeg_output_kernel.  No frame is written;
-//       a sample outside the window stays uninitialised and is never read.
+//   jpeg_crop_kernel         the decoders' shared crop tail (crop_tail.h) over jpeg_pixel(), the arithmetic of jpeg_output_kernel, as
+//       its pixel source.  No frame is written; a sample outside the window stays uninitialised and is never read.
 // A speculative walk from a wrong state decodes garbage by design: every iteration consumes at least one bit, the walk ends with
 // the subsequence (plus one code word) or the segment, zeros are fed past the end of the data, and nothing but the thread's own
 // slot and count is written.  No code word starts in the encoder's fill bits (the last min(7, trailing ones) bits of a segment):
 // no Huffman code is all ones.  No floating point, no atomics but integer ORs into status; two runs are bitwise equal.
 #include "jpeg_common.h"
 #include "scan_device.h"
-#include "bilinear_fixed.h"
+#include "crop_tail.h"
 
 namespace scpose {
 
@@ -467,13 +466,6 @@ __global__ __launch_bounds__(kThreads) void jpeg_idct_kernel(const uint8_t* __re
   idct_blocks<false>(desc, geo, coef, dc, plane_y, plane_c, blockIdx.y, nullptr);
 }
 
-// The windows of up to kRoiChunk images travel in the kernel arguments: the host has them (api.cpp checks each against the frame),
-// and the workspace keeps the size scpose_jpeg_decode_workspace_bytes() states.  Image img0 + blockIdx.y has rois.v[blockIdx.y].
-constexpr int kRoiChunk = 128;
-struct RoiChunk {
-  int32_t v[kRoiChunk][4];
-};
-
 __global__ __launch_bounds__(kThreads) void jpeg_idct_window_kernel(const uint8_t* __restrict__ desc, Geo geo, const int16_t* __restrict__ coef,
                                                                     const int32_t* __restrict__ dc, uint8_t* __restrict__ plane_y,
                                                                     uint8_t* __restrict__ plane_c, RoiChunk rois, int img0) {
@@ -565,38 +557,16 @@ __global__ __launch_bounds__(kThreads) void jpeg_output_kernel(Geo geo, int bgr,
   }
 }
 
-// crop_warp_kernel (crop.hip) of frame img0 + blockIdx.y without the frame: the same source position and weights, every tap from
-// the sample planes.  A tap outside the frame or outside the image's window counts as 0 -- the window bounds every plane sample
+// The crop tail (crop_tail.h) of frame img0 + blockIdx.y, every tap from the sample planes: the window bounds every plane sample
 // that is read, and idct_blocks<true> has written exactly those (sample_span).
-__global__ __launch_bounds__(kThreads) void jpeg_crop_kernel(Geo geo, int bgr, const uint8_t* __restrict__ plane_y,
-                                                             const uint8_t* __restrict__ plane_c, const double* __restrict__ minv,
-                                                             RoiChunk rois, int img0, int oh, int ow, uint8_t* __restrict__ out) {
+__global__ __launch_bounds__(kCropThreads) void jpeg_crop_kernel(Geo geo, int bgr, const uint8_t* __restrict__ plane_y,
+                                                                 const uint8_t* __restrict__ plane_c, const double* __restrict__ minv,
+                                                                 RoiChunk rois, int img0, int oh, int ow, uint8_t* __restrict__ out) {
   const int img = img0 + (int)blockIdx.y;
-  const int32_t rx = rois.v[blockIdx.y][0], ry = rois.v[blockIdx.y][1], rw = rois.v[blockIdx.y][2], rh = rois.v[blockIdx.y][3];
   const Planes pl = image_planes(geo, plane_y, plane_c, img);
-  const double* m = minv + (size_t)img * 6;
-  const int64_t total = (int64_t)oh * ow;
-  uint8_t* o = out + (size_t)img * total * 3;
-  for (int64_t pix = (int64_t)blockIdx.x * kThreads + threadIdx.x; pix < total; pix += (int64_t)gridDim.x * kThreads) {
-    const AffineSource p = affine_source(m, (int)(pix % ow), (int)(pix / ow));
-    const BilinearTap bil(p.a, p.b);
-    Pixel t[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const long long yy = p.y0 + (j >> 1), xx = p.x0 + (j & 1);
-      const bool ok = yy >= 0 && yy < geo.h && xx >= 0 && xx < geo.w && yy >= ry && yy < ry + rh && xx >= rx && xx < rx + rw;
-      t[j] = ok ? jpeg_pixel(geo, pl, (int32_t)xx, (int32_t)yy) : Pixel{0, 0, 0, 0};
-    }
-    const uint8_t r = bil(t[0].r, t[1].r, t[2].r, t[3].r);
-    uint8_t g = r, b = r;
-    if (geo.mode != SCPOSE_JPEG_GRAY) {
-      g = bil(t[0].g, t[1].g, t[2].g, t[3].g);
-      b = bil(t[0].b, t[1].b, t[2].b, t[3].b);
-    }
-    o[pix * 3] = bgr ? b : r;
-    o[pix * 3 + 1] = g;
-    o[pix * 3 + 2] = bgr ? r : b;
-  }
+  const auto px = [&](int32_t x, int32_t y) { const Pixel v = jpeg_pixel(geo, pl, x, y); return Rgb{v.r, v.g, v.b}; };
+  crop_tail(px, geo.h, geo.w, geo.mode == SCPOSE_JPEG_GRAY, bgr, minv + (size_t)img * 6, rois.v[blockIdx.y], oh, ow,
+            out + (size_t)img * ((int64_t)oh * ow) * 3);
 }
 
 struct Plan {
@@ -669,16 +639,12 @@ int32_t jpeg_decode_crop_launch(const uint8_t* desc, const int32_t* segs, int64_
   const Geo g = make_geo(n, h, w, mode, max_subs, n_bytes, n_rows);
   const Plan p = make_plan(g, ws);
   if (int32_t rc = launch_entropy_passes(g, p, desc, segs, data, max_rounds, status, ws, stream)) return rc;
-  const int64_t crop_groups = ((int64_t)out_h * out_w + kThreads - 1) / kThreads;
-  for (int img0 = 0; img0 < n; img0 += kRoiChunk) {
-    const int count = n - img0 < kRoiChunk ? n - img0 : kRoiChunk;
-    RoiChunk rois{};
-    for (int k = 0; k < count * 4; ++k) rois.v[k / 4][k % 4] = roi_host[(size_t)img0 * 4 + k];
+  for_each_roi_chunk(roi_host, n, [&](const RoiChunk& rois, int img0, int count) {
     hipLaunchKernelGGL(jpeg_idct_window_kernel, dim3((unsigned)((g.n_blocks + kThreads - 1) / kThreads), (unsigned)count), dim3(kThreads), 0,
                        stream, desc, g, p.coef, p.dc, p.plane_y, p.plane_c, rois, img0);
-    hipLaunchKernelGGL(jpeg_crop_kernel, dim3((unsigned)(crop_groups < 4096 ? crop_groups : 4096), (unsigned)count), dim3(kThreads), 0, stream, g,
-                       bgr, p.plane_y, p.plane_c, minv, rois, img0, out_h, out_w, crops);
-  }
+    hipLaunchKernelGGL(jpeg_crop_kernel, crop_tail_grid(out_h, out_w, count), dim3(kCropThreads), 0, stream, g, bgr, p.plane_y, p.plane_c, minv, rois,
+                       img0, out_h, out_w, crops);
+  });
   SCP_CHECK_HIP(hipGetLastError());
   return SCPOSE_OK;
 }

@@ -15,10 +15,10 @@
 //                         filter types take this one path.  In place.  A filter byte above 4 sets SCPOSE_PNG_FILTER.  An image
 //                         that inflate left CORRUPT is not looked at: its plane is incomplete.
 //   png_output_kernel     one thread per pixel: gray replicated, palette looked up, alpha dropped -> (n, h, w, 3) RGB or BGR.
-//   png_crop_kernel       crop.hip's warp without the frame: affine_source + BilinearTap (bilinear_fixed.h), each tap fetched from
-//                         the unfiltered plane through the same expansion.  Only the rows down to the window's last are unfiltered.
+//   png_crop_kernel       the decoders' shared crop tail (crop_tail.h), each tap fetched from the unfiltered plane through the same
+//                         expansion.  Only the rows down to the window's last are unfiltered.
 #include "common.h"
-#include "bilinear_fixed.h"
+#include "crop_tail.h"
 
 namespace scpose {
 namespace {
@@ -29,7 +29,6 @@ constexpr int kWin = 32768;              // deflate's window: the output ring in
 constexpr int kFlush = 4096;             // the ring is written out when this much of it is new
 constexpr int kInWords = 1024;           // input window in LDS, 32-bit words
 constexpr int kLitBits = 10, kDistBits = 8;
-constexpr int kRoiChunk = 64;            // windows per launch of the crop tail (kernel arguments)
 
 struct Desc {
   long long off, len;
@@ -431,9 +430,6 @@ __global__ __launch_bounds__(kWave) void png_unfilter_kernel(uint8_t* __restrict
 }
 
 // pixel (x, y) of the frame from the unfiltered plane: gray replicated, palette looked up, alpha dropped
-struct Rgb {
-  int32_t r, g, b;
-};
 __device__ __forceinline__ Rgb png_pixel(const uint8_t* __restrict__ plane, size_t line, int bpp, int color_type,
                                          const uint8_t* __restrict__ palette, int x, int y) {
   const uint8_t* p = plane + (size_t)y * line + 1 + (size_t)x * bpp;
@@ -461,42 +457,20 @@ __global__ __launch_bounds__(256) void png_output_kernel(const uint8_t* __restri
   }
 }
 
-struct RoiChunk {
-  int32_t v[kRoiChunk][4];
-};
-
 __global__ void png_rows_kernel(RoiChunk rois, int img0, int count, int32_t* __restrict__ rows_of) {
   if ((int)threadIdx.x < count) rows_of[img0 + threadIdx.x] = rois.v[threadIdx.x][1] + rois.v[threadIdx.x][3];
 }
 
-// crop_warp_kernel (crop.hip) of frame img0 + blockIdx.y without the frame.  A tap outside the frame or outside the image's window
-// counts as 0: the window bounds the rows png_unfilter_kernel has reconstructed.
-__global__ __launch_bounds__(256) void png_crop_kernel(const uint8_t* __restrict__ desc, const uint8_t* __restrict__ planes, size_t stride,
-                                                       int h, int w, int bpp, int bgr, const double* __restrict__ minv, RoiChunk rois,
-                                                       int img0, int oh, int ow, uint8_t* __restrict__ out) {
+// The crop tail (crop_tail.h) of frame img0 + blockIdx.y: the window bounds the rows png_unfilter_kernel has reconstructed.
+__global__ __launch_bounds__(kCropThreads) void png_crop_kernel(const uint8_t* __restrict__ desc, const uint8_t* __restrict__ planes, size_t stride,
+                                                                int h, int w, int bpp, int bgr, const double* __restrict__ minv, RoiChunk rois,
+                                                                int img0, int oh, int ow, uint8_t* __restrict__ out) {
   const int img = img0 + (int)blockIdx.y;
-  const int32_t rx = rois.v[blockIdx.y][0], ry = rois.v[blockIdx.y][1], rw = rois.v[blockIdx.y][2], rh = rois.v[blockIdx.y][3];
   const int color_type = load_desc(desc, img).color_type;
   const uint8_t* palette = desc + (size_t)img * kDesc + kDescHead;
   const uint8_t* plane = planes + (size_t)img * stride;
-  const double* m = minv + (size_t)img * 6;
-  const int64_t total = (int64_t)oh * ow;
-  uint8_t* o = out + (size_t)img * total * 3;
-  for (int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x; pix < total; pix += (int64_t)gridDim.x * 256) {
-    const AffineSource p = affine_source(m, (int)(pix % ow), (int)(pix / ow));
-    const BilinearTap bil(p.a, p.b);
-    Rgb t[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const long long yy = p.y0 + (j >> 1), xx = p.x0 + (j & 1);
-      const bool ok = yy >= 0 && yy < h && xx >= 0 && xx < w && yy >= ry && yy < ry + rh && xx >= rx && xx < rx + rw;
-      t[j] = ok ? png_pixel(plane, 1 + (size_t)w * bpp, bpp, color_type, palette, (int)xx, (int)yy) : Rgb{0, 0, 0};
-    }
-    const uint8_t r = bil(t[0].r, t[1].r, t[2].r, t[3].r), g = bil(t[0].g, t[1].g, t[2].g, t[3].g), b = bil(t[0].b, t[1].b, t[2].b, t[3].b);
-    o[pix * 3] = bgr ? b : r;
-    o[pix * 3 + 1] = g;
-    o[pix * 3 + 2] = bgr ? r : b;
-  }
+  const auto px = [&](int32_t x, int32_t y) { return png_pixel(plane, 1 + (size_t)w * bpp, bpp, color_type, palette, x, y); };
+  crop_tail(px, h, w, false, bgr, minv + (size_t)img * 6, rois.v[blockIdx.y], oh, ow, out + (size_t)img * ((int64_t)oh * ow) * 3);
 }
 
 // the workspace: the descriptors as uploaded, the rows to unfilter per image, the planes
@@ -545,21 +519,14 @@ int32_t png_decode_crop_launch(const uint8_t* desc_host, const uint8_t* data, in
                                hipStream_t stream) {
   const Plan p = make_plan(n, h, w, channels, ws);
   if (int32_t rc = launch_inflate(p, desc_host, data, n, status, stream)) return rc;
-  const int64_t groups = ((int64_t)out_h * out_w + 255) / 256;
-  for (int img0 = 0; img0 < n; img0 += kRoiChunk) {
-    const int count = n - img0 < kRoiChunk ? n - img0 : kRoiChunk;
-    RoiChunk rois{};
-    for (int k = 0; k < count * 4; ++k) rois.v[k / 4][k % 4] = roi_host[(size_t)img0 * 4 + k];
+  for_each_roi_chunk(roi_host, n, [&](const RoiChunk& rois, int img0, int count) {
     hipLaunchKernelGGL(png_rows_kernel, dim3(1), dim3(kRoiChunk), 0, stream, rois, img0, count, p.rows);
-  }
+  });
   hipLaunchKernelGGL(png_unfilter_kernel, dim3((unsigned)n), dim3(kWave), 0, stream, p.planes, p.stride, h, w, channels, p.rows, status);
-  for (int img0 = 0; img0 < n; img0 += kRoiChunk) {
-    const int count = n - img0 < kRoiChunk ? n - img0 : kRoiChunk;
-    RoiChunk rois{};
-    for (int k = 0; k < count * 4; ++k) rois.v[k / 4][k % 4] = roi_host[(size_t)img0 * 4 + k];
-    hipLaunchKernelGGL(png_crop_kernel, dim3((unsigned)(groups < 4096 ? groups : 4096), (unsigned)count), dim3(256), 0, stream, p.desc,
-                       p.planes, p.stride, h, w, channels, bgr, minv, rois, img0, out_h, out_w, crops);
-  }
+  for_each_roi_chunk(roi_host, n, [&](const RoiChunk& rois, int img0, int count) {
+    hipLaunchKernelGGL(png_crop_kernel, crop_tail_grid(out_h, out_w, count), dim3(kCropThreads), 0, stream, p.desc, p.planes, p.stride, h, w,
+                       channels, bgr, minv, rois, img0, out_h, out_w, crops);
+  });
   SCP_CHECK_HIP(hipGetLastError());
   return SCPOSE_OK;
 }

@@ -152,12 +152,11 @@ class JointsDataset(Dataset):
         return input, torch.from_numpy(target), torch.from_numpy(target_weight), meta
 
     def _read_compressed(self, image_file):
-        """device_decode / device_decode_png: (the file's bytes, frame height, frame width) when the device decodes it -- a baseline
-        JPEG under device_decode (jpeg_read.parse_jpeg accepts it), a PNG of the decoded subset under device_decode_png
-        (png_read.parse_png accepts it and its chunks pass their CRCs) --, None when the file goes the way of device_crop (PIL here,
-        the window travels)."""
-        from ..jpeg_read import JpegError, parse_jpeg
-        from ..png_read import UnsupportedPng, parse_png
+        """device_decode / device_decode_png: (the file's bytes, frame height, frame width) when the device decodes it -- by
+        image_read.sniff, the rule ops.decode_crop applies to the batch: a baseline JPEG under device_decode, a PNG of the decoded subset
+        under device_decode_png --, None when the file goes the way of device_crop (PIL here, the window travels)."""
+        from ..image_read import sniff
+        from ..jpeg_read import JpegError
         if not self.device_crop:
             raise ValueError("device_decode needs device_crop: the device decodes a frame straight into its crop")
         if self.numpy_transform:
@@ -167,22 +166,11 @@ class JointsDataset(Dataset):
                 raw = fh.read()
         except OSError:
             return None
-        head = None
-        if self.device_decode:
-            try:
-                head = parse_jpeg(raw)
-            except JpegError:
-                pass
-        if head is None and self.device_decode_png:
-            try:
-                head = parse_png(raw)
-                if not head.crc_ok:
-                    head = None
-            except UnsupportedPng:
-                pass
-        if head is None:
+        try:
+            kind, head, _ = sniff(raw, jpeg=self.device_decode, png=self.device_decode_png)
+        except JpegError:                   # a JPEG with a broken table: PIL says what it means
             return None
-        return raw, int(head.height), int(head.width)
+        return (raw, int(head.height), int(head.width)) if kind else None
 
     @staticmethod
     def is_compressed(input):

@@ -3,13 +3,14 @@
 Every function here launches HIP kernels from libscpose_hip.so on the current torch
 stream; tensors must live on a ROCm device.  Nothing falls back to eager PyTorch.
 """
+import collections
 import ctypes
 from ctypes import c_int32, c_int64, c_void_p, c_char_p, c_size_t, c_double
 
 import numpy as np
 import torch
 
-from . import _native as nat
+from . import _native as nat, image_read, jpeg_read as jr, png_read as pr
 
 _TORCH_DT = {nat.DT_BF16: torch.bfloat16, nat.DT_F16: torch.float16}
 _DT_OF = {"bf16": nat.DT_BF16, "f16": nat.DT_F16, "fp16": nat.DT_F16, "bfloat16": nat.DT_BF16,
@@ -575,25 +576,35 @@ def _aedat4_raise(status, hw):
         raise nat.NativeError("unpack_events_aedat4: status %d" % status)
 
 
-# ------------------------------------------------------------------ baseline JPEG files -> frames
+# ------------------------------------------------------------------ image files (baseline JPEG, PNG) -> frames or network crops
 JPEG_MAX_ROUNDS = 96          # launches of the relaxation (measured distribution and head-room)
-_JPEG_WORKSPACE = {}          # device index -> uint8 tensor, grown on demand (2 bytes per coefficient: too large to allocate per call)
+_IMAGE_WORKSPACE = {}         # device index -> uint8 tensor, grown on demand (2 bytes per coefficient: too large to allocate per call)
+_JPEG_WORKSPACE = _IMAGE_WORKSPACE      # its name before the PNG decoder shared it: the suite of the commit before the rename pokes it
 
 
-def _jpeg_workspace(dev, nbytes):
-    ws = _JPEG_WORKSPACE.get(dev.index)
+def _image_workspace(dev, nbytes):
+    ws = _IMAGE_WORKSPACE.get(dev.index)
     if ws is None or ws.numel() < nbytes:
-        _JPEG_WORKSPACE.pop(dev.index, None)
+        _IMAGE_WORKSPACE.pop(dev.index, None)
         ws = None
         ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-        _JPEG_WORKSPACE[dev.index] = ws
+        _IMAGE_WORKSPACE[dev.index] = ws
     return ws
 
 
-def _jpeg_decode_group(headers, files, rgb, max_rounds, dev, out=None, y_out=None, crop=None):
+def _crop_target(crop, n, dev):
+    """crop = (minv float64 (n, 6), roi int32 (n, 4), out_h, out_w) -> (the crops to fill, the arguments minv .. crops of a
+    scpose_*_decode_crop call, what those point to)"""
+    minv, roi, oh, ow = crop
+    d_minv = torch.from_numpy(np.ascontiguousarray(minv, dtype=np.float64)).to(dev, non_blocking=True)
+    roi = np.ascontiguousarray(roi, dtype=np.int32)      # host memory: read before the call returns
+    out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=dev)
+    return out, (_ptr(d_minv), c_void_p(roi.ctypes.data), oh, ow, _ptr(out)), (d_minv, roi)
+
+
+def _jpeg_decode_group(headers, files, rgb, dev, crop=None, max_rounds=JPEG_MAX_ROUNDS, out=None, y_out=None):
     """One device call on the current stream for images of one geometry; -> (frames, status list): scpose_jpeg_decode, or with
-    crop = (minv float64 (n, 6), roi int32 (n, 4), out_h, out_w) scpose_jpeg_decode_crop -> (crops, status list)."""
-    from . import jpeg_read as jr
+    crop (_crop_target) scpose_jpeg_decode_crop -> (crops, status list)."""
     h, w, mode = headers[0].geometry
     n = len(headers)
     desc, rows, data, max_subs = jr.pack_batch(headers, files)
@@ -604,7 +615,7 @@ def _jpeg_decode_group(headers, files, rgb, max_rounds, dev, out=None, y_out=Non
         d_rows = torch.from_numpy(rows).to(dev, non_blocking=True)
         d_data = torch.from_numpy(data).to(dev, non_blocking=True)
         status = torch.empty(n, dtype=torch.int32, device=dev)
-        work = _jpeg_workspace(dev, ws)
+        work = _image_workspace(dev, ws)
         front = (_ptr(d_desc), _ptr(d_rows), int(rows.shape[0]), _ptr(d_data), int(data.size), n, h, w, jr.MODES[mode], int(max_subs),
                  0 if rgb else 1, int(max_rounds))
         if crop is None:
@@ -612,13 +623,50 @@ def _jpeg_decode_group(headers, files, rgb, max_rounds, dev, out=None, y_out=Non
                 out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
             nat.check(lib.scpose_jpeg_decode(*front, _ptr(out), _ptr(y_out), _ptr(status), _ptr(work), ws, _stream()), "jpeg_decode")
         else:
-            minv, roi, oh, ow = crop
-            d_minv = torch.from_numpy(np.ascontiguousarray(minv, dtype=np.float64)).to(dev, non_blocking=True)
-            roi = np.ascontiguousarray(roi, dtype=np.int32)      # host memory: read before the call returns
-            out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=dev)
-            nat.check(lib.scpose_jpeg_decode_crop(*front, _ptr(d_minv), c_void_p(roi.ctypes.data), oh, ow, _ptr(out), _ptr(status),
-                                                  _ptr(work), ws, _stream()), "jpeg_decode_crop")
+            out, target, alive = _crop_target(crop, n, dev)
+            nat.check(lib.scpose_jpeg_decode_crop(*front, *target, _ptr(status), _ptr(work), ws, _stream()), "jpeg_decode_crop")
         return out, status.tolist()
+
+
+def _png_decode_group(headers, files, rgb, dev, crop=None, max_rounds=None):
+    """One device call on the current stream for PNGs of one geometry; -> (frames, status list): scpose_png_decode, or with
+    crop (_crop_target) scpose_png_decode_crop -> (crops, status list)."""
+    h, w, channels = headers[0].geometry
+    n = len(headers)
+    desc, data = pr.pack_batch(headers, files)         # desc stays on the host: the library checks and uploads it
+    lib = nat.lib()
+    ws = _query_bytes("png_decode_workspace_bytes", n, h, w, channels)
+    with torch.cuda.device(dev):
+        d_data = torch.from_numpy(data).to(dev, non_blocking=True)
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        work = _image_workspace(dev, ws)
+        front = (c_void_p(desc.ctypes.data), _ptr(d_data), int(data.size), n, h, w, channels, 0 if rgb else 1)
+        if crop is None:
+            out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+            nat.check(lib.scpose_png_decode(*front, _ptr(out), _ptr(status), _ptr(work), ws, _stream()), "png_decode")
+        else:
+            out, target, alive = _crop_target(crop, n, dev)
+            nat.check(lib.scpose_png_decode_crop(*front, *target, _ptr(status), _ptr(work), ws, _stream()), "png_decode_crop")
+        return out, status.tolist()                    # the copy back waits for the stream: desc has been read by then
+
+
+def _jpeg_judge(who, i, st, rounds_cap):
+    """One image's status word -> None: decoded on the device, or why the host decodes it; raises for a corrupt stream"""
+    # not converged: the walk started from entries that are not the stream's, so CORRUPT says nothing; the host decides
+    if st & nat.JPEG_NOT_CONVERGED:
+        return "entry states not converged after %d rounds" % rounds_cap
+    if st & nat.JPEG_CORRUPT:
+        raise jr.JpegError("%s: file %d: corrupt or truncated entropy-coded data" % (who, i))
+    return None
+
+
+def _png_judge(who, i, st, rounds_cap):
+    """The same for a PNG: the device never decides what a damaged file means"""
+    if not st:
+        return None
+    names = [w for bit, w in ((nat.PNG_CORRUPT, "corrupt deflate stream"), (nat.PNG_CHECKSUM, "Adler-32 mismatch"),
+                              (nat.PNG_FILTER, "filter type above 4")) if st & bit]
+    return "device status %d (%s)" % (st, ", ".join(names))
 
 
 def _pil_decode(data, rgb):
@@ -630,15 +678,31 @@ def _pil_decode(data, rgb):
     return arr if rgb else arr[:, :, ::-1].copy()
 
 
-def _jpeg_host_decode(data, rgb):
-    from . import jpeg_read as jr
-    try:
+def _jpeg_host_decode(data, rgb, who, i):
+    try:                                   # the message names decode_jpeg and no file, whoever calls: callers match on it
         return _pil_decode(data, rgb)
     except Exception as e:
         raise jr.JpegError("decode_jpeg: the host decoder cannot read the file either: %s" % e)
 
 
-def _jpeg_device(device, who):
+def _png_host_decode(data, rgb, who, i):
+    try:
+        return _pil_decode(data, rgb)
+    except Exception as e:
+        raise pr.PngError("%s: file %d: %s" % (who, i, e))
+
+
+# What the batch driver asks of a device decoder: group(headers, files, rgb, dev, crop, rounds_cap) -> (tensor, status list), one
+# call and one read-back; judge (above); host_decode(data, rgb, who, i) -> PIL's pixels, or the format's error with PIL's message;
+# error, unsupported: what a file that cannot be decoded, or that fallback=False keeps from the host, raises.
+_ImageFormat = collections.namedtuple("_ImageFormat", "group judge host_decode error unsupported")
+_FORMATS = {
+    "jpeg": _ImageFormat(_jpeg_decode_group, _jpeg_judge, _jpeg_host_decode, jr.JpegError, jr.UnsupportedJpeg),
+    "png": _ImageFormat(_png_decode_group, _png_judge, _png_host_decode, pr.PngError, pr.UnsupportedPng),
+}
+
+
+def _image_device(device, who):
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     if dev.type != "cuda":
         raise nat.NativeError("%s needs a ROCm device (got %s); there is no CPU path" % (who, dev))
@@ -663,36 +727,77 @@ def _file_blobs(files, who):
     return blobs
 
 
-def _jpeg_parse(files, fallback, who, key):
-    """files (bytes, uint8 arrays / tensors or paths) -> (blobs, headers, host, groups): the bytes of each file, its JpegHeader or
-    None, {index: reason} for the files jpeg_read.parse_jpeg refuses, and {key(header): [indices]}, one device call each."""
-    from . import jpeg_read as jr
+def _decode_files(who, files, kinds, rgb, dev, fallback, crop=None, max_rounds=None):
+    """The batch driver of decode_jpeg, decode_png and decode_crop.  kinds = (jpeg, png): the device decoders on offer, as for
+    image_read.sniff, which says per file who takes it.  crop: None for frames, else crop(indices, (h, w)) -> the crop argument of
+    the group call for those files, all of that frame size.  Files are grouped by (decoder, geometry); every group is one call.
+    -> (parts, host, facts).  parts: [(file indices, their rows of a group's tensor)], what the device decoded.  host: {index: reason},
+    the files left to the host decoder (fallback=False: the first one raises instead); facts["host_px"] has their pixels.
+    facts["rounds"]: per file the relaxation rounds used (0: no JPEG decoded on the device); facts["png"]: the indices png_decode.hip
+    decoded; facts["device"]: per file whether the device decoded it."""
     blobs = _file_blobs(files, who)
-    headers, host, groups = [None] * len(blobs), {}, {}
+    n, rounds_cap = len(blobs), JPEG_MAX_ROUNDS if max_rounds is None else int(max_rounds)
+    heads, fmts, host, groups = [None] * n, [None] * n, {}, {}
     for i, b in enumerate(blobs):
-        try:
-            headers[i] = jr.parse_jpeg(b)
-            groups.setdefault(key(headers[i]), []).append(i)
-        except jr.UnsupportedJpeg as e:
-            if not fallback:
-                raise
-            host[i] = str(e)
-    return blobs, headers, host, groups
+        kind, heads[i], reason = image_read.sniff(b, *kinds)
+        # a refusal is the PNG side's (its error classes, its host message) when the file is a PNG or no other decoder was on offer
+        fmts[i] = _FORMATS[kind or ("png" if kinds[1] and (not kinds[0] or image_read.is_png(b)) else "jpeg")]
+        if kind:
+            groups.setdefault((kind, heads[i].geometry), []).append(i)
+        elif fallback:
+            host[i] = reason
+        elif reason == image_read.BAD_CRC:
+            raise fmts[i].error("%s: file %d: %s" % (who, i, reason))
+        else:
+            raise fmts[i].unsupported(reason)
+    facts = {"rounds": [0] * n, "png": [], "device": [False] * n}
+    parts = []
+    for (kind, geom), idx in groups.items():
+        fmt = _FORMATS[kind]
+        out, status = fmt.group([heads[i] for i in idx], [blobs[i] for i in idx], rgb, dev, crop(idx, geom[:2]) if crop else None, rounds_cap)
+        keep = []
+        for row, i in enumerate(idx):
+            facts["rounds"][i] = (status[row] >> 8) & 255          # a PNG's status word has no such byte
+            reason = fmt.judge(who, i, status[row], rounds_cap)
+            if reason is None:
+                keep.append(row)
+            elif fallback:
+                host[i] = reason
+            else:
+                raise fmt.error("%s: file %d: %s" % (who, i, reason))
+        if len(keep) < len(idx):
+            out, idx = out[torch.tensor(keep, dtype=torch.int64, device=dev)], [idx[row] for row in keep]
+        if idx:
+            parts.append((idx, out))
+            for i in idx:
+                facts["device"][i] = True
+            if kind == "png":
+                facts["png"] += idx
+    facts["host_px"] = {i: fmts[i].host_decode(blobs[i], rgb, who, i) for i in sorted(host)}
+    return parts, host, facts
 
 
-def _jpeg_status(who, i, st, rounds_cap, fallback, host):
-    """One image's status word: raises for a corrupt stream; a stream that has not converged goes to `host` (or raises); -> decoded on the device"""
-    from . import jpeg_read as jr
-    # not converged: the walk started from entries that are not the stream's, so CORRUPT says nothing; the host decides
-    if st & nat.JPEG_CORRUPT and not st & nat.JPEG_NOT_CONVERGED:
-        raise jr.JpegError("%s: file %d: corrupt or truncated entropy-coded data" % (who, i))
-    if st & nat.JPEG_NOT_CONVERGED:
-        reason = "entry states not converged after %d rounds" % rounds_cap
-        if not fallback:
-            raise jr.JpegError("%s: file %d: %s" % (who, i, reason))
-        host[i] = reason
-        return False
-    return True
+def _assemble(parts, n, dev):
+    """parts [(indices, rows)] that cover 0 .. n - 1 -> the (n, ...) tensor; a part that is everything, in order, is returned itself"""
+    if len(parts) == 1 and parts[0][0] == list(range(n)):
+        return parts[0][1]
+    with torch.cuda.device(dev):
+        out = torch.empty((n,) + tuple(parts[0][1].shape[1:]), dtype=torch.uint8, device=dev)
+        for idx, rows in parts:
+            out.index_copy_(0, torch.tensor(idx, dtype=torch.int64, device=dev), rows)
+    return out
+
+
+def _decode_frames(who, files, kinds, rgb, device, fallback, max_rounds=None):
+    """decode_jpeg and decode_png behind their info: -> ((N, H, W, 3) frames, host, facts) of _decode_files; one frame size or ValueError"""
+    dev = _image_device(device, who)
+    parts, host, facts = _decode_files(who, files, kinds, rgb, dev, fallback, max_rounds=max_rounds)
+    sizes = {tuple(rows.shape[1:3]) for _, rows in parts} | {a.shape[:2] for a in facts["host_px"].values()}
+    if len(sizes) != 1:
+        raise ValueError("%s: the frames have different sizes %s: decode them in separate calls" % (who, sorted(sizes)))
+    if host:
+        parts.append((sorted(host), torch.from_numpy(np.stack([facts["host_px"][i] for i in sorted(host)])).to(dev)))
+    return _assemble(parts, len(facts["rounds"]), dev), host, facts
 
 
 def decode_jpeg(files, rgb=True, device=None, max_rounds=None, fallback=True):
@@ -702,33 +807,20 @@ def decode_jpeg(files, rgb=True, device=None, max_rounds=None, fallback=True):
     info = {"rounds": per image the relaxation rounds used (0: not decoded on the device), "fallback": {index: reason}}.
     A file jpeg_read.parse_jpeg refuses, or one whose entry states have not converged after max_rounds launches, is decoded by PIL
     on the host when `fallback`, else raises UnsupportedJpeg / JpegError.  A corrupt or truncated stream always raises JpegError."""
-    from . import jpeg_read as jr
-    dev, rounds_cap = _jpeg_device(device, "decode_jpeg"), JPEG_MAX_ROUNDS if max_rounds is None else int(max_rounds)
-    blobs, headers, host, groups = _jpeg_parse(files, fallback, "decode_jpeg", lambda h: h.geometry)
-    n = len(blobs)
-    rounds = [0] * n
-    decoded = {}                    # index -> (group tensor, row)
-    for geom, idx in groups.items():
-        frames, status = _jpeg_decode_group([headers[i] for i in idx], [blobs[i] for i in idx], rgb, rounds_cap, dev)
-        for row, i in enumerate(idx):
-            rounds[i] = (status[row] >> 8) & 255
-            if _jpeg_status("decode_jpeg", i, status[row], rounds_cap, fallback, host):
-                decoded[i] = (frames, row)
-    host_px = {i: _jpeg_host_decode(blobs[i], rgb) for i in host}
-    sizes = {(h.height, h.width) for i, h in enumerate(headers) if i in decoded} | {a.shape[:2] for a in host_px.values()}
-    if len(sizes) != 1:
-        raise ValueError("decode_jpeg: the frames have different sizes %s: decode them in separate calls" % sorted(sizes))
-    info = {"rounds": rounds, "fallback": host}
-    if len(groups) == 1 and not host:
-        return next(iter(decoded.values()))[0], info
-    (hh, ww), = sizes
-    with torch.cuda.device(dev):
-        out = torch.empty((n, hh, ww, 3), dtype=torch.uint8, device=dev)
-        for i, (frames, row) in decoded.items():
-            out[i].copy_(frames[row])
-        for i, arr in host_px.items():
-            out[i].copy_(torch.from_numpy(np.ascontiguousarray(arr)))
-    return out, info
+    out, host, facts = _decode_frames("decode_jpeg", files, (True, False), rgb, device, fallback, max_rounds)
+    return out, {"rounds": facts["rounds"], "fallback": host}
+
+
+def decode_png(files, rgb=True, device=None, fallback=True):
+    """PNG files -> ((N, H, W, 3) uint8 frames on the device, info), decoded by csrc/png_decode.hip bit for bit as PIL's
+    Image.open(f).convert("RGB") decodes them.  files: a list of bytes or of paths; all frames must have one size.  rgb: R, G, B order,
+    else B, G, R.  Files are grouped by (height, width, channels) and every group is one call.
+    info = {"device": per file whether the device decoded it, "fallback": {index: reason}}.
+    A file png_read.parse_png refuses (interlaced, 1/2/4/16-bit, APNG, not a PNG), one that fails a chunk CRC and one whose status word
+    is not 0 are the host decoder's: PIL returns pixels (bytes after the stream, say) or raises, and a raise becomes PngError with PIL's
+    message -- the device never decides what a damaged file means.  fallback=False: UnsupportedPng / PngError at once."""
+    out, host, facts = _decode_frames("decode_png", files, (False, True), rgb, device, fallback)
+    return out, {"device": facts["device"], "fallback": host}
 
 
 def decode_crop(files, trans, out_wh, rgb=True, device=None, max_rounds=None, fallback=True, png=False):
@@ -742,177 +834,21 @@ def decode_crop(files, trans, out_wh, rgb=True, device=None, max_rounds=None, fa
     csrc/png_decode.hip (rounds 0), info gains "png": the indices decoded that way; a PNG whose status word is not 0 takes the PIL row
     (PngError when PIL raises, or at once without `fallback`).  png=False: a PNG is just a file parse_jpeg refuses."""
     from .utils.transforms import invert_affine_cv
-    dev, rounds_cap = _jpeg_device(device, "decode_crop"), JPEG_MAX_ROUNDS if max_rounds is None else int(max_rounds)
-    blobs, headers, host, groups = _jpeg_parse(files, fallback or png, "decode_crop", lambda h: h.geometry)
-    n = len(blobs)
-    trans = np.asarray(trans, dtype=np.float64).reshape(n, 2, 3)
+    dev = _image_device(device, "decode_crop")
+    files = _file_blobs(files, "decode_crop")
+    trans = np.asarray(trans, dtype=np.float64).reshape(len(files), 2, 3)
     ow, oh = int(out_wh[0]), int(out_wh[1])
-    rounds, parts = [0] * n, []            # parts: (row indices, crops of those rows)
-    png_rows, png_host = [], set()         # decoded by png_decode.hip; PNGs the host decodes after all
-    if png:
-        from . import jpeg_read as jr, png_read as pr
-        png_headers, png_groups = {}, {}
-        for i in sorted(host):
-            try:
-                hd = pr.parse_png(blobs[i])
-            except pr.UnsupportedPng as e:
-                is_png = blobs[i][:8] == pr.SIGNATURE
-                if is_png:
-                    host[i] = str(e)                   # a PNG outside the subset: its own reason, not "not a JPEG"
-                    png_host.add(i)                    # ... and PngError, not JpegError, should PIL not read it either
-                if not fallback:
-                    if is_png:
-                        raise
-                    raise jr.UnsupportedJpeg(host[i])  # neither format: what png=False raises for the file
-                continue
-            if not hd.crc_ok:
-                if not fallback:
-                    raise pr.PngError("decode_crop: file %d: a chunk fails its CRC" % i)
-                host[i] = "a chunk fails its CRC"
-                png_host.add(i)
-                continue
-            png_headers[i] = hd
-            png_groups.setdefault(hd.geometry, []).append(i)
-            del host[i]
-        for geom, idx in png_groups.items():
-            minv = np.stack([np.asarray(invert_affine_cv(trans[i]), dtype=np.float64).reshape(6) for i in idx])
-            roi = np.array([warp_window(trans[i], (ow, oh), geom[:2]) for i in idx], dtype=np.int32)
-            crops, status = _png_decode_group([png_headers[i] for i in idx], [blobs[i] for i in idx], rgb, dev, crop=(minv, roi, oh, ow))
-            keep = []
-            for row, i in enumerate(idx):
-                if status[row] == 0:
-                    keep.append(row)
-                    continue
-                if not fallback:
-                    raise pr.PngError("decode_crop: file %d: %s" % (i, _png_status_words(status[row])))
-                host[i] = _png_status_words(status[row])
-                png_host.add(i)
-            if len(keep) < len(idx):
-                crops, idx = crops[torch.tensor(keep, dtype=torch.int64, device=dev)], [idx[row] for row in keep]
-            if idx:
-                parts.append((idx, crops))
-                png_rows += idx
-    for geom, idx in groups.items():
+
+    def crop(idx, frame_hw):
         minv = np.stack([np.asarray(invert_affine_cv(trans[i]), dtype=np.float64).reshape(6) for i in idx])
-        roi = np.array([warp_window(trans[i], (ow, oh), geom[:2]) for i in idx], dtype=np.int32)
-        crops, status = _jpeg_decode_group([headers[i] for i in idx], [blobs[i] for i in idx], rgb, rounds_cap, dev, crop=(minv, roi, oh, ow))
-        for row, i in enumerate(idx):
-            rounds[i] = (status[row] >> 8) & 255
-        keep = [row for row, i in enumerate(idx) if _jpeg_status("decode_crop", i, status[row], rounds_cap, fallback, host)]
-        if len(keep) < len(idx):
-            crops, idx = crops[torch.tensor(keep, dtype=torch.int64, device=dev)], [idx[row] for row in keep]
-        if idx:
-            parts.append((idx, crops))
+        return minv, np.array([warp_window(trans[i], (ow, oh), frame_hw) for i in idx], dtype=np.int32), oh, ow
+    parts, host, facts = _decode_files("decode_crop", files, (True, bool(png)), rgb, dev, fallback, crop, max_rounds)
     if host:
-        idx = sorted(host)
-        parts.append((idx, crop_warp([_png_host_decode(blobs[i], rgb, "decode_crop", i) if i in png_host else _jpeg_host_decode(blobs[i], rgb)
-                                      for i in idx], trans[idx], (ow, oh), device=dev)))
-    info = {"rounds": rounds, "fallback": host}
+        parts.append((sorted(host), crop_warp([facts["host_px"][i] for i in sorted(host)], trans[sorted(host)], (ow, oh), device=dev)))
+    info = {"rounds": facts["rounds"], "fallback": host}
     if png:
-        info["png"] = sorted(png_rows)
-    if len(parts) == 1 and parts[0][0] == list(range(n)):
-        return parts[0][1], info
-    with torch.cuda.device(dev):
-        out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=dev)
-        for idx, crops in parts:
-            out.index_copy_(0, torch.tensor(idx, dtype=torch.int64, device=dev), crops)
-    return out, info
-
-
-# ------------------------------------------------------------------ PNG files -> frames
-def _png_status_words(st):
-    names = [w for bit, w in ((nat.PNG_CORRUPT, "corrupt deflate stream"), (nat.PNG_CHECKSUM, "Adler-32 mismatch"),
-                              (nat.PNG_FILTER, "filter type above 4")) if st & bit]
-    return "device status %d (%s)" % (st, ", ".join(names))
-
-
-def _png_host_decode(data, rgb, who, i):
-    from . import png_read as pr
-    try:
-        return _pil_decode(data, rgb)
-    except Exception as e:
-        raise pr.PngError("%s: file %d: %s" % (who, i, e))
-
-
-def _png_decode_group(headers, files, rgb, dev, crop=None):
-    """One device call on the current stream for PNGs of one geometry; -> (frames, status list): scpose_png_decode, or with
-    crop = (minv float64 (n, 6), roi int32 (n, 4), out_h, out_w) scpose_png_decode_crop -> (crops, status list)."""
-    from . import png_read as pr
-    h, w, channels = headers[0].geometry
-    n = len(headers)
-    desc, data = pr.pack_batch(headers, files)         # desc stays on the host: the library checks and uploads it
-    lib = nat.lib()
-    ws = _query_bytes("png_decode_workspace_bytes", n, h, w, channels)
-    with torch.cuda.device(dev):
-        d_data = torch.from_numpy(data).to(dev, non_blocking=True)
-        status = torch.empty(n, dtype=torch.int32, device=dev)
-        work = _jpeg_workspace(dev, ws)
-        front = (c_void_p(desc.ctypes.data), _ptr(d_data), int(data.size), n, h, w, channels, 0 if rgb else 1)
-        if crop is None:
-            out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
-            nat.check(lib.scpose_png_decode(*front, _ptr(out), _ptr(status), _ptr(work), ws, _stream()), "png_decode")
-        else:
-            minv, roi, oh, ow = crop
-            d_minv = torch.from_numpy(np.ascontiguousarray(minv, dtype=np.float64)).to(dev, non_blocking=True)
-            roi = np.ascontiguousarray(roi, dtype=np.int32)      # host memory: read before the call returns
-            out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=dev)
-            nat.check(lib.scpose_png_decode_crop(*front, _ptr(d_minv), c_void_p(roi.ctypes.data), oh, ow, _ptr(out), _ptr(status),
-                                                 _ptr(work), ws, _stream()), "png_decode_crop")
-        return out, status.tolist()                    # the copy back waits for the stream: desc has been read by then
-
-
-def decode_png(files, rgb=True, device=None, fallback=True):
-    """PNG files -> ((N, H, W, 3) uint8 frames on the device, info), decoded by csrc/png_decode.hip bit for bit as PIL's
-    Image.open(f).convert("RGB") decodes them.  files: a list of bytes or of paths; all frames must have one size.  rgb: R, G, B order,
-    else B, G, R.  Files are grouped by (height, width, channels) and every group is one call.
-    info = {"device": per file whether the device decoded it, "fallback": {index: reason}}.
-    A file png_read.parse_png refuses (interlaced, 1/2/4/16-bit, APNG, not a PNG), one that fails a chunk CRC and one whose status word
-    is not 0 are the host decoder's: PIL returns pixels (bytes after the stream, say) or raises, and a raise becomes PngError with PIL's
-    message -- the device never decides what a damaged file means.  fallback=False: UnsupportedPng / PngError at once."""
-    from . import png_read as pr
-    dev = _jpeg_device(device, "decode_png")
-    blobs = _file_blobs(files, "decode_png")
-    n = len(blobs)
-    headers, host, groups = [None] * n, {}, {}
-    for i, b in enumerate(blobs):
-        try:
-            headers[i] = pr.parse_png(b)
-        except pr.UnsupportedPng as e:
-            if not fallback:
-                raise
-            host[i] = str(e)
-            continue
-        if not headers[i].crc_ok:
-            if not fallback:
-                raise pr.PngError("decode_png: file %d: a chunk fails its CRC" % i)
-            host[i] = "a chunk fails its CRC"
-            continue
-        groups.setdefault(headers[i].geometry, []).append(i)
-    decoded = {}                    # index -> (group tensor, row)
-    for geom, idx in groups.items():
-        frames, status = _png_decode_group([headers[i] for i in idx], [blobs[i] for i in idx], rgb, dev)
-        for row, i in enumerate(idx):
-            if status[row] == 0:
-                decoded[i] = (frames, row)
-            elif not fallback:
-                raise pr.PngError("decode_png: file %d: %s" % (i, _png_status_words(status[row])))
-            else:
-                host[i] = _png_status_words(status[row])
-    host_px = {i: _png_host_decode(blobs[i], rgb, "decode_png", i) for i in host}
-    sizes = {(headers[i].height, headers[i].width) for i in decoded} | {a.shape[:2] for a in host_px.values()}
-    if len(sizes) != 1:
-        raise ValueError("decode_png: the frames have different sizes %s: decode them in separate calls" % sorted(sizes))
-    info = {"device": [i in decoded for i in range(n)], "fallback": host}
-    if len(groups) == 1 and not host:
-        return next(iter(decoded.values()))[0], info
-    (hh, ww), = sizes
-    with torch.cuda.device(dev):
-        out = torch.empty((n, hh, ww, 3), dtype=torch.uint8, device=dev)
-        for i, (frames, row) in decoded.items():
-            out[i].copy_(frames[row])
-        for i, arr in host_px.items():
-            out[i].copy_(torch.from_numpy(np.ascontiguousarray(arr)))
-    return out, info
+        info["png"] = sorted(facts["png"])
+    return _assemble(parts, len(files), dev), info
 
 
 # ------------------------------------------------------------------ frames -> baseline JPEG files; the pose overlay
@@ -955,7 +891,7 @@ def encode_jpeg(frames, quality=75, subsampling="420", device=None, comment=None
         out = torch.empty(cap.value, dtype=torch.uint8, device=dev)
         offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
         status = torch.empty(n, dtype=torch.int32, device=dev)
-        work = _jpeg_workspace(dev, ws)
+        work = _image_workspace(dev, ws)
         nat.check(lib.scpose_jpeg_encode(_ptr(frames), n, h, w, mode, int(quality), _ptr(huff), _ptr(d_head), len(head), _ptr(out),
                                          cap.value, _ptr(offsets), _ptr(status), _ptr(work), ws, _stream()), "jpeg_encode")
         off = offsets.tolist()

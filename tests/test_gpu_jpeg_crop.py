@@ -109,7 +109,7 @@ def test_no_skipped_sample_is_read(gpu_ops):
     first, _ = gpu_ops.decode_crop(files, trans, C.CROP_WH, fallback=False)                   # sizes the cached workspace
     got = []
     for fill in (0x00, 0xFF):
-        gpu_ops._JPEG_WORKSPACE[dev].fill_(fill)
+        gpu_ops._IMAGE_WORKSPACE[dev].fill_(fill)
         got.append(gpu_ops.decode_crop(files, trans, C.CROP_WH, fallback=False)[0])
     assert torch.equal(got[0], got[1]) and torch.equal(got[0], first) and torch.equal(first, reference(gpu_ops, frames, trans))
 
@@ -125,3 +125,12 @@ def test_batch_of_one_no_files_and_a_corrupt_stream(gpu_ops):
     cut = data[:h.data_start + (h.data_end - h.data_start) // 2] + b"\xff\xd9"
     with pytest.raises(J.JpegError, match="corrupt"):
         gpu_ops.decode_crop([data, cut], np.repeat(trans, 2, 0), C.CROP_WH)
+
+
+@pytest.mark.parametrize("mode", ("420", "gray"))
+def test_one_call_past_the_chunk_of_windows(gpu_ops, mode):
+    """130 files of one geometry: the windows of 128 travel with one launch of the crop tail, rows 128 and 129 with the next"""
+    files = [R.fixture(mode, C.CHUNK_SIZE[0], C.CHUNK_SIZE[1], 90, "noise", seed=100 + i) for i in range(C.CHUNK_N)]
+    assert len({J.parse_jpeg(f).geometry for f in files}) == 1
+    info = C.check_chunk_call(gpu_ops, files, [R.pil_decode(f) for f in files])
+    assert not info["fallback"] and min(info["rounds"]) >= 1

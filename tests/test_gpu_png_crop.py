@@ -124,7 +124,29 @@ def test_whatever_the_workspace_held(gpu_ops):
     first, _ = gpu_ops.decode_crop(files, trans, C.CROP_WH, fallback=False, png=True)
     got = []
     for fill in (0x00, 0xFF):
-        gpu_ops._JPEG_WORKSPACE[dev].fill_(fill)
+        gpu_ops._IMAGE_WORKSPACE[dev].fill_(fill)
         got.append(gpu_ops.decode_crop(files, trans, C.CROP_WH, fallback=False, png=True)[0])
     assert torch.equal(got[0], got[1]) and torch.equal(got[0], first)
     assert torch.equal(first, reference(gpu_ops, [pil_rgb(f) for f in files], trans))
+
+
+def chunk_png(color_type, seed):
+    return png_frame(C.CHUNK_SIZE, color_type, seed)
+
+
+@pytest.mark.parametrize("color_type", (2, 3))
+def test_one_call_past_the_chunk_of_windows(gpu_ops, color_type):
+    """130 files of one geometry: the windows of 128 travel with one launch of the rows and crop kernels, rows 128 and 129 with the next"""
+    files = [chunk_png(color_type, 300 + i) for i in range(C.CHUNK_N)]
+    info = C.check_chunk_call(gpu_ops, files, [pil_rgb(f) for f in files], png=True)
+    assert info["png"] == list(range(C.CHUNK_N)) and info["fallback"] == {} and info["rounds"] == [0] * C.CHUNK_N
+
+
+def test_jpegs_and_pngs_interleaved_past_the_chunk(gpu_ops):
+    """65 + 65: two groups in one call, each row back in its place"""
+    import jpeg_decode_restated as R
+    files = [R.fixture("420", C.CHUNK_SIZE[0], C.CHUNK_SIZE[1], 90, "noise", seed=500 + i) if i % 2 == 0 else chunk_png(2, 500 + i)
+             for i in range(C.CHUNK_N)]
+    info = C.check_chunk_call(gpu_ops, files, [pil_rgb(f) for f in files], png=True)
+    assert info["png"] == list(range(1, C.CHUNK_N, 2)) and info["fallback"] == {}
+    assert all((r >= 1) == (i % 2 == 0) for i, r in enumerate(info["rounds"]))

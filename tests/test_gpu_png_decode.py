@@ -96,7 +96,7 @@ def test_whatever_the_workspace_held(gpu_ops):
     first, _ = gpu_ops.decode_png(files, fallback=False)                  # sizes the cached workspace
     got = []
     for fill in (0x00, 0xFF):
-        gpu_ops._JPEG_WORKSPACE[dev].fill_(fill)
+        gpu_ops._IMAGE_WORKSPACE[dev].fill_(fill)
         got.append(gpu_ops.decode_png(files, fallback=False)[0])
     assert torch.equal(got[0], got[1]) and torch.equal(got[0], first)
     assert np.array_equal(first[0].cpu().numpy(), reference(names[0], files[0])[0])
@@ -110,7 +110,7 @@ def test_damaged_files_are_the_host_decoders(gpu_ops, name):
     if hd.crc_ok:
         device_status(gpu_ops, data)                                      # sizes the cached workspace
         for fill in (0x00, 0xFF, 0x03):                                   # whatever the workspace held: all-bad and all-good "filter bytes"
-            gpu_ops._JPEG_WORKSPACE[torch.cuda.current_device()].fill_(fill)
+            gpu_ops._IMAGE_WORKSPACE[torch.cuda.current_device()].fill_(fill)
             frame, got_status = device_status(gpu_ops, data)
             assert got_status == status, (name, fill, got_status, status)
             if status == 0:
@@ -136,7 +136,7 @@ def test_a_damaged_file_beside_good_ones(gpu_ops):
     assert all(np.array_equal(got[i].cpu().numpy(), w) for i, w in enumerate((want, reference("idat_crc", crc)[0], want)))
     with pytest.raises(pr.PngError, match="file 1"):
         gpu_ops.decode_png([good, bad, good])
-    gpu_ops._JPEG_WORKSPACE[torch.cuda.current_device()].fill_(0xFF)       # the message names what the stream is, not what the workspace held
+    gpu_ops._IMAGE_WORKSPACE[torch.cuda.current_device()].fill_(0xFF)       # the message names what the stream is, not what the workspace held
     with pytest.raises(pr.PngError, match=r"device status 1 \(corrupt deflate stream\)"):
         gpu_ops.decode_png([good, W.damaged_cases()["block_type_3"]], fallback=False)
     with pytest.raises(pr.PngError, match="CRC"):
