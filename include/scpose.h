@@ -129,6 +129,12 @@ int32_t scpose_hrnet_heatmap_size(scpose_hrnet_t h, int32_t height, int32_t widt
 /* number of kernel launches of one forward and total conv FLOPs (2*MAC) per frame. */
 int32_t scpose_hrnet_stats(scpose_hrnet_t h, int32_t height, int32_t width, int32_t* launches,
                            double* flops_per_frame, double* act_bytes_per_frame);
+/* the same two figures for the work the launches DO.  A NUM_CHANNELS entry that is no multiple of 16 is carried at
+ * the next multiple (its added planes are zero: zero weights, zero bias), so a W18 / W30 / W40 / W44 network executes
+ * more than scpose_hrnet_stats -- the algorithmic work at the widths the model describes -- reports.  Equal to
+ * scpose_hrnet_stats for widths that are multiples of 16. */
+int32_t scpose_hrnet_executed_stats(scpose_hrnet_t h, int32_t height, int32_t width,
+                                    double* flops_per_frame, double* act_bytes_per_frame);
 
 /* in: device pointer in in_fmt; heatmaps: device float32 N x J x H/4 x W/4 (scpose_hrnet_heatmap_size for the
  * hrnet_cms heads) (NCHW, raw scores,

@@ -83,6 +83,7 @@ SYMBOLS = {
     "scpose_hrnet_heatmap_size": (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32)]),
     "scpose_hrnet_stats": (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_int32), POINTER(c_double),
                                      POINTER(c_double)]),
+    "scpose_hrnet_executed_stats": (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_double), POINTER(c_double)]),
     "scpose_hrnet_forward": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p,
                                        c_void_p, c_size_t, c_void_p]),
     "scpose_hrnet_tail_fused": (c_int32, [c_void_p, c_int32, c_int32, c_int32, POINTER(c_int32)]),

@@ -346,8 +346,9 @@ int32_t flip_merge_launch(const float* a, const float* b, const int32_t* perm, i
                           float* out, hipStream_t stream);
 int32_t nchw_to_blocked_launch(const float* src, int N, int C, int H, int W, int dtype, void* dst,
                                hipStream_t stream);
+// Cd: channels of dst (the first Cd of the blocked tensor's C are copied); -1: all C
 int32_t blocked_to_nchw_launch(const void* src, int N, int C, int H, int W, int dtype, float* dst,
-                               hipStream_t stream);
+                               hipStream_t stream, int Cd = -1);
 
 // ---- decode / pnp --------------------------------------------------------------------------
 // head_fused.hip: last fuse sum + final_layer (+ decode) in one pass (pose_hrnet.py:256-263, :458; lib/core/inference.py:18-79)

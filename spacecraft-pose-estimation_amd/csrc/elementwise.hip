@@ -106,8 +106,10 @@ __global__ void nchw_to_blocked_kernel(const float* __restrict__ src, int N, int
   }
 }
 
+// Cd <= C: channels the float32 tensor has; the blocked tensor's planes beyond them are not copied (bounds: a store goes to
+// channel c < Cd of image n < N only, so dst needs N * Cd * H * W floats)
 template <int DT>
-__global__ void blocked_to_nchw_kernel(const void* __restrict__ src, int N, int C, int H, int W,
+__global__ void blocked_to_nchw_kernel(const void* __restrict__ src, int N, int C, int Cd, int H, int W,
                                        float* __restrict__ dst) {
   typedef typename EwDt<DT>::type T;
   const size_t HW = (size_t)H * W;
@@ -121,7 +123,7 @@ __global__ void blocked_to_nchw_kernel(const void* __restrict__ src, int N, int 
     const uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
     for (int j = 0; j < 8; ++j)
-      dst[(n * C + pl * 8 + j) * HW + pix] = ew_from<T>((w[j >> 1] >> ((j & 1) * 16)) & 0xffff);
+      if ((int)pl * 8 + j < Cd) dst[(n * Cd + pl * 8 + j) * HW + pix] = ew_from<T>((w[j >> 1] >> ((j & 1) * 16)) & 0xffff);
   }
 }
 
@@ -176,13 +178,15 @@ int32_t nchw_to_blocked_launch(const float* src, int N, int C, int H, int W, int
 }
 
 int32_t blocked_to_nchw_launch(const void* src, int N, int C, int H, int W, int dtype, float* dst,
-                               hipStream_t stream) {
+                               hipStream_t stream, int Cd) {
   SCP_REQUIRE(C % 8 == 0, "layout: C=%d must be a multiple of 8", C);
+  if (Cd < 0) Cd = C;
+  SCP_REQUIRE(Cd > 0 && Cd <= C, "layout: %d of %d channels", Cd, C);
   const size_t total = (size_t)N * (C / 8) * H * W;
   if (dtype == SCPOSE_DT_BF16)
-    hipLaunchKernelGGL(blocked_to_nchw_kernel<0>, dim3(ew_grid(total)), dim3(256), 0, stream, src, N, C, H, W, dst);
+    hipLaunchKernelGGL(blocked_to_nchw_kernel<0>, dim3(ew_grid(total)), dim3(256), 0, stream, src, N, C, Cd, H, W, dst);
   else
-    hipLaunchKernelGGL(blocked_to_nchw_kernel<1>, dim3(ew_grid(total)), dim3(256), 0, stream, src, N, C, H, W, dst);
+    hipLaunchKernelGGL(blocked_to_nchw_kernel<1>, dim3(ew_grid(total)), dim3(256), 0, stream, src, N, C, Cd, H, W, dst);
   SCP_CHECK_HIP(hipGetLastError());
   return SCPOSE_OK;
 }

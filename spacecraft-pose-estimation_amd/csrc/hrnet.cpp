@@ -29,33 +29,71 @@ static const double kBnEps = 1e-5;
 
 struct HostTensor { const float* p; int64_t n; };
 
+// A branch of real width c is carried at c rounded up to a multiple of 16 -- the granularity of every MFMA kernel's channel
+// loops (conv_igemm.hip: Cin % 16) -- so that any NUM_CHANNELS runs (W18, W30, W40, W44) on the kernels the multiples of 16 use.
+struct Chan {
+  int real, car;   // channels the model describes / channels the engine carries
+  bool operator==(const Chan& o) const { return real == o.real; }
+  bool operator!=(const Chan& o) const { return real != o.real; }
+};
+static Chan chan(int real) { return Chan{real, (real + 15) / 16 * 16}; }
+static Chan chan_exact(int c) { return Chan{c, c}; }   // never padded: NUM_JOINTS, the heads' tap maps
+
 struct Weights {
   std::map<std::string, HostTensor> m;
   bool allow_missing;
   std::string missing;  // first missing key
+  std::vector<std::vector<float>> padded;   // the zero-extended copies get() handed out (alive until hrnet_build returns)
 
-  const float* get(const std::string& k, int64_t numel) {
+  // The ONE place checkpoint tensors are read.  Tensor k of REAL shape [d0.real][d1.real][inner] (d1 = {1, 1} for a vector) comes
+  // back at its CARRIED shape [d0.car][d1.car][inner]: the checkpoint's values in the leading rows / columns, `fill` elsewhere --
+  // 0 for convolution weights and biases (an added output channel has zero weights and zero bias, an added input channel a zero
+  // column), BatchNorm's identity (weight 1, bias 0, mean 0, var 1) for its vectors, under which fold() leaves those zeros zero.
+  // Invariant: a carried plane beyond the real width holds +0.0 at every point of the forward -- out of a convolution (zero
+  // weights, zero bias: the accumulator starts at +0 and only ever adds +-0), through a residual add (+0 + +0), ReLU, a fuse sum
+  // and a nearest upsample -- and, its columns being zero, feeds nothing into a real plane.  That follows from the weights alone:
+  // no kernel knows which planes are padding.
+  // The element count is checked against the REAL shape (a tensor that happens to have the carried shape is refused too).
+  // A width that is a multiple of 16 gets the checkpoint's own pointer back: nothing is copied, nothing changes.
+  const float* get(const std::string& k, Chan d0, Chan d1, int64_t inner, float fill = 0.f) {
     auto it = m.find(k);
-    if (it == m.end() || it->second.n != numel) {
-      if (missing.empty()) missing = k + (it == m.end() ? "" : " (wrong size)");
+    if (it == m.end() || it->second.n != d0.real * d1.real * inner) {
+      if (missing.empty()) {
+        missing = k;
+        if (it != m.end()) {
+          char buf[160];
+          snprintf(buf, sizeof(buf), " (wrong size: %lld elements, the model's %d x %d x %lld has %lld)", (long long)it->second.n, d0.real,
+                   d1.real, (long long)inner, (long long)(d0.real * d1.real * inner));
+          missing += buf;
+        }
+      }
       return nullptr;
     }
-    return it->second.p;
+    if (d0.car == d0.real && d1.car == d1.real) return it->second.p;
+    padded.emplace_back((size_t)d0.car * d1.car * inner, fill);
+    std::vector<float>& v = padded.back();
+    for (int a = 0; a < d0.real; ++a)
+      for (int b = 0; b < d1.real; ++b)
+        std::copy(it->second.p + ((int64_t)a * d1.real + b) * inner, it->second.p + ((int64_t)a * d1.real + b + 1) * inner,
+                  v.begin() + ((int64_t)a * d1.car + b) * inner);
+    return v.data();
   }
+  const float* get(const std::string& k, Chan d0, float fill = 0.f) { return get(k, d0, Chan{1, 1}, 1, fill); }
 };
 
-// conv(+bn) -> folded f32 weight [cout][cin][k][k] and bias [cout]
-static bool fold(Weights& W, const std::string& conv, const std::string& bn, int cout, int cin,
+// conv(+bn) -> folded f32 weight [cout][cin][k][k] and bias [cout], at the carried widths
+static bool fold(Weights& W, const std::string& conv, const std::string& bn, Chan co, Chan ci,
                  int ks, bool conv_bias, std::vector<float>* w, std::vector<float>* b) {
-  const int64_t per = (int64_t)cin * ks * ks;
+  const int cout = co.car;
+  const int64_t per = (int64_t)ci.car * ks * ks;
   w->assign((size_t)cout * per, 0.f);
   b->assign(cout, 0.f);
-  const float* cw = W.get(conv + ".weight", cout * per);
-  const float* cb = conv_bias ? W.get(conv + ".bias", cout) : nullptr;
+  const float* cw = W.get(conv + ".weight", co, ci, ks * ks);
+  const float* cb = conv_bias ? W.get(conv + ".bias", co) : nullptr;
   const float *g = nullptr, *be = nullptr, *mu = nullptr, *var = nullptr;
   if (!bn.empty()) {
-    g = W.get(bn + ".weight", cout); be = W.get(bn + ".bias", cout);
-    mu = W.get(bn + ".running_mean", cout); var = W.get(bn + ".running_var", cout);
+    g = W.get(bn + ".weight", co, 1.f); be = W.get(bn + ".bias", co);
+    mu = W.get(bn + ".running_mean", co); var = W.get(bn + ".running_var", co, 1.f);
   }
   if (!W.missing.empty() && !W.allow_missing) return false;
   for (int o = 0; o < cout; ++o) {
@@ -75,8 +113,10 @@ static bool fold(Weights& W, const std::string& conv, const std::string& bn, int
 enum OpKind { OP_CONV = 1, OP_FUSE = 2, OP_BLOCK = 3, OP_HEAD = 4, OP_STEM2 = 5, OP_BNECK = 6, OP_FDOWN = 8 };   // OP_FDOWN: fuse row 0 + first down hops of branch 0 (fuse_down.hip; 7 is the fused tail's profile signature)   // OP_STEM2: fused stem (stem_fused.hip); OP_BNECK: fused Bottleneck (bottleneck.hip)   // OP_BLOCK: fused BasicBlock (conv_block_kernel.h); OP_HEAD: head.hip
 
 struct TensorDesc {
-  int C, ds;       // channels, log2 spatial downscale w.r.t. the network input
+  int C, ds;       // channels (as carried: Chan::car), log2 spatial downscale w.r.t. the network input
   int last_use;    // index of the last op reading it
+  int Cr;          // channels the model describes (Chan::real); planes Cr..C-1 hold +0.0 (Weights::get)
+  Chan chan() const { return Chan{Cr, C}; }
 };
 
 struct Op {
@@ -157,8 +197,8 @@ struct Builder {
   // Every tensor an op writes is named where it is created (scpose_hrnet_forward_tap): the reference module path that produces
   // it -- "layer1.<b>", "transition<k>.<i>[.<j>]", "stage<S>.<M>.branches.<B>.<K>[.conv1|.conv2]", "stage<S>.<M>.fuse_layers.<i>.<j>[.<k>]",
   // "stage<S>.<M>.out<i>", "<head>.tapmap".  Only the f32 levels of the hrnet_cms pyramid (OP_HEAD) stay unnamed.
-  int new_tensor(int C, int ds, const std::string& name) {
-    net->tensors.push_back(TensorDesc{C, ds, -1});
+  int new_tensor(Chan c, int ds, const std::string& name) {
+    net->tensors.push_back(TensorDesc{c.car, ds, -1, c.real});
     const int t = (int)net->tensors.size() - 1;
     if (!name.empty()) net->taps.emplace_back(name, t);
     return t;
@@ -172,14 +212,14 @@ struct Builder {
     return cname.size() > 2 && cname.compare(cname.size() - 2, 2, ".0") == 0 ? cname.substr(0, cname.size() - 2) : cname;
   }
   // y = [relu](conv_bn(x) [+ res]);  returns output tensor id (or -2 for heatmaps)
-  int conv(int x, const std::string& cname, const std::string& bname, int cout, int ks, int stride,
+  int conv(int x, const std::string& cname, const std::string& bname, Chan cout, int ks, int stride,
            bool relu, int res = -1, bool conv_bias = false, bool to_heatmaps = false) {
     if (status != SCPOSE_OK) return -1;
-    const int cin = net->tensors[x].C;
+    const Chan cin = net->tensors[x].chan();
     std::vector<float> w, b;
     if (!fold(*W, cname, bname, cout, cin, ks, conv_bias, &w, &b)) { status = SCPOSE_E_MISSING; return -1; }
     PackedConv pc;
-    const int32_t st = conv_upload(w.data(), b.data(), cout, cin, ks, stride, net->desc.dtype, &pc);
+    const int32_t st = conv_upload(w.data(), b.data(), cout.car, cin.car, ks, stride, net->desc.dtype, &pc);
     if (st != SCPOSE_OK) { status = st; return -1; }
     net->convs.push_back(pc);
     const int ds = net->tensors[x].ds + (stride == 2 ? 1 : 0);
@@ -197,9 +237,9 @@ struct Builder {
     const int cin = net->tensors[x].C;
     const bool proj = cin == 64;
     std::vector<float> w1, b1, w2, b2, w3, b3, wd, bd;
-    if (!fold(*W, p + ".conv1", p + ".bn1", 64, cin, 1, false, &w1, &b1) || !fold(*W, p + ".conv2", p + ".bn2", 64, 64, 3, false, &w2, &b2) ||
-        !fold(*W, p + ".conv3", p + ".bn3", 256, 64, 1, false, &w3, &b3) ||
-        (proj && !fold(*W, p + ".downsample.0", p + ".downsample.1", 256, 64, 1, false, &wd, &bd))) { status = SCPOSE_E_MISSING; return -1; }
+    if (!fold(*W, p + ".conv1", p + ".bn1", chan(64), chan(cin), 1, false, &w1, &b1) || !fold(*W, p + ".conv2", p + ".bn2", chan(64), chan(64), 3, false, &w2, &b2) ||
+        !fold(*W, p + ".conv3", p + ".bn3", chan(256), chan(64), 1, false, &w3, &b3) ||
+        (proj && !fold(*W, p + ".downsample.0", p + ".downsample.1", chan(256), chan(64), 1, false, &wd, &bd))) { status = SCPOSE_E_MISSING; return -1; }
     std::vector<uint16_t> pw1, pw2, pw3;
     std::vector<float> pb;
     bottleneck_pack(w1.data(), w2.data(), w3.data(), proj ? wd.data() : nullptr, b1.data(), b2.data(), b3.data(), proj ? bd.data() : nullptr,
@@ -215,29 +255,30 @@ struct Builder {
     if (status != SCPOSE_OK) { set_error("hrnet_create: uploading the fused Bottleneck weights failed"); return -1; }
     Op op{};
     op.kind = OP_BNECK; op.in = x; op.res = -1; op.conv = (int)net->bnecks.size() - 1; op.relu = 1;
-    op.out = new_tensor(256, net->tensors[x].ds, p);
+    op.out = new_tensor(chan(256), net->tensors[x].ds, p);
     push(op);
     return op.out;
   }
   // Bottleneck as a STAGE block (EXTRA.STAGEk.BLOCK = BOTTLENECK, pose_hrnet.py:266-269, :142-154): 4 * planes channels in and out,
-  // identity residual.  256 -> 64 -> 256 runs on the fused layer1 kernel, anything else as its three convolutions.
+  // identity residual.  256 -> 64 -> 256 runs on the fused layer1 kernel, anything else as its three convolutions.  The two
+  // widths are carried separately: planes p at chan(p) inside the block, 4p at chan(4p) between blocks (18 -> 32, 72 -> 80).
   int stage_bottleneck(int x, const std::string& p, int planes) {
     if (status != SCPOSE_OK) return -1;
     if (planes == 64 && net->tensors[x].C == 256 && bottleneck_fusable(256, 64, 256)) return bottleneck(x, p);
-    int y = conv(x, p + ".conv1", p + ".bn1", planes, 1, 1, true);
-    y = conv(y, p + ".conv2", p + ".bn2", planes, 3, 1, true);
-    y = conv(y, p + ".conv3", p + ".bn3", 4 * planes, 1, 1, true, x);
+    int y = conv(x, p + ".conv1", p + ".bn1", chan(planes), 1, 1, true);
+    y = conv(y, p + ".conv2", p + ".bn2", chan(planes), 3, 1, true);
+    y = conv(y, p + ".conv3", p + ".bn3", chan(4 * planes), 1, 1, true, x);
     if (y >= 0) rename_tap(y, p);
     return y;
   }
   // BasicBlock relu(conv2(relu(conv1(x))) + x): one fused launch when the pair qualifies, else two convolutions
-  int basic_block(int x, const std::string& p, int C) {
+  int basic_block(int x, const std::string& p, Chan C) {
     if (status != SCPOSE_OK) return -1;
     const size_t first = net->convs.size(), first_op = net->ops.size();
     const int u = conv(x, p + ".conv1", p + ".bn1", C, 3, 1, true);
     const int t = conv(u, p + ".conv2", p + ".bn2", C, 3, 1, true, x);
     if (t >= 0) rename_tap(t, p);   // the block's output; "<p>.conv1" stays while the two convolutions are separate launches
-    if (status != SCPOSE_OK || net->tensors[x].C != C) return t;
+    if (status != SCPOSE_OK || net->tensors[x].chan() != C) return t;
     if (!block_fusable(net->convs[first], net->convs[first + 1])) return t;
     // replace the two ops by one; the intermediate tensor u stays unused (never planned: last_use < 0) and is no tap
     net->ops.resize(first_op);
@@ -255,10 +296,10 @@ struct Builder {
   int head(int y, const std::string& name, int b, int K, int S, int prev, bool to_heatmaps) {
     if (status != SCPOSE_OK) return -1;
     const int C = net->tensors[y].C, J = net->desc.num_joints, M = 32, cpt = J <= 8 ? 8 : 16;
-    const float* wt = W->get(name + ".0.weight", (int64_t)C * M * K * K);   // ConvTranspose2d weight: (in, out, k, k)
-    const float* bt = W->get(name + ".0.bias", M);
-    const float* wc = W->get(name + ".1.weight", (int64_t)J * M);
-    const float* bc = W->get(name + ".1.bias", J);
+    const float* wt = W->get(name + ".0.weight", net->tensors[y].chan(), chan_exact(M), K * K);   // ConvTranspose2d weight: (in, out, k, k)
+    const float* bt = W->get(name + ".0.bias", chan_exact(M));
+    const float* wc = W->get(name + ".1.weight", chan_exact(J), chan_exact(M), 1);
+    const float* bc = W->get(name + ".1.bias", chan_exact(J));
     if (!W->missing.empty() && !W->allow_missing) { status = SCPOSE_E_MISSING; return -1; }
     const int cout = K * K * cpt;
     std::vector<float> w((size_t)cout * C, 0.f), zero(cout, 0.f);
@@ -285,28 +326,28 @@ struct Builder {
     net->convs.push_back(pc);
     Op cv{};
     cv.kind = OP_CONV; cv.in = y; cv.res = -1; cv.conv = (int)net->convs.size() - 1;
-    cv.out = new_tensor(cout, net->tensors[y].ds, name + ".tapmap");
+    cv.out = new_tensor(chan_exact(cout), net->tensors[y].ds, name + ".tapmap");
     push(cv);
     Op op{};
     op.kind = OP_HEAD; op.in = cv.out; op.res = prev; op.conv = -1; op.head = b;
     // an f32 map of J x (S*h) x (S*w) occupies as many bytes as 2*J*S*S 16-bit channels at the branch resolution
-    op.out = to_heatmaps ? -2 : new_tensor(2 * J * S * S, net->tensors[y].ds, "");
+    op.out = to_heatmaps ? -2 : new_tensor(chan_exact(2 * J * S * S), net->tensors[y].ds, "");
     push(op);
     return op.out;
   }
   // Fuse row 0 and the first hop of every down path from branch 0 as one launch (fuse_down.hip; pose_hrnet.py:211-239, :256-263).
   // fp: "stageS.M.fuse_layers"; low[j - 1]: the 1x1 up-path outputs of branches j = 1..nb-1 for row 0.  Returns fuse row 0's
   // output and fills first[i - 1] with row i's first-hop tensor (row 1: its finished term; rows 2, 3: the chain's intermediate).
-  int fuse_down(int x0, const std::string& fp, const std::vector<int>& low, const std::vector<int>& cur, std::vector<int>* first) {
+  int fuse_down(int x0, const std::string& fp, const std::vector<int>& low, const std::vector<Chan>& cur, std::vector<int>* first) {
     if (status != SCPOSE_OK) return -1;
-    const int nb = (int)cur.size(), c0 = cur[0];
+    const int nb = (int)cur.size(), c0 = cur[0].car;
     std::vector<float> w((size_t)nb * c0 * c0 * 9), b((size_t)nb * c0);
     size_t wo = 0, bo = 0;
     for (int i = 1; i < nb; ++i) {
-      const int cout = i == 1 ? cur[1] : c0;   // row 1's single hop ends at its width; longer chains keep branch 0's until their last hop
+      const Chan cout = i == 1 ? cur[1] : cur[0];   // row 1's single hop ends at its width; longer chains keep branch 0's until their last hop
       std::vector<float> wi, bi;
       const std::string cn = fmt2(fp, i);
-      if (!fold(*W, cn + ".0", cn + ".1", cout, c0, 3, false, &wi, &bi)) { status = SCPOSE_E_MISSING; return -1; }
+      if (!fold(*W, cn + ".0", cn + ".1", cout, cur[0], 3, false, &wi, &bi)) { status = SCPOSE_E_MISSING; return -1; }
       std::copy(wi.begin(), wi.end(), w.begin() + wo); wo += wi.size();
       std::copy(bi.begin(), bi.end(), b.begin() + bo); bo += bi.size();
     }
@@ -320,8 +361,8 @@ struct Builder {
     op.nterms = nb - 1;
     for (int k = 0; k < nb - 1; ++k) { op.term[k] = low[k]; op.shift[k] = k + 1; }
     op.nouts = nb - 1;
-    for (int i = 1; i < nb; ++i) { op.outs[i - 1] = new_tensor(i == 1 ? cur[1] : c0, ds + 1, fmt2(fp, i)); first->push_back(op.outs[i - 1]); }
-    op.out = new_tensor(c0, ds, fp.substr(0, fp.size() - 11) + "out0");   // fp = "<module>.fuse_layers"
+    for (int i = 1; i < nb; ++i) { op.outs[i - 1] = new_tensor(i == 1 ? cur[1] : cur[0], ds + 1, fmt2(fp, i)); first->push_back(op.outs[i - 1]); }
+    op.out = new_tensor(cur[0], ds, fp.substr(0, fp.size() - 11) + "out0");   // fp = "<module>.fuse_layers"
     push(op);
     return op.out;
   }
@@ -330,7 +371,7 @@ struct Builder {
     snprintf(buf, sizeof(buf), "%s.%d.0.0", fp.c_str(), i);
     return buf;
   }
-  int fuse(const std::vector<int>& terms, const std::vector<int>& shifts, int C, int ds, const std::string& name) {
+  int fuse(const std::vector<int>& terms, const std::vector<int>& shifts, Chan C, int ds, const std::string& name) {
     if (status != SCPOSE_OK) return -1;
     Op op{};
     op.kind = OP_FUSE; op.in = -1; op.res = -1; op.conv = -1; op.relu = 1;
@@ -359,7 +400,7 @@ int32_t hrnet_build(scpose_hrnet* net, Weights& W) {
     float ms[6] = {d.mean[0], d.mean[1], d.mean[2], d.std[0], d.std[1], d.std[2]};
     SCP_CHECK_HIP(hipMemcpy(net->d_mean_std, ms, sizeof(ms), hipMemcpyHostToDevice));
     std::vector<float> w1, b1, w2, b2;
-    if (!fold(W, "conv1", "bn1", 64, 3, 3, false, &w1, &b1) || !fold(W, "conv2", "bn2", 64, 64, 3, false, &w2, &b2)) return SCPOSE_E_MISSING;
+    if (!fold(W, "conv1", "bn1", chan(64), chan_exact(3), 3, false, &w1, &b1) || !fold(W, "conv2", "bn2", chan(64), chan(64), 3, false, &w2, &b2)) return SCPOSE_E_MISSING;
     std::vector<uint16_t> pw1, pw2;
     std::vector<float> pb1, pb2;
     stem_fused_pack(w1.data(), b1.data(), w2.data(), b2.data(), d.dtype, &pw1, &pw2, &pb1, &pb2);
@@ -373,7 +414,7 @@ int32_t hrnet_build(scpose_hrnet* net, Weights& W) {
     SCP_CHECK_HIP(hipMemcpy(net->d_stemf_b2, pb2.data(), 64 * 4, hipMemcpyHostToDevice));
     Op stem{};
     stem.kind = OP_STEM2; stem.in = -2; stem.res = -1; stem.conv = -1; stem.relu = 1;
-    stem.out = B.new_tensor(64, 2, "stem2");
+    stem.out = B.new_tensor(chan(64), 2, "stem2");
     B.push(stem);
     x = stem.out;
   }
@@ -383,12 +424,12 @@ int32_t hrnet_build(scpose_hrnet* net, Weights& W) {
 
   net->taps.emplace_back("layer1", x);   // the same tensor as "layer1.3" (kept: the oracle's forward(taps=) names it so)
   std::vector<int> ylist{x};
-  std::vector<int> pre{256};
+  std::vector<Chan> pre{chan(256)};
   for (int si = 0; si < 3; ++si) {
     const int nb = d.num_branches[si];
     const bool bneck_stage = d.block[si] == 1;
-    std::vector<int> cur(d.num_channels[si], d.num_channels[si] + nb);
-    if (bneck_stage) for (int& c : cur) c *= 4;          // num_channels * block.expansion (pose_hrnet.py:393-400)
+    std::vector<Chan> cur;                               // num_channels * block.expansion (pose_hrnet.py:393-400)
+    for (int b = 0; b < nb; ++b) cur.push_back(chan(d.num_channels[si][b] * (bneck_stage ? 4 : 1)));
     const std::string tname = fmt("transition%d", si + 1);
     std::vector<int> xs;
     B.parallel_begin(3);   // transition convs: independent of each other (lane = branch they create)
@@ -402,7 +443,7 @@ int32_t hrnet_build(scpose_hrnet* net, Weights& W) {
       } else {
         int t = ylist.back();
         for (int j = 0; j < i + 1 - (int)pre.size(); ++j) {
-          const int cout = (j == i - (int)pre.size()) ? cur[i] : pre.back();
+          const Chan cout = (j == i - (int)pre.size()) ? cur[i] : pre.back();
           t = B.conv(t, fmt("%s.%d.%d.0", tname.c_str(), i, j), fmt("%s.%d.%d.1", tname.c_str(), i, j), cout, 3, 2, true);
         }
         xs.push_back(t);
@@ -425,7 +466,7 @@ int32_t hrnet_build(scpose_hrnet* net, Weights& W) {
       B.parallel_end();
       std::vector<int> outs;
       static const char* fd_env = dev_env("SCPOSE_FUSE_DOWN");
-      if (multi && !bneck_stage && fuse_down_supported(nb, cur[0], cur[1]) && !(fd_env && atoi(fd_env) == 0)) {
+      if (multi && !bneck_stage && fuse_down_supported(nb, cur[0].car, cur[1].car) && !(fd_env && atoi(fd_env) == 0)) {
         // Branch 0 is read ONCE (fuse_down.hip): its fuse row and the first hop of every down path that starts from it are one
         // launch.  Two epochs instead of one: (A) lane 0: row 0's 1x1 up paths, then that launch; lanes 1..: everything of rows 1..
         // that does not depend on it -- their up paths and the down chains from branches 1..; (B) the remaining hops of the
@@ -505,14 +546,14 @@ int32_t hrnet_build(scpose_hrnet* net, Weights& W) {
     pre = cur;
   }
   if (B.status == SCPOSE_OK && d.head == SCPOSE_HEAD_FINAL_LAYER) {
-    B.conv(ylist[0], "final_layer", "", d.num_joints, d.final_conv_kernel, 1, false, -1, true, true);
+    B.conv(ylist[0], "final_layer", "", chan_exact(d.num_joints), d.final_conv_kernel, 1, false, -1, true, true);
     const int nops = (int)net->ops.size();
     if (B.status == SCPOSE_OK && d.final_conv_kernel == 1 && nops >= 2 && net->ops[nops - 2].kind == OP_FUSE &&
         net->ops[nops - 2].out == ylist[0] && net->ops[nops - 1].in == ylist[0] &&
         head_fused_supported(net->ops[nops - 2].nterms, net->tensors[ylist[0]].C, d.num_joints, 1, 32, 32)) {
       const int C = net->tensors[ylist[0]].C;
-      const float* fw = W.get("final_layer.weight", (int64_t)d.num_joints * C);
-      const float* fb = W.get("final_layer.bias", d.num_joints);
+      const float* fw = W.get("final_layer.weight", chan_exact(d.num_joints), net->tensors[ylist[0]].chan(), 1);
+      const float* fb = W.get("final_layer.bias", chan_exact(d.num_joints));
       if (fw && fb) {
         std::vector<uint16_t> wf(2 * 4 * 16 * 8);
         float bias[16];
@@ -790,7 +831,11 @@ int32_t hrnet_forward(scpose_hrnet* net, const void* in, int in_fmt, int n, int 
 // per-op algorithmic work (per frame) and a signature identifying the kernel variant
 // `unfused`: count a fused BasicBlock as SURVEY.md 8(d) counts the unfused pair (5 tensors); otherwise the bytes are the
 // ones the launch itself has to move (block input once + output once), which is what a roofline of that launch needs.
-static void op_work(const scpose_hrnet* net, const Op& op, int h, int w, double* f, double* by, int32_t sig[4], bool unfused = false) {
+// `real`: the work of the network as the model describes it (TensorDesc::Cr) instead of the work the launches do at the carried
+// widths (TensorDesc::C); the two differ only for widths that are no multiple of 16.  sig[] always names the launch (carried).
+static void op_work(const scpose_hrnet* net, const Op& op, int h, int w, double* f, double* by, int32_t sig[4], bool unfused = false,
+                    bool real = false) {
+  auto ch = [&](int t) -> double { return real ? net->tensors[t].Cr : net->tensors[t].C; };
   *f = 0; *by = 0;
   sig[0] = op.kind; sig[1] = sig[2] = sig[3] = 0;
   if (!unfused && net->headf.active && &op == &net->ops[net->headf.fuse_op]) {
@@ -802,9 +847,9 @@ static void op_work(const scpose_hrnet* net, const Op& op, int h, int w, double*
     const Op& fo = net->ops[net->headf.fuse_op];
     const TensorDesc& to = net->tensors[fo.out];
     const double ho = h >> to.ds, wo = w >> to.ds, J = net->desc.num_joints;
-    *f = 2.0 * to.C * J * ho * wo;
+    *f = 2.0 * ch(fo.out) * J * ho * wo;
     *by = J * ho * wo * 4;
-    for (int k = 0; k < fo.nterms; ++k) *by += to.C * (ho / (1 << fo.shift[k])) * (wo / (1 << fo.shift[k])) * 2;
+    for (int k = 0; k < fo.nterms; ++k) *by += ch(fo.out) * (ho / (1 << fo.shift[k])) * (wo / (1 << fo.shift[k])) * 2;
     sig[0] = 7; sig[1] = fo.nterms; sig[2] = to.C; sig[3] = (int)J;
   } else if (op.kind == OP_STEM2) {
     // both stem convolutions; bytes: the launch reads the image and writes the H/4 x W/4 result (unfused accounting:
@@ -817,8 +862,9 @@ static void op_work(const scpose_hrnet* net, const Op& op, int h, int w, double*
     const TensorDesc& ti = net->tensors[op.in];
     const double hi = h >> ti.ds, wi = w >> ti.ds;
     const double ho = pc.stride == 2 ? hi / 2 : hi, wo = pc.stride == 2 ? wi / 2 : wi;
-    *f = 2.0 * pc.cin * pc.cout * pc.ks * pc.ks * ho * wo;
-    *by = pc.cin * hi * wi * 2 + pc.cout * ho * wo * (op.out_f32 ? 4 : 2) + (op.res >= 0 ? pc.cout * ho * wo * 2 : 0);
+    const double cin = ch(op.in), cout = op.out >= 0 ? ch(op.out) : pc.cout;   // (the heat-maps' NUM_JOINTS is never padded)
+    *f = 2.0 * cin * cout * pc.ks * pc.ks * ho * wo;
+    *by = cin * hi * wi * 2 + cout * ho * wo * (op.out_f32 ? 4 : 2) + (op.res >= 0 ? cout * ho * wo * 2 : 0);
     sig[1] = pc.ks * 10 + pc.stride; sig[2] = pc.cin; sig[3] = pc.cout;
   } else if (op.kind == OP_BLOCK) {
     // flops of the two convolutions; bytes: the fused launch reads x once and writes the block output once (the
@@ -826,8 +872,8 @@ static void op_work(const scpose_hrnet* net, const Op& op, int h, int w, double*
     const PackedConv& pc = net->convs[op.conv];
     const TensorDesc& ti = net->tensors[op.in];
     const double hi = h >> ti.ds, wi = w >> ti.ds;
-    *f = 2.0 * 2.0 * pc.cin * pc.cout * 9 * hi * wi;
-    *by = (unfused ? 5.0 : 2.0) * pc.cin * hi * wi * 2;
+    *f = 2.0 * 2.0 * ch(op.in) * ch(op.out) * 9 * hi * wi;
+    *by = (unfused ? 5.0 : 2.0) * ch(op.in) * hi * wi * 2;
     sig[1] = 31; sig[2] = pc.cin; sig[3] = pc.cout;
   } else if (op.kind == OP_BNECK) {
     // flops of the three convolutions; bytes: the launch reads x once and writes y once (unfused accounting: conv1 in + out,
@@ -842,32 +888,34 @@ static void op_work(const scpose_hrnet* net, const Op& op, int h, int w, double*
     // fuse row 0 + the first down hops of branch 0: flops of the nb - 1 stride-2 convolutions; bytes: x0 in, y0 out, the
     // low-resolution terms in, the hops' outputs out (unfused accounting: every convolution and the sum read x0 for themselves)
     const TensorDesc& ti = net->tensors[op.in];
-    const double hi = h >> ti.ds, wi = w >> ti.ds, c0 = ti.C;
+    const double hi = h >> ti.ds, wi = w >> ti.ds, c0 = ch(op.in);
     double cout = 0, low = 0;
-    for (int k = 0; k < op.nouts; ++k) cout += net->tensors[op.outs[k]].C;
+    for (int k = 0; k < op.nouts; ++k) cout += ch(op.outs[k]);
     for (int k = 0; k < op.nterms; ++k) low += c0 * (hi / (1 << op.shift[k])) * (wi / (1 << op.shift[k])) * 2;
     *f = 2.0 * c0 * cout * 9 * (hi / 2) * (wi / 2);
     *by = (unfused ? 2.0 + op.nouts : 2.0) * c0 * hi * wi * 2 + low + cout * (hi / 2) * (wi / 2) * 2;
-    sig[1] = 32; sig[2] = (int)c0; sig[3] = (int)cout;
+    sig[1] = 32; sig[2] = ti.C; sig[3] = 0;
+    for (int k = 0; k < op.nouts; ++k) sig[3] += net->tensors[op.outs[k]].C;
   } else if (op.kind == OP_HEAD) {
     const TensorDesc& ti = net->tensors[op.in];
     const double hi = h >> ti.ds, wi = w >> ti.ds, S = net->head_s, J = net->desc.num_joints;
-    *by = ti.C * hi * wi * 2 + J * S * S * hi * wi * 4 + (op.res >= 0 ? J * S * S * hi * wi : 0);   // tap map + f32 out + coarser f32 level
+    *by = ch(op.in) * hi * wi * 2 + J * S * S * hi * wi * 4 + (op.res >= 0 ? J * S * S * hi * wi : 0);   // tap map + f32 out + coarser f32 level
     sig[1] = net->head_k * 10 + net->head_s; sig[2] = ti.C; sig[3] = net->desc.num_joints;
   } else {
     const TensorDesc& to = net->tensors[op.out];
     const double ho = h >> to.ds, wo = w >> to.ds;
-    *by = to.C * ho * wo * 2;
-    for (int k = 0; k < op.nterms; ++k) *by += to.C * (ho / (1 << op.shift[k])) * (wo / (1 << op.shift[k])) * 2;
+    *by = ch(op.out) * ho * wo * 2;
+    for (int k = 0; k < op.nterms; ++k) *by += ch(op.out) * (ho / (1 << op.shift[k])) * (wo / (1 << op.shift[k])) * 2;
     sig[1] = op.nterms; sig[2] = to.C; sig[3] = to.C;
   }
 }
 
-void hrnet_stats(scpose_hrnet* net, int h, int w, int* launches, double* flops, double* bytes) {
+// real: the network as described (scpose_hrnet_stats); else as executed, at the carried widths (scpose_hrnet_executed_stats)
+void hrnet_stats(scpose_hrnet* net, int h, int w, int* launches, double* flops, double* bytes, bool real) {
   double f = 0, by = 0;
   for (const Op& op : net->ops) {
     double of, ob; int32_t sig[4];
-    op_work(net, op, h, w, &of, &ob, sig, true);   // whole-net figure in SURVEY.md 8(d)'s accounting (422 MB for W48 384^2)
+    op_work(net, op, h, w, &of, &ob, sig, true, real);   // whole-net figure in SURVEY.md 8(d)'s accounting (422 MB for W48 384^2)
     if (op.kind == OP_STEM2) ob -= 3.0 * h * w;   // network input is not an inter-layer activation
     f += of; by += ob;
   }
@@ -924,8 +972,9 @@ extern "C" int32_t scpose_hrnet_create(const scpose_hrnet_desc* desc, const char
     SCP_REQUIRE(desc->num_branches[s] == s + 2, "hrnet_create: STAGE%d NUM_BRANCHES=%d (expected %d)", s + 2, desc->num_branches[s], s + 2);
     SCP_REQUIRE(desc->num_modules[s] >= 1, "hrnet_create: STAGE%d NUM_MODULES=%d", s + 2, desc->num_modules[s]);
     for (int b = 0; b < desc->num_branches[s]; ++b) {
-      SCP_REQUIRE(desc->num_channels[s][b] > 0 && desc->num_channels[s][b] % 16 == 0,
-                  "hrnet_create: STAGE%d NUM_CHANNELS[%d]=%d must be a positive multiple of 16", s + 2, b, desc->num_channels[s][b]);
+      // any positive width: one that is no multiple of 16 is carried at the next one, its added planes zero (Weights::get)
+      SCP_REQUIRE(desc->num_channels[s][b] > 0 && desc->num_channels[s][b] <= (1 << 16),
+                  "hrnet_create: STAGE%d NUM_CHANNELS[%d]=%d must be positive", s + 2, b, desc->num_channels[s][b]);
       SCP_REQUIRE(desc->num_blocks[s][b] >= 1, "hrnet_create: STAGE%d NUM_BLOCKS[%d]=%d", s + 2, b, desc->num_blocks[s][b]);
       if (s > 0 && b < desc->num_branches[s - 1]) {   // channels a branch carries: planes * block.expansion
         const int was = desc->num_channels[s - 1][b] * (desc->block[s - 1] == 1 ? 4 : 1), is = desc->num_channels[s][b] * (desc->block[s] == 1 ? 4 : 1);
@@ -984,7 +1033,14 @@ extern "C" int32_t scpose_hrnet_stats(scpose_hrnet_t h, int32_t height, int32_t 
                                       int32_t* launches, double* flops_per_frame,
                                       double* act_bytes_per_frame) {
   SCP_REQUIRE(h, "hrnet_stats: null handle");
-  hrnet_stats(h, height, width, launches, flops_per_frame, act_bytes_per_frame);
+  hrnet_stats(h, height, width, launches, flops_per_frame, act_bytes_per_frame, true);
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_hrnet_executed_stats(scpose_hrnet_t h, int32_t height, int32_t width, double* flops_per_frame,
+                                               double* act_bytes_per_frame) {
+  SCP_REQUIRE(h, "hrnet_executed_stats: null handle");
+  hrnet_stats(h, height, width, nullptr, flops_per_frame, act_bytes_per_frame, false);
   return SCPOSE_OK;
 }
 
@@ -1140,7 +1196,7 @@ extern "C" int32_t scpose_hrnet_forward_tap(scpose_hrnet_t h, const void* in, in
     return SCPOSE_E_INVALID;
   }
   const TensorDesc& td = h->tensors[tid];
-  if (channels) *channels = td.C;
+  if (channels) *channels = td.Cr;   // the model's channel count: the carried planes beyond it (all zero) are not copied out
   if (out_h) *out_h = height >> td.ds;
   if (out_w) *out_w = width >> td.ds;
   if (!out) return SCPOSE_OK;   // shape query
@@ -1149,7 +1205,7 @@ extern "C" int32_t scpose_hrnet_forward_tap(scpose_hrnet_t h, const void* in, in
   const int32_t rc = hrnet_forward(h, in, in_fmt, n, height, width, nullptr, workspace, workspace_bytes, st, false, tid);
   if (rc != SCPOSE_OK) return rc;
   return blocked_to_nchw_launch(static_cast<const char*>(workspace) + h->plan[0].off[tid], n, td.C, height >> td.ds, width >> td.ds,
-                                h->desc.dtype, out, st);
+                                h->desc.dtype, out, st, td.Cr);
 }
 
 extern "C" int32_t scpose_hrnet_forward_profiled(scpose_hrnet_t h, const void* in, int32_t in_fmt,

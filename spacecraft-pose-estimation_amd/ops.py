@@ -1276,6 +1276,13 @@ class HrnetEngine:
         nat.check(nat.lib().scpose_hrnet_stats(self._h, h, w, ctypes.byref(l), ctypes.byref(f), ctypes.byref(by)), "hrnet_stats")
         return {"launches": l.value, "flops_per_frame": f.value, "act_bytes_per_frame": by.value}
 
+    def executed_stats(self, h, w):
+        """stats()'s two work figures for what the launches do: a NUM_CHANNELS entry that is no multiple of 16 is carried at
+        the next one (zero planes), so W18 / W30 / W40 / W44 execute more than stats() -- the network as described -- counts."""
+        f = c_double(); by = c_double()
+        nat.check(nat.lib().scpose_hrnet_executed_stats(self._h, h, w, ctypes.byref(f), ctypes.byref(by)), "hrnet_executed_stats")
+        return {"flops_per_frame": f.value, "act_bytes_per_frame": by.value}
+
     def forward(self, x, out=None, profile=False):
         """x: float32 (N,3,H,W) normalised, or uint8 (N,H,W,3) raw RGB.  Returns f32 (N,J,H/4,W/4).
         profile=True records a HIP event around every launch (read with profile_read())."""

@@ -1,0 +1,397 @@
+"""HRNet widths that are no multiple of 16 (W18 18/36/72/144, W30, W40, W44) on the HIP engine.
+
+The engine carries a branch of real width c at ceil(c / 16) * 16 channels whose added planes are exactly zero (zero weights, zero
+folded bias: csrc/hrnet.cpp, Weights::get).  So a network of width c must compute, bit for bit, what the network of the rounded-up
+widths computes from the zero-extended checkpoint (test 1); it must sit within the project's whole-net bounds of the oracle and of
+what the reference modules returned (test 2); and nothing about the padding may show at the Python surface (tests 3 - 6).
+64 x 64 frames with modules (1, 1, 1) are the smallest shapes that still cross every padded layer kind: BasicBlock (fused at carried
+widths 32 / 48, two convolutions elsewhere), transitions, the stride-2 fuse chains and fuse_down (c = 44: 48 / 96), the 1x1 up paths,
+the fuse sums, final_layer and the fused tail, the Bottleneck stage block, the hrnet_cms head folds.
+"""
+import os
+import subprocess
+import sys
+import types
+from collections import OrderedDict
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import hrnet_ref as R
+from test_hrnet_widths_host import GOLDEN, golden_cases, golden_inputs
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# the project's whole-net bounds, copied from tests/test_gpu_hrnet.py (E_LOGIC_* / E_PREC_*, ~1.3x the largest value measured over its
+# configurations): vs the oracle run in the engine's storage model, and vs fp32 reference arithmetic
+E_LOGIC_BF16, E_LOGIC_F16 = 1.3e-2, 1.8e-3
+E_PREC_BF16, E_PREC_F16 = 1.2e-2, 1.6e-3
+BOUNDS = {"bf16": (E_LOGIC_BF16, E_PREC_BF16), "f16": (E_LOGIC_F16, E_PREC_F16)}
+
+
+def _rel(a, b):
+    return ((a - b).norm() / b.norm()).item()
+
+
+def _up16(c):
+    return (c + 15) // 16 * 16
+
+
+def padded_cfg(cfg, up=_up16):
+    """cfg with every NUM_CHANNELS entry rounded up to a multiple of 16 (18/36/72/144 -> 32/48/80/144)."""
+    out = {"MODEL": dict(cfg["MODEL"])}
+    out["MODEL"]["EXTRA"] = dict(cfg["MODEL"]["EXTRA"])
+    for s in ("STAGE2", "STAGE3", "STAGE4"):
+        st = dict(cfg["MODEL"]["EXTRA"][s])
+        st["NUM_CHANNELS"] = [up(c) for c in st["NUM_CHANNELS"]]
+        out["MODEL"]["EXTRA"][s] = st
+    return out
+
+
+def padded_state_dict(pcfg, sd):
+    """sd zero-extended to the shapes of pcfg (a padded_cfg): convolution weights (both axes) and biases with zeros, the added
+    BatchNorm channels with the identity (weight 1, bias 0, mean 0, var 1)."""
+    out = OrderedDict()
+    for k, shape in R.state_dict_spec(pcfg).items():
+        v = sd[k]
+        leaf = k.rsplit(".", 1)[1]
+        if leaf == "num_batches_tracked":
+            out[k] = v.clone()
+            continue
+        is_bn = len(shape) == 1 and k.rsplit(".", 1)[0] + ".running_var" in sd
+        t = torch.ones(shape) if is_bn and leaf in ("weight", "running_var") else torch.zeros(shape)
+        t[tuple(slice(0, d) for d in v.shape)] = v
+        out[k] = t
+    return out
+
+
+# ------------------------------------------------------------------------------------------ 1. exact zero-extension
+def _zero_extension(gpu_ops, cfg, dt, n, seed, pcfg=None):
+    sd = R.make_state_dict(cfg, seed=seed)
+    x = torch.randn(n, 3, 64, 64, generator=torch.Generator().manual_seed(seed + 1)).cuda()
+    eng = gpu_ops.HrnetEngine(cfg, sd, dtype=dt)
+    pcfg = pcfg or padded_cfg(cfg)
+    pad = gpu_ops.HrnetEngine(pcfg, padded_state_dict(pcfg, sd), dtype=dt)
+    ya, yb = eng(x).clone(), pad(x).clone()
+    assert ya.shape == (n, 11, 16, 16) and torch.isfinite(ya).all()
+    assert torch.equal(ya, yb), "heat-maps differ from the zero-extended network's: max |d| %.3e" % (ya - yb).abs().max().item()
+    names = eng.tap_names()
+    assert names == pad.tap_names()
+    widened = 0
+    for tap in names:
+        a, b = eng.forward_tap(x, tap), pad.forward_tap(x, tap)
+        c = a.shape[1]
+        assert b.shape[1] >= c and a.shape[0] == n and a.shape[2:] == b.shape[2:], tap
+        assert torch.equal(a, b[:, :c]), "%s differs from the zero-extended network's" % tap
+        extra = b[:, c:]
+        # exactly +0.0: no bit set, not even the sign
+        assert extra.numel() == 0 or not extra.contiguous().view(torch.int32).any().item(), "%s: an added plane is not +0.0" % tap
+        widened += int(b.shape[1] > c)
+    assert widened >= 10
+    eng.close(); pad.close()
+    return names
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+@pytest.mark.parametrize("c", [18, 40])
+def test_width_c_equals_the_zero_extended_network_bit_for_bit(gpu_ops, c, dt):
+    cfg = R.tiny_cfg(c=c)
+    names = _zero_extension(gpu_ops, cfg, dt, 2, 50 + c)
+    eng = gpu_ops.HrnetEngine(cfg, R.make_state_dict(cfg, seed=1), dtype=dt)
+    x = torch.zeros(1, 3, 64, 64).cuda()
+    # taps come back at the model's channel counts, under the names every width has
+    assert eng.forward_tap(x, "stage2.0.out0").shape == (1, c, 16, 16)
+    assert eng.forward_tap(x, "stage4.0.branches.3.0").shape == (1, 8 * c, 2, 2)
+    ref = gpu_ops.HrnetEngine(R.tiny_cfg(c=16), R.make_state_dict(R.tiny_cfg(c=16), seed=1), dtype=dt)
+    # (a BasicBlock at a carried width of 32 / 48 is one launch and so offers no "<block>.conv1" tap, as for the real widths 32 / 48)
+    assert set(n for n in names if not n.endswith(".conv1")) == set(n for n in ref.tap_names() if not n.endswith(".conv1"))
+    eng.close(); ref.close()
+
+
+def test_bottleneck_stage_of_width_18_equals_the_zero_extended_network(gpu_ops):
+    """BLOCK: BOTTLENECK pads planes and 4 * planes separately: 18 -> 32 inside the block, 72 -> 80 between blocks.  No configuration
+    of multiples of 16 has those layer shapes (planes 32 carry 128 between blocks), so the zero-extended network that must agree
+    BIT FOR BIT is the one of planes 20 / 36 / 72 / 144 -- 4 * planes = 80 / 144 / 288 / 576, the carried widths; its own planes
+    are carried at 32 / 48 / 80 / 144 as well -- built from the checkpoint zero-extended to its shapes.
+    Against the network of planes 32 / 48 / 80 / 144 (128 / 192 / 320 / 576 between blocks) the real terms are the same but the
+    convolutions that read 80 or 128 channels split their sums differently (measured: max |d| 2.9e-3 on heat-maps of std 0.37, bf16),
+    which is what the project's whole-net bound for "same logic, other summation order" covers: rel-L2 <= E_LOGIC_BF16."""
+    cfg = R.bneck_cfg(c=18, blocks=1)
+    _zero_extension(gpu_ops, cfg, "bf16", 1, 90, padded_cfg(cfg, up=lambda p: _up16(4 * p) // 4))
+    sd = R.make_state_dict(cfg, seed=90)
+    x = torch.randn(1, 3, 64, 64, generator=torch.Generator().manual_seed(91)).cuda()
+    eng = gpu_ops.HrnetEngine(cfg, sd)
+    pad = gpu_ops.HrnetEngine(padded_cfg(cfg), padded_state_dict(padded_cfg(cfg), sd))
+    ya, yb = eng(x).cpu(), pad(x).cpu()
+    e = _rel(ya, yb)
+    print("bneck18 vs the network of planes 32/48/80/144: rel-L2 %.3e, max |d| %.3e" % (e, (ya - yb).abs().max().item()))
+    assert e <= E_LOGIC_BF16
+    for tap in ("stage2.0.branches.0.0", "stage4.0.branches.3.0"):
+        a, b = eng.forward_tap(x, tap), pad.forward_tap(x, tap)
+        assert (a.shape[1], b.shape[1]) in ((72, 128), (576, 576))
+        assert not b[:, a.shape[1]:].contiguous().view(torch.int32).any().item(), "%s: an added plane is not +0.0" % tap
+    eng.close(); pad.close()
+
+
+# ------------------------------------------------------------------------------------------ 2. parity
+PARITY = {"c18_64": (18, (64, 64)), "c40_64": (40, (64, 64)), "c44_64": (44, (64, 64)), "c18_96x64": (18, (96, 64))}
+
+
+@pytest.fixture(scope="module")
+def parity_refs():
+    """name -> (cfg, sd, x, {None / dtype: oracle heat-maps}), computed once."""
+    out = {}
+    for name, (c, (h, w)) in PARITY.items():
+        cfg = R.tiny_cfg(c=c)
+        sd = R.make_state_dict(cfg, seed=3)
+        x = torch.randn(2, 3, h, w, generator=torch.Generator().manual_seed(4))
+        with torch.no_grad():
+            refs = {dt: R.forward(sd, cfg, x, emulate=dt) for dt in (None, "bf16", "f16")}
+        out[name] = (cfg, sd, x, refs)
+    return out
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+@pytest.mark.parametrize("name", list(PARITY))
+def test_forward_matches_oracle(gpu_ops, parity_refs, name, dt):
+    cfg, sd, x, refs = parity_refs[name]
+    eng = gpu_ops.HrnetEngine(cfg, sd, dtype=dt)
+    got = eng(x.cuda()).cpu()
+    eng.close()
+    e_logic, e_prec = _rel(got, refs[dt]), _rel(got, refs[None])
+    print("%s %s: rel-L2 vs storage-model oracle %.3e, vs fp32 reference arithmetic %.3e" % (name, dt, e_logic, e_prec))
+    assert got.shape == refs[None].shape and torch.isfinite(got).all()
+    assert e_logic <= BOUNDS[dt][0]
+    assert e_prec <= BOUNDS[dt][1]
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+@pytest.mark.parametrize("name", list(golden_cases()))
+def test_forward_matches_the_reference_modules_heatmaps(gpu_ops, name, dt):
+    """Against what the reference modules themselves returned at these widths (tests/golden/hrnet_widths_reference_outputs.npz)."""
+    gold = np.load(GOLDEN)
+    _, cfg = golden_cases()[name]
+    sd, x, ref = golden_inputs(gold, name, cfg)
+    eng = gpu_ops.HrnetEngine(cfg, sd, dtype=dt)
+    got = eng(x.cuda()).cpu()
+    eng.close()
+    e = _rel(got, ref)
+    print("%s %s vs reference golden: rel-L2 %.3e" % (name, dt, e))
+    assert got.shape == ref.shape and e <= BOUNDS[dt][1]
+
+
+# ------------------------------------------------------------------------------------------ 3. invariance
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+def test_w18_frames_are_batch_invariant_and_captured_and_fused_paths_agree(gpu_ops, dt):
+    cfg = R.tiny_cfg(c=18, modules=(1, 4, 3))
+    sd = R.make_state_dict(cfg, seed=6)
+    x = torch.randn(5, 3, 64, 64, generator=torch.Generator().manual_seed(7)).cuda()
+    eng = gpu_ops.HrnetEngine(cfg, sd, dtype=dt)
+    got = eng(x).clone()
+    assert torch.equal(eng(x[0:1].contiguous()), got[0:1]), "frame 0 alone differs from frame 0 of the batch"
+    for concurrent in (True, False):
+        g = eng.capture(x.clone(), concurrent=concurrent)
+        assert torch.equal(g.replay(), got), "captured forward (concurrent=%s) differs from the eager one" % concurrent
+        g.close()
+    center = torch.tensor([[80.0 + 3 * i, 60.0 - i] for i in range(5)]).cuda()
+    scale = torch.tensor([[0.45 + 0.02 * i, 0.35] for i in range(5)]).cuda()
+    for post in (True, False):
+        kp = eng.forward_decode(x, center, scale, post)
+        assert kp.shape == (5, 11, 3)
+        assert torch.equal(kp, gpu_ops.decode(got, center, scale, post)), "forward_decode differs from decode(forward)"
+    gd = eng.capture_decode(x.clone(), center.clone(), scale.clone(), True)
+    assert torch.equal(gd.replay(), gpu_ops.decode(got, center, scale, True))
+    gd.close()
+    u8 = torch.randint(0, 256, (3, 64, 64, 3), generator=torch.Generator().manual_seed(8), dtype=torch.uint8).cuda()
+    assert torch.equal(eng(u8)[1:2], eng(u8[1:2].contiguous()))
+    eng.close()
+
+
+# ------------------------------------------------------------------------------------------ 4. stats
+def _with_blocks(cfg, stage2_blocks):
+    out = {"MODEL": dict(cfg["MODEL"])}
+    out["MODEL"]["EXTRA"] = dict(cfg["MODEL"]["EXTRA"])
+    out["MODEL"]["EXTRA"]["STAGE2"] = dict(cfg["MODEL"]["EXTRA"]["STAGE2"], NUM_BLOCKS=stage2_blocks)
+    return out
+
+
+def test_stats_count_the_real_widths_and_executed_stats_the_carried_ones(gpu_ops):
+    c32 = R.tiny_cfg(c=32)
+    eng = gpu_ops.HrnetEngine(c32, R.make_state_dict(c32, seed=1))
+    st, ex = eng.stats(64, 64), eng.executed_stats(64, 64)
+    assert ex["flops_per_frame"] == st["flops_per_frame"] and ex["act_bytes_per_frame"] == st["act_bytes_per_frame"]
+    eng.close()
+    # One more BasicBlock on branch 0 of stage 2 (16 x 16 maps for a 64 x 64 frame) adds two 3x3 layers: 2 * c * c * 9 * 16 * 16 FLOPs
+    # each -- c = 18 as described, 32 as executed.
+    figs = []
+    for blocks in ([1, 1], [2, 1]):
+        cfg = _with_blocks(R.tiny_cfg(c=18), blocks)
+        eng = gpu_ops.HrnetEngine(cfg, R.make_state_dict(cfg, seed=1))
+        figs.append((eng.stats(64, 64), eng.executed_stats(64, 64)))
+        eng.close()
+    (st1, ex1), (st2, ex2) = figs
+    layer = lambda c: 2.0 * c * c * 9 * 16 * 16
+    assert st2["flops_per_frame"] - st1["flops_per_frame"] == 2 * layer(18)
+    assert ex2["flops_per_frame"] - ex1["flops_per_frame"] == 2 * layer(32)
+    assert ex1["flops_per_frame"] > st1["flops_per_frame"] and ex1["act_bytes_per_frame"] > st1["act_bytes_per_frame"]
+    # the executed figure of width 18 is the described figure of the rounded-up widths
+    pc = padded_cfg(_with_blocks(R.tiny_cfg(c=18), [1, 1]))
+    eng = gpu_ops.HrnetEngine(pc, R.make_state_dict(pc, seed=1))
+    assert eng.stats(64, 64)["flops_per_frame"] == ex1["flops_per_frame"]
+    assert eng.stats(64, 64)["launches"] == st1["launches"]
+    eng.close()
+
+
+# ------------------------------------------------------------------------------------------ 5. errors
+def _with_width(cfg, c0):
+    out = padded_cfg(cfg)
+    for s in ("STAGE2", "STAGE3", "STAGE4"):
+        out["MODEL"]["EXTRA"][s]["NUM_CHANNELS"] = [c0] + list(cfg["MODEL"]["EXTRA"][s]["NUM_CHANNELS"][1:])
+    return out
+
+
+def test_checkpoints_are_validated_against_the_real_shapes(gpu_ops):
+    cfg = R.tiny_cfg(c=18)
+    sd = R.make_state_dict(cfg, seed=1)
+    for bad in (0, -16):
+        with pytest.raises(gpu_ops.nat.NativeError, match=r"NUM_CHANNELS\[0\]=%d" % bad):
+            gpu_ops.HrnetEngine(_with_width(cfg, bad), sd, allow_missing=True)
+    wrong = dict(sd)
+    wrong["stage2.0.branches.0.0.conv1.weight"] = torch.zeros(32, 32, 3, 3)       # the carried shape is not the model's
+    with pytest.raises(gpu_ops.nat.NativeError, match=r"stage2\.0\.branches\.0\.0\.conv1\.weight \(wrong size.*18 x 18 x 9"):
+        gpu_ops.HrnetEngine(cfg, wrong)
+    wrong_bn = dict(sd)
+    wrong_bn["stage2.0.branches.0.0.bn1.running_var"] = torch.ones(32)
+    with pytest.raises(gpu_ops.nat.NativeError, match=r"bn1\.running_var \(wrong size.*18 x 1 x 1"):
+        gpu_ops.HrnetEngine(cfg, wrong_bn)
+    missing = dict(sd)
+    del missing["stage3.0.fuse_layers.2.0.1.0.weight"]
+    with pytest.raises(gpu_ops.nat.NativeError, match="stage3.0.fuse_layers.2.0.1.0.weight"):
+        gpu_ops.HrnetEngine(cfg, missing)
+    eng = gpu_ops.HrnetEngine(cfg, missing, allow_missing=True)                   # strict=False behaviour, as for every width
+    assert torch.isfinite(eng(torch.zeros(1, 3, 64, 64).cuda())).all()
+    eng.close()
+    # STAGE3 must keep STAGE2's branch widths: compared at the real counts (18 vs 20 are both carried at 32)
+    changed = padded_cfg(cfg)
+    changed["MODEL"]["EXTRA"]["STAGE2"]["NUM_CHANNELS"] = [20, 36]
+    changed["MODEL"]["EXTRA"]["STAGE3"]["NUM_CHANNELS"] = [18, 36, 72]
+    changed["MODEL"]["EXTRA"]["STAGE4"]["NUM_CHANNELS"] = [18, 36, 72, 144]
+    with pytest.raises(gpu_ops.nat.NativeError, match="changes channel count"):
+        gpu_ops.HrnetEngine(changed, sd, allow_missing=True)
+
+
+# ------------------------------------------------------------------------------------------ 6. module + CLI
+def _scene(tmp_path, n=4, j=11, size=(160, 120)):
+    """A scene directory as tests/test_gpu_e2e.py builds it: n random PNG frames and a COCO-style annotation file."""
+    import json
+    from PIL import Image
+    rng = np.random.default_rng(3)
+    (tmp_path / "frames").mkdir()
+    images, anns = [], []
+    for i in range(n):
+        name = "frame_%03d.png" % i
+        Image.fromarray(rng.integers(0, 255, (size[1], size[0], 3), dtype=np.uint8)).save(tmp_path / "frames" / name)
+        images.append({"id": i + 1, "file_name": name, "width": size[0], "height": size[1]})
+        anns.append({"image_id": i + 1, "bbox": [10 + 3 * i, 8, 90, 70], "keypoints": [2.0] * (3 * j), "id": i, "category_id": 1})
+    (tmp_path / "data").mkdir()
+    (tmp_path / "data" / "real_test.json").write_text(json.dumps({"images": images, "annotations": anns}))
+
+
+def test_cli_runs_the_w18_yaml_and_equals_the_in_process_forward_decode(gpu_ops, tmp_path):
+    """tools/test.py --cfg experiments/bench/w18_256.yaml (the reference's data flow for the crops: --host_crop) on a 4-frame scene:
+    pred.mat's rows are, bit for bit, the module's forward_decode on the same crops -- and the module has the real shapes."""
+    from importlib import import_module
+    from scipy.io import loadmat
+    pkg = gpu_ops.__name__.rsplit(".", 1)[0]
+    config, T, dataset = (import_module(pkg + m) for m in (".config", ".utils.transforms", ".dataset"))
+    _scene(tmp_path)
+    yaml_path = os.path.join(ROOT, "landmark_regression", "experiments", "bench", "w18_256.yaml")
+    cfg_node = R.w32_cfg(11, 64)
+    for s, nb in (("STAGE2", 2), ("STAGE3", 3), ("STAGE4", 4)):
+        cfg_node["MODEL"]["EXTRA"][s]["NUM_CHANNELS"] = [18 * 2 ** i for i in range(nb)]
+    sd = R.make_state_dict(cfg_node, seed=31)
+    torch.save(sd, tmp_path / "model.pth")
+    out = tmp_path / "out"
+    cmd = [sys.executable, "tools/test.py", "--host_crop", "--cfg", yaml_path, "OUTPUT_DIR", str(out), "LOG_DIR", str(tmp_path / "log"),
+           "DATA_DIR", str(tmp_path / "frames"), "DATASET.ROOT", str(tmp_path / "data"), "DATASET.TEST_SET", "test",
+           "MODEL.NUM_JOINTS", "11", "MODEL.IMAGE_SIZE", "[64, 64]", "MODEL.HEATMAP_SIZE", "[16, 16]",
+           "TEST.MODEL_FILE", str(tmp_path / "model.pth"), "TEST.BATCH_SIZE_PER_GPU", "4"]
+    r = subprocess.run(cmd, cwd=os.path.join(ROOT, "landmark_regression"), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    preds = loadmat(out / "EventsDataset" / "pose_hrnet" / "w18_256" / "pred.mat")["preds"]
+    assert preds.shape == (4, 11, 3) and preds.dtype == np.float32
+
+    c = config._defaults()
+    config.update_config(c, types.SimpleNamespace(cfg=yaml_path, opts=cmd[cmd.index(yaml_path) + 1:], modelDir="", logDir="", dataDir=""))
+    ds = dataset.EventsDataset(c, c.DATASET.ROOT, c.DATA_DIR, "test", False,
+                               T.Compose([T.ToTensor(), T.Normalize([0.485, 0.456, 0.406], [0.229, 0.224, 0.225])]))
+    xs = torch.stack([ds[i][0] for i in range(4)])
+    cs = torch.from_numpy(np.stack([ds.db[i]["center"] for i in range(4)])).float()
+    ss = torch.from_numpy(np.stack([ds.db[i]["scale"] for i in range(4)])).float()
+    net = import_module(pkg + ".models.pose_hrnet").get_pose_net(c, is_train=False).eval()
+    assert {k: tuple(v.shape) for k, v in net.state_dict().items()} == {k: tuple(s) for k, s in R.state_dict_spec(cfg_node).items()}
+    net.load_state_dict(sd, strict=True)
+    with torch.no_grad():
+        kp = net.forward_decode(xs.cuda(), cs.cuda(), ss.cuda(), True)
+        hm = net(xs.cuda())
+    assert hm.shape == (4, 11, 16, 16)
+    assert np.array_equal(kp.cpu().numpy().view(np.int32), preds.view(np.int32)), "pred.mat differs from the in-process forward_decode"
+    with torch.no_grad():
+        ref = R.forward(sd, cfg_node, xs)
+    assert _rel(hm.cpu(), ref) <= E_PREC_BF16
+
+
+@pytest.mark.parametrize("mode", ["flip_test", "ensemble"])
+def test_validate_flip_test_and_validate_cv_run_width_18(gpu_ops, mode):
+    """core.function.validate with TEST.FLIP_TEST and validate_cv over two members, on modules of width 18: all_preds equal, bit for
+    bit, the same heat-map arithmetic (function.py:347-366, :530-536) done here on HrnetEngine forwards of the same checkpoints."""
+    from importlib import import_module
+    pkg = gpu_ops.__name__.rsplit(".", 1)[0]
+    fn, models, inference = (import_module(pkg + m) for m in (".core.function", ".models", ".core.inference"))
+    cfg = R.tiny_cfg(c=18)
+    sds = [R.make_state_dict(cfg, seed=s) for s in ((71, 72) if mode == "ensemble" else (71,))]
+    nets = []
+    for sd in sds:
+        m = models.pose_hrnet.get_pose_net(cfg, is_train=False)
+        m.load_state_dict(sd, strict=True)
+        nets.append(m.cuda().eval())
+    n = 6
+    x = torch.randn(n, 3, 64, 64, generator=torch.Generator().manual_seed(73))
+    center = torch.tensor([[80.0 + 3 * i, 60.0 - i] for i in range(n)])
+    scale = torch.tensor([[0.45 + 0.02 * i, 0.35] for i in range(n)])
+    batches = [(x[i:i + 4], torch.zeros(0), torch.zeros(0), {"center": center[i:i + 4], "scale": scale[i:i + 4],
+                                                            "score": torch.ones(len(x[i:i + 4]), dtype=torch.float64),
+                                                            "image": ["frame_%03d.png" % k for k in range(i, min(i + 4, n))]})
+               for i in range(0, n, 4)]
+    N = types.SimpleNamespace
+    config = N(MODEL=N(NUM_JOINTS=11, NAME="pose_hrnet", IMAGE_SIZE=[64, 64], HEATMAP_SIZE=[16, 16]),
+               TEST=N(FLIP_TEST=mode == "flip_test", SHIFT_HEATMAP=True, POST_PROCESS=True), PRINT_FREQ=100)
+    got = {}
+
+    class DS:
+        flip_pairs = [[1, 2], [3, 4], [5, 6]]
+
+        def __len__(self):
+            return n
+
+        def evaluate(self, c, preds, output_dir, pred_file_name, all_boxes, image_path, filenames, imgnums):
+            got.update(preds=preds.copy())
+            return {"Null": 0}, 0
+    if mode == "ensemble":
+        fn.validate_cv(config, batches, DS(), nets, None, "", "", "pred_real", log_metrics=False, engine_batch=0)
+    else:
+        fn.validate(config, batches, DS(), nets[0], None, "", "", pred_file_name="pred_test", log_metrics=False, engine_batch=0)
+    engs = [gpu_ops.HrnetEngine(cfg, sd) for sd in sds]
+    xd = x.cuda()
+    hm = engs[0](xd).clone()
+    if mode == "ensemble":
+        gpu_ops.heatmap_accumulate(hm, engs[1](xd), 2.0)
+    else:
+        hm = gpu_ops.flip_merge(hm, engs[0](xd.flip(3)), DS.flip_pairs, True)
+    ref = inference.get_final_preds_device(config, hm, center.cuda(), scale.cuda()).cpu().numpy()
+    assert got["preds"].shape == (n, 11, 3) and np.isfinite(got["preds"]).all()
+    assert np.array_equal(got["preds"].view(np.int32), ref.view(np.int32))
+    for e in engs:
+        e.close()
