@@ -526,15 +526,11 @@ static int32_t bneck_launch_one(const BneckLaunch& L, hipStream_t stream) {
 int32_t bottleneck_launch(const void* in, const void* w1, const void* w2, const void* w3, const float* bias, int N, int H, int W,
                           int cin, int dtype, void* out, uint32_t* sched, hipStream_t stream) {
   SCP_REQUIRE(sched, "bottleneck: null tile-queue words");
-  // batches whose 256-channel tensor does not fit a buffer descriptor (~900 frames at 96 x 96) run as several launches over
-  // frame ranges (common.h: buf_max_frames)
   const bool proj = cin == 64;
   SCP_REQUIRE(cin == 64 || cin == 256, "bottleneck: Cin = %d (64 or 256)", cin);
   const size_t in_frame = blocked_bytes(1, cin / 8, H, W), out_frame = blocked_bytes(1, 32, H, W);
-  SCP_REQUIRE(fits_buf(out_frame), "bottleneck: one %dx%d frame does not fit a 32-bit buffer descriptor", H, W);
-  const int max_n = buf_max_frames(out_frame);
-  for (int n0 = 0; n0 < N; n0 += max_n) {
-    const int n = N - n0 < max_n ? N - n0 : max_n;
+  // the 256-channel output is the largest tensor (~900 frames at 96 x 96 fit one descriptor)
+  return for_frame_ranges(N, out_frame, [&](int n0, int n) -> int32_t {
     BneckLaunch L{};
     L.in = static_cast<const char*>(in) + (size_t)n0 * in_frame;
     L.out = static_cast<char*>(out) + (size_t)n0 * out_frame;
@@ -547,12 +543,9 @@ int32_t bottleneck_launch(const void* in, const void* w1, const void* w2, const 
     L.sched = sched;
     { static const char* e = dev_env("SCPOSE_BNECK_GLOBALQ"); L.xcd_local = !(e && atoi(e)); }
     { static const char* e = dev_env("SCPOSE_BNECK_DBG"); L.dbg_buf = (kDevBuild && e && atoi(e)) ? conv_dbg_buffer(stream) : nullptr; if (L.dbg_buf) conv_dbg_set_grid(L.grid); }
-    int32_t rc;
-    if (dtype == SCPOSE_DT_BF16) rc = proj ? bneck_launch_one<0, true>(L, stream) : bneck_launch_one<0, false>(L, stream);
-    else rc = proj ? bneck_launch_one<1, true>(L, stream) : bneck_launch_one<1, false>(L, stream);
-    if (rc != SCPOSE_OK) return rc;
-  }
-  return SCPOSE_OK;
+    if (dtype == SCPOSE_DT_BF16) return proj ? bneck_launch_one<0, true>(L, stream) : bneck_launch_one<0, false>(L, stream);
+    return proj ? bneck_launch_one<1, true>(L, stream) : bneck_launch_one<1, false>(L, stream);
+  }, "bottleneck %d %dx%d", cin, H, W);
 }
 
 }  // namespace scpose

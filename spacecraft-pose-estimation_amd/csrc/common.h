@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <stdarg.h>
+#include <stdio.h>
 #include <string>
 #include <vector>
 #include <string.h>
@@ -88,21 +90,45 @@ struct Carve {
 };
 
 // ---- 32-bit buffer descriptors ---------------------------------------------------------------
-// Most kernels address their tensors through raw buffer descriptors (conv_pipe_kernel.h: make_buf): base + 32-bit offset,
-// num_records = the tensor's bytes, which must stay below kBufLimit -- the offset given to padding lanes (BUF_OOB) has to
-// lie past every tensor.  A kernel without a 64-bit path takes a batch whose tensor is larger as several launches over
-// frame ranges (bottleneck, fuse_down, fused BasicBlock): the kernel a frame runs on never depends on the batch.
+// The convolution kernels address their tensors through raw buffer descriptors (conv_pipe_kernel.h: make_buf): base + 32-bit
+// offset, num_records = the tensor's bytes, which must stay below kBufLimit -- the offset given to padding lanes (BUF_OOB) has
+// to lie past every tensor.  There is no second, 64-bit form of that traffic.  One rule covers larger batches: a launch whose
+// largest buffer-addressed tensor would not fit runs as several launches over consecutive frame ranges, every pointer
+// advanced by its frame size (for_frame_ranges: conv_launch, bottleneck, fuse_down, fused BasicBlock).  Inside a range every
+// tensor fits, so the kernel a frame runs on never depends on the batch.
 constexpr size_t kBufLimit = 0xfffffff0ull;
 inline size_t blocked_bytes(int n, int planes, int h, int w) { return (size_t)n * planes * h * w * 16; }   // [N][C/8][H][W][8] x 16 bit
 inline bool fits_buf(size_t bytes) { return bytes < kBufLimit; }
-// num_records for a kernel that also has a 64-bit path: 0 selects that path -- the tensor does not fit, or the development
-// switch SCPOSE_M32_BUF=0 asks for it (util.cpp; the one place that switch is read)
-uint32_t buf_bytes_or_64bit(size_t bytes);
-// frames per launch of a kernel that splits the batch: the largest range whose largest tensor (frame_bytes per frame, itself
-// fits_buf) fits; cap > 0 = a smaller range, with which tests force the split on a small batch (a development switch's value)
+// frames per launch: the largest range whose largest tensor (frame_bytes per frame, itself fits_buf) fits; cap > 0 = a smaller
+// range, with which tests force the split on a small batch
 inline int buf_max_frames(size_t frame_bytes, int cap = 0) {
   const int max_n = (int)(kBufLimit / frame_bytes);
   return cap > 0 && cap < max_n ? cap : max_n;
+}
+// the two development switches of the split, read once (util.cpp): SCPOSE_MAXN caps the range, SCPOSE_DBG bit 32 prints each range
+struct FrameRangeSwitches { int cap; bool print; };
+const FrameRangeSwitches& frame_range_switches();
+// launch(n0, n) for consecutive ranges of the N frames, until one fails.  frame_bytes: bytes per frame of the launch's largest
+// buffer-addressed tensor; name_fmt, ...: printf form of the launch's name, formatted only for the error and the debug line
+template <class Launch>
+__attribute__((format(printf, 4, 5))) int32_t for_frame_ranges(int N, size_t frame_bytes, Launch&& launch, const char* name_fmt, ...) {
+  const FrameRangeSwitches& sw = frame_range_switches();
+  char name[96] = "";
+  if (sw.print || !fits_buf(frame_bytes)) {
+    va_list ap;
+    va_start(ap, name_fmt);
+    vsnprintf(name, sizeof(name), name_fmt, ap);
+    va_end(ap);
+  }
+  SCP_REQUIRE(fits_buf(frame_bytes), "%s: one frame (%zu bytes) does not fit a 32-bit buffer descriptor", name, frame_bytes);
+  const int max_n = buf_max_frames(frame_bytes, sw.cap);
+  for (int n0 = 0; n0 < N; n0 += max_n) {
+    const int n = N - n0 < max_n ? N - n0 : max_n;
+    if (sw.print) fprintf(stderr, "%s N=%d: frames %d..%d\n", name, N, n0, n0 + n);
+    const int32_t rc = launch(n0, n);
+    if (rc != SCPOSE_OK) return rc;
+  }
+  return SCPOSE_OK;
 }
 
 // ---- 3x3 / 1x1 implicit-GEMM convolution ---------------------------------------------------
@@ -129,7 +155,7 @@ struct ConvLaunch {
   int32_t out_nchw_f32;
   int32_t store_stages;  // conv_m32p: stages that store the previous tile, when SCPOSE_NST overrides the kernel's own count; else 0
   // pipelined (persistent) variant
-  const void* zero16;    // >= 16 zero bytes in global memory (source of padding pixels for LDS-DMA)
+  const void* zero16;    // >= 16 zero bytes in global memory: what a masked lane of the 64-bit residual loads reads (conv_pipe, conv_m32; conv_m32p does not read it)
   int32_t items_total;   // (tile, Cout block) work items
   int32_t items_per_wg;
   int32_t grid;          // persistent workgroups
@@ -140,12 +166,12 @@ struct ConvLaunch {
   int32_t nt;            // pixel tiles per wave group processed one after the other on one staged weight chunk
   int32_t wreg_chunks;   // conv_m32p: K-chunks of weights held in producer registers (6 or 1)
   FastDiv fd_npix, fd_tw, fd_hp, fd_halo_w, fd_tiles_img, fd_tiles_x, fd_nmblk;   // conv_m32: divisions by launch constants
-  uint32_t in_bytes, out_bytes;   // sizes of the input / output (= residual) tensors when both are < 4 GiB
-                                  // (buffer-addressed global traffic, conv_pipe_kernel.h: dma16_buf), else 0 (64-bit
-                                  // addressing).  conv_pipe addresses only its input that way and leaves out_bytes 0.
+  uint32_t in_bytes, out_bytes;   // bytes of the input / output (= residual) tensors of this frame range: num_records of their
+                                  // buffer descriptors (conv_pipe_kernel.h: dma16_buf), always set.  conv_pipe and conv_m32 address
+                                  // only their input that way (output and residual through 64-bit pointers); conv_pipe leaves out_bytes 0.
   unsigned long long* dbg_buf;  // development build only (SCP_DBG_BUF): per-workgroup phase cycle sums (dbg & 8), else null
   int32_t dbg;           // development build only (SCP_DBG; the shipped library's kernels read neither field): bits 1 skip MFMA loop, 2 skip epilogue, 4 skip input DMA, 8 phase stamps
-                         // bit 32 is the one bit the shipped library honours: the host prints the m32 tile choice (and block_launch its frame ranges)
+                         // bit 32 is the one bit the shipped library honours: the host prints the m32 tile choice (and for_frame_ranges its ranges)
   int32_t cu_share;      // host only: CUs to size the layer for (0 = the whole chip)
 };
 

@@ -22,16 +22,10 @@ int32_t block_launch(const PackedConv& c1, const PackedConv& c2, const void* in,
   SCP_REQUIRE(block_fusable(c1, c2), "block: the two convolutions are not a fusable BasicBlock");
   SCP_REQUIRE(N > 0 && H > 0 && W > 0, "block: bad shape N=%d H=%d W=%d", N, H, W);
   const size_t frame = blocked_bytes(1, c1.cin / 8, H, W);
-  SCP_REQUIRE(fits_buf(frame), "block: one %dx%d frame does not fit a 32-bit buffer descriptor", H, W);
-  // batches whose tensor does not fit a buffer descriptor run as several launches over frame ranges (common.h: buf_max_frames)
-  static const char* cap = dev_env("SCPOSE_BLOCK_MAXN");   // tests: force the split on a small batch
-  const int max_n = buf_max_frames(frame, cap ? atoi(cap) : 0);
   static const char* dbg_env = dev_env("SCPOSE_DBG");
-  const int dbg = dbg_env ? atoi(dbg_env) : 0;   // bit 32, the host's line, also in the shipped library (common.h: ConvLaunch::dbg)
+  const int dbg = dbg_env ? atoi(dbg_env) : 0;
   const int mrep = c1.cin / 16;
-  for (int n0 = 0; n0 < N; n0 += max_n) {
-    const int n = N - n0 < max_n ? N - n0 : max_n;
-    if (dbg & 32) fprintf(stderr, "block %d %dx%d N=%d: frames %d..%d\n", c1.cin, H, W, N, n0, n0 + n);
+  return for_frame_ranges(N, frame, [&](int n0, int n) -> int32_t {
     BlockLaunch L{};
     L.in = static_cast<const char*>(in) + (size_t)n0 * frame;
     L.out = static_cast<char*>(out) + (size_t)n0 * frame;
@@ -50,12 +44,9 @@ int32_t block_launch(const PackedConv& c1, const PackedConv& c2, const void* in,
     L.tiles_per_wg = (L.tiles_total + grid - 1) / grid;
     L.grid = (L.tiles_total + L.tiles_per_wg - 1) / L.tiles_per_wg;
     if (kDevBuild && (dbg & 8)) { L.dbg_buf = conv_dbg_buffer(stream); conv_dbg_set_grid(L.grid); }
-    int32_t rc;
-    if (c1.dtype == SCPOSE_DT_BF16) rc = mrep == 3 ? block_launch_variant<0, 3>(L, stream) : block_launch_variant<0, 2>(L, stream);
-    else rc = mrep == 3 ? block_launch_variant<1, 3>(L, stream) : block_launch_variant<1, 2>(L, stream);
-    if (rc != SCPOSE_OK) return rc;
-  }
-  return SCPOSE_OK;
+    if (c1.dtype == SCPOSE_DT_BF16) return mrep == 3 ? block_launch_variant<0, 3>(L, stream) : block_launch_variant<0, 2>(L, stream);
+    return mrep == 3 ? block_launch_variant<1, 3>(L, stream) : block_launch_variant<1, 2>(L, stream);
+  }, "block %d %dx%d", c1.cin, H, W);
 }
 
 }  // namespace scpose

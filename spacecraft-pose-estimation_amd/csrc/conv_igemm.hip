@@ -242,10 +242,9 @@ size_t conv_lds_bytes(const PackedConv& pc, int nrep, int th, int tw) {
          (size_t)pc.cp * plane_stride_for(pc.stride, hh, hw);
 }
 
-int32_t conv_launch(const PackedConv& pc, const void* in, int N, int H, int W, const void* res,
-                    int relu, int out_nchw_f32, void* out, hipStream_t stream, int cu_share) {
-  SCP_REQUIRE(N > 0 && H > 0 && W > 0, "conv: bad shape N=%d H=%d W=%d", N, H, W);
-  SCP_REQUIRE(out_nchw_f32 || pc.cout % 8 == 0, "conv: blocked output needs Cout%%8==0 (Cout=%d)", pc.cout);
+// one frame range (conv_launch): every tensor fits a buffer descriptor, so the route depends on the layer and the map size only
+static int32_t conv_launch_range(const PackedConv& pc, const void* in, int N, int H, int W, const void* res,
+                                 int relu, int out_nchw_f32, void* out, hipStream_t stream, int cu_share) {
   ConvLaunch L{};
   L.in = in; L.wpk = pc.d_w; L.bias = pc.d_bias; L.res = res; L.out = out;
   L.N = N; L.H = H; L.W = W;
@@ -254,18 +253,16 @@ int32_t conv_launch(const PackedConv& pc, const void* in, int N, int H, int W, c
   L.cin_planes = pc.cin / 8;
   L.cout = pc.cout;
   L.cu_share = cu_share;
-  if (pc.d_ws2 && !res && !out_nchw_f32 && fits_buf(blocked_bytes(N, L.cin_planes, H, W)) &&
-      fits_buf(blocked_bytes(N, pc.cout / 8, L.Ho, L.Wo)))
+  if (pc.d_ws2 && !res && !out_nchw_f32)
     return conv_s2r_launch(pc, in, N, H, W, relu, out, stream);
   if (pc.variant == 1) {
     SCP_REQUIRE(!out_nchw_f32, "conv m32: float32 NCHW output unsupported");
     L.relu = relu; L.out_nchw_f32 = 0;
     return conv_launch_m32(pc, L, stream);
   }
-  {   // 1x1 layers whose weights fit LDS: barrier-free streaming kernel (needs buffer-addressable tensors)
+  {   // 1x1 layers whose weights fit LDS: barrier-free streaming kernel
     static const char* e1 = dev_env("SCPOSE_K1_STREAM");
-    if (pc.d_w1 && !out_nchw_f32 && fits_buf(blocked_bytes(N, L.cin_planes, H, W)) && fits_buf(blocked_bytes(N, pc.cout / 8, H, W)) &&
-        !(e1 && atoi(e1) == 0))
+    if (pc.d_w1 && !out_nchw_f32 && !(e1 && atoi(e1) == 0))
       return conv1x1_stream_launch(pc, in, N, H, W, res, relu, out, stream);
   }
   int nrep;
@@ -320,10 +317,8 @@ int32_t conv_launch(const PackedConv& pc, const void* in, int N, int H, int W, c
     }
     if (2 * conv_pipe_lds_bytes(pc, L.plane_stride) <= 160 * 1024 && pc.mrep * nrep * 4 <= 128) occ = 2;
   }
-  {   // buffer-addressed input DMA when the input tensor fits a 32-bit descriptor
-    L.in_bytes = buf_bytes_or_64bit(blocked_bytes(N, L.cin_planes, H, W));
-    L.out_bytes = 0;   // conv_pipe writes its output through 64-bit pointers
-  }
+  L.in_bytes = (uint32_t)blocked_bytes(N, L.cin_planes, H, W);   // buffer-addressed input DMA
+  L.out_bytes = 0;   // conv_pipe writes its output through 64-bit pointers
   L.cp = pc.cp; L.nchunks = pc.nchunks; L.ksteps_full = pc.ksteps_full;
   L.n_mblk = pc.n_mblk;
   L.relu = relu; L.out_nchw_f32 = out_nchw_f32;
@@ -331,6 +326,20 @@ int32_t conv_launch(const PackedConv& pc, const void* in, int N, int H, int W, c
               L.halo_h, L.halo_w);
   SCP_REQUIRE((pc.ksteps_full + 1) * 4 <= 64, "conv: k-offset table overflow (%d ksteps)", pc.ksteps_full);
   return conv_launch_pipe(pc, L, nrep, nt, occ, stream);
+}
+
+int32_t conv_launch(const PackedConv& pc, const void* in, int N, int H, int W, const void* res,
+                    int relu, int out_nchw_f32, void* out, hipStream_t stream, int cu_share) {
+  SCP_REQUIRE(N > 0 && H > 0 && W > 0, "conv: bad shape N=%d H=%d W=%d", N, H, W);
+  SCP_REQUIRE(out_nchw_f32 || pc.cout % 8 == 0, "conv: blocked output needs Cout%%8==0 (Cout=%d)", pc.cout);
+  const int Ho = (H - 1) / pc.stride + 1, Wo = (W - 1) / pc.stride + 1;
+  const size_t in_frame = blocked_bytes(1, pc.cin / 8, H, W), blk_frame = blocked_bytes(1, (pc.cout + 7) / 8, Ho, Wo);
+  const size_t out_frame = out_nchw_f32 ? (size_t)pc.cout * Ho * Wo * 4 : blk_frame;
+  return for_frame_ranges(N, in_frame > blk_frame ? in_frame : blk_frame, [&](int n0, int n) -> int32_t {
+    return conv_launch_range(pc, static_cast<const char*>(in) + (size_t)n0 * in_frame, n, H, W,
+                             res ? static_cast<const char*>(res) + (size_t)n0 * blk_frame : nullptr, relu, out_nchw_f32,
+                             static_cast<char*>(out) + (size_t)n0 * out_frame, stream, cu_share);
+  }, "conv %d->%d k%d s%d %dx%d", pc.cin, pc.cout, pc.ks, pc.stride, H, W);
 }
 
 }  // namespace scpose

@@ -255,19 +255,18 @@ int32_t conv_launch_m32(const PackedConv& pc, ConvLaunch& L, hipStream_t stream)
   L.nbuf_x = 2;
   L.wreg_chunks = 1;
   const size_t lds = pcons ? m32p_lds_bytes(pc, ck, L.plane_stride, pxcap) : m32_lds_bytes(pc, L.plane_stride);
-  L.zero16 = conv_zero_page();
-  SCP_REQUIRE(L.zero16, "conv: cannot allocate the zero page");
+  if (!pcons) {   // the single-role kernel's residual loads
+    L.zero16 = conv_zero_page();
+    SCP_REQUIRE(L.zero16, "conv: cannot allocate the zero page");
+  }
   L.tiles_total = L.N * L.tiles_x * L.tiles_y;
   { static const char* e = dev_env("SCPOSE_NST"); const int v = e ? atoi(e) : 0;   // producer/consumer kernel: stages that store the previous tile
     L.store_stages = (pcons && v > 0 && v <= pc.nchunks - 2) ? v : 0; }
   L.items_total = ((L.tiles_total + L.nt - 1) / L.nt) * pc.n_mblk;
   { static const char* e = dev_env("SCPOSE_DBG"); L.dbg = e ? atoi(e) : 0; }
   if (!kDevBuild) L.dbg &= 32;   // shipped library: only the host-side "print the tile choice" bit means anything (common.h: SCP_DBG)
-  {   // producer/consumer kernel: buffer-addressed global traffic when both tensors fit a 32-bit descriptor
-    L.in_bytes = buf_bytes_or_64bit(blocked_bytes(L.N, L.cin_planes, L.H, L.W));
-    L.out_bytes = buf_bytes_or_64bit(blocked_bytes(L.N, (pc.cout + 7) / 8, L.Ho, L.Wo));
-    if (!L.in_bytes || !L.out_bytes) L.in_bytes = L.out_bytes = 0;   // one addressing mode for both
-  }
+  L.in_bytes = (uint32_t)blocked_bytes(L.N, L.cin_planes, L.H, L.W);   // both fit: conv_launch splits the batch
+  L.out_bytes = (uint32_t)blocked_bytes(L.N, (pc.cout + 7) / 8, L.Ho, L.Wo);
   L.dbg_buf = nullptr;
   if (L.dbg & 8) L.dbg_buf = conv_dbg_buffer(stream);
   if (L.dbg & 32)

@@ -156,8 +156,8 @@ __global__ __launch_bounds__(256, OCC) void conv_m32_kernel(const ConvLaunch p) 
     oy0 = ty * p.th; ox0 = (rem - ty * p.tiles_x) * p.tw;
   };
 
-  // global byte offset (plane 0 of its image) of each halo pixel of the item being staged; ~0 = zero page
-  size_t xoff[MAXP];
+  // buffer offset (plane 0 of its image) of each halo pixel of the item being staged; BUF_OOB for padding pixels
+  uint32_t xoff[MAXP];
   auto locate_halo = [&](int it) {
 #pragma unroll
     for (int i = 0; i < MAXP; ++i) {
@@ -165,9 +165,7 @@ __global__ __launch_bounds__(256, OCC) void conv_m32_kernel(const ConvLaunch p) 
       decode_tile(it, hs[i], img, oy0, ox0);
       const int iy = oy0 * STRIDE - (KS / 2) + hy[i], ix = ox0 * STRIDE - (KS / 2) + hx[i];
       const bool ok = img >= 0 && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-      // buffer addressing (p.in_bytes != 0): the slot holds a 32-bit offset, BUF_OOB for padding pixels
-      if (p.in_bytes) xoff[i] = ok ? (size_t)((uint32_t)(img * p.cin_planes * HW + iy * p.W + ix) * 16u) : (size_t)BUF_OOB;
-      else xoff[i] = ok ? ((size_t)img * p.cin_planes * HW + (size_t)(iy * p.W + ix)) * 16 : ~(size_t)0;
+      xoff[i] = ok ? (uint32_t)(img * p.cin_planes * HW + iy * p.W + ix) * 16u : BUF_OOB;
     }
   };
   const buf_rsrc_t rs_in = make_buf(p.in, p.in_bytes);
@@ -178,26 +176,13 @@ __global__ __launch_bounds__(256, OCC) void conv_m32_kernel(const ConvLaunch p) 
     if SCP_DBG(p, 4) return;
     const int c = cl;
     const int planes = c == p.nchunks - 1 ? planes_last : p.cp;
-    const char* inb = static_cast<const char*>(p.in) + (size_t)c * p.cp * HW * 16;
     char* xl = xl0 + xb * p.lds_x;
-    if (p.in_bytes) {   // conv_pipe_kernel.h: dma16_buf (plane displacement in an SGPR, hardware zero fill for padding)
+    // conv_pipe_kernel.h: dma16_buf (plane displacement in an SGPR, hardware zero fill for padding)
 #pragma unroll
-      for (int i = 0; i < MAXP; ++i)
-        if (hs[i] >= 0)
-          for (int pl = 0; pl < planes; ++pl)
-            dma16_buf(rs_in, (uint32_t)xoff[i], (uint32_t)((c * p.cp + pl) * HW) * 16u, xl + pl * p.plane_stride + (i * 256 + wave * 64) * 16);
-      return;
-    }
-#pragma unroll
-    for (int i = 0; i < MAXP; ++i) {
-      if (hs[i] >= 0) {
-        const bool ok = xoff[i] != ~(size_t)0;
-        for (int pl = 0; pl < planes; ++pl) {
-          const char* src = ok ? inb + xoff[i] + (size_t)pl * HW * 16 : static_cast<const char*>(p.zero16);
-          dma16(src, xl + pl * p.plane_stride + (i * 256 + wave * 64) * 16);
-        }
-      }
-    }
+    for (int i = 0; i < MAXP; ++i)
+      if (hs[i] >= 0)
+        for (int pl = 0; pl < planes; ++pl)
+          dma16_buf(rs_in, xoff[i], (uint32_t)((c * p.cp + pl) * HW) * 16u, xl + pl * p.plane_stride + (i * 256 + wave * 64) * 16);
   };
   auto issue_w = [&](int it, int cl, int wb) {
     const int c = cl;

@@ -88,10 +88,7 @@ static_assert(m48_wait(8, 0, true, true) == 7 && m48_wait(8, 7, true, true) == 1
 // M16 > 0 (round 4): the Cout block is M16 16-row blocks instead of MR 32-row ones -- M16 = 3 with C16 = 8: 48-row blocks on 3 x 8
 // accumulators per consumer wave (512-pixel tile groups), for the one stride-1 layer with 48 output channels and a deep K
 // (transition1: 256 -> 48), which the 64-row form ran with a quarter of its MFMAs on padding rows.
-// ADDR: 0 = every tensor of the launch is buffer-addressed (< 4 GiB), 1 = 64-bit pointers, 2 = decided at run time (p.in_bytes).  The
-// 16x16x32-consumer variants are built for 0 and 1 separately: with both paths in one kernel the producers' stage loop is twice the
-// code and spills 70 SGPRs (round 5).
-template <int DT, int KS, int STRIDE, int MR, int NR, int WREG = 0, int C16 = 0, int M16 = 0, int ADDR = 2>
+template <int DT, int KS, int STRIDE, int MR, int NR, int WREG = 0, int C16 = 0, int M16 = 0>
 __global__ __launch_bounds__(512, 2) void conv_m32p_kernel(const ConvLaunch p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef typename DtOf<DT>::type T;
@@ -186,13 +183,11 @@ __global__ __launch_bounds__(512, 2) void conv_m32p_kernel(const ConvLaunch p) {
 #pragma unroll
     for (int k = 0; k < NQ; ++k) pixel_of(slot_of(k) < PXCAP ? slot_of(k) : P, qs[k], qy[k], qx[k]);
 
-    // Tensors below 4 GiB are addressed through buffer descriptors (conv_pipe_kernel.h: dma16_buf): per-item 32-bit
-    // lane offsets, chunk / plane displacement in an SGPR, padding lanes out of range.  Larger ones keep 64-bit pointers.
-    const bool buf = ADDR == 2 ? p.in_bytes != 0 : ADDR == 0;
+    // All tensors are addressed through buffer descriptors (conv_pipe_kernel.h: dma16_buf): per-item 32-bit lane offsets,
+    // chunk / plane displacement in an SGPR, padding lanes out of range (common.h: a launch covers a frame range that fits).
     const buf_rsrc_t rs_w = make_buf(p.wpk, (uint32_t)(p.n_mblk * p.nchunks * (int)chunk_wbytes));
     const buf_rsrc_t rs_in = make_buf(p.in, p.in_bytes), rs_res = make_buf(p.res ? p.res : p.out, p.out_bytes),
                      rs_out = make_buf(p.out, p.out_bytes);
-    size_t xoff[MAXP];
     uint32_t xvo[MAXP];
     auto locate_halo = [&](int it) {
 #pragma unroll
@@ -201,32 +196,17 @@ __global__ __launch_bounds__(512, 2) void conv_m32p_kernel(const ConvLaunch p) {
         decode_tile(it, hs[i], img, oy0, ox0);
         const int iy = oy0 * STRIDE - (KS / 2) + hy[i], ix = ox0 * STRIDE - (KS / 2) + hx[i];
         const bool ok = img >= 0 && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-        if (buf) xvo[i] = ok ? (uint32_t)(img * p.cin_planes * HW + (iy * p.W + ix)) * 16u : BUF_OOB;
-        else xoff[i] = ok ? ((size_t)img * p.cin_planes * HW + (size_t)(iy * p.W + ix)) * 16 : ~(size_t)0;
+        xvo[i] = ok ? (uint32_t)(img * p.cin_planes * HW + (iy * p.W + ix)) * 16u : BUF_OOB;
       }
     };
     auto issue_x = [&](int cl, int xb) {
       const int c = cl;   // chunks in natural order: results do not depend on the workgroup (batch position)
-      const char* inb = static_cast<const char*>(p.in) + (size_t)c * p.cp * HW * 16;
       char* xl = xl0 + xb * p.lds_x;
-      if (buf) {
 #pragma unroll
-        for (int i = 0; i < MAXP; ++i)
-          if (hs[i] >= 0)
-            for (int pl = 0; pl < p.cp; ++pl)
-              dma16_buf(rs_in, xvo[i], (uint32_t)((c * p.cp + pl) * HW) * 16u, xl + pl * p.plane_stride + (i * 256 + wave * 64) * 16);
-        return;
-      }
-#pragma unroll
-      for (int i = 0; i < MAXP; ++i) {
-        if (hs[i] >= 0) {
-          const bool ok = xoff[i] != ~(size_t)0;
-          for (int pl = 0; pl < p.cp; ++pl) {
-            const char* src = ok ? inb + xoff[i] + (size_t)pl * HW * 16 : static_cast<const char*>(p.zero16);
-            dma16(src, xl + pl * p.plane_stride + (i * 256 + wave * 64) * 16);
-          }
-        }
-      }
+      for (int i = 0; i < MAXP; ++i)
+        if (hs[i] >= 0)
+          for (int pl = 0; pl < p.cp; ++pl)
+            dma16_buf(rs_in, xvo[i], (uint32_t)((c * p.cp + pl) * HW) * 16u, xl + pl * p.plane_stride + (i * 256 + wave * 64) * 16);
     };
     // the first tile's first halo chunk is requested before anything else: it comes from HBM and lands under the weight loads below
     if (it_begin < it_end) { locate_halo(it_begin); issue_x(0, 0); }
@@ -281,52 +261,29 @@ __global__ __launch_bounds__(512, 2) void conv_m32p_kernel(const ConvLaunch p) {
         decode_tile(it, qs[k], img, oy0, ox0);
         const int oy = oy0 + qy[k], ox = ox0 + qx[k];
         const bool ok = img >= 0 && oy < p.Ho && ox < p.Wo;
-        // buffer addressing: the 32-bit offset lives in the same slot (BUF_OOB for pixels outside the map)
-        if (buf) qb[k] = ok ? (size_t)((uint32_t)(img * cout_planes * HoWo + oy * p.Wo + ox) * 16u) : (size_t)BUF_OOB;
-        else qb[k] = ok ? ((size_t)img * cout_planes * HoWo + (size_t)oy * p.Wo + ox) * 16 : ~(size_t)0;
+        // a 32-bit offset (BUF_OOB for pixels outside the map)
+        qb[k] = ok ? (size_t)((uint32_t)(img * cout_planes * HoWo + oy * p.Wo + ox) * 16u) : (size_t)BUF_OOB;
       }
     };
     // planes [pl0, pl1) of the retire buffer: residual rows of tile `it` -> RO (LDS-DMA)
     auto load_residual = [&](int it, const size_t* qb, int pl0, int pl1) {
       const int plane0 = (it - fdiv(it, p.fd_nmblk) * p.n_mblk) * ROPL;
-      if (buf) {
-        for (int pl = pl0; pl < pl1; ++pl)
-#pragma unroll
-          for (int k = 0; k < NQ; ++k)
-            if (moves(k, pl))
-              dma16_buf(rs_res, plane0 + pl < cout_planes ? (uint32_t)qb[k] : BUF_OOB, (uint32_t)((plane0 + pl) * HoWo) * 16u,
-                        ro + ((pl * PXCAP) + wslot_of(k)) * 16);
-        return;
-      }
       for (int pl = pl0; pl < pl1; ++pl)
 #pragma unroll
         for (int k = 0; k < NQ; ++k)
-          if (moves(k, pl)) {
-            const bool ok = qb[k] != ~(size_t)0 && plane0 + pl < cout_planes;
-            const char* src = ok ? static_cast<const char*>(p.res) + qb[k] + (size_t)(plane0 + pl) * HoWo * 16
-                                 : static_cast<const char*>(p.zero16);
-            dma16(src, ro + ((pl * PXCAP) + wslot_of(k)) * 16);
-          }
+          if (moves(k, pl))
+            dma16_buf(rs_res, plane0 + pl < cout_planes ? (uint32_t)qb[k] : BUF_OOB, (uint32_t)((plane0 + pl) * HoWo) * 16u,
+                      ro + ((pl * PXCAP) + wslot_of(k)) * 16);
     };
     // planes [pl0, pl1) of the retire buffer: results of tile `it` -> global
     auto store_results = [&](int it, const size_t* qb, int pl0, int pl1) {
       const int plane0 = (it - fdiv(it, p.fd_nmblk) * p.n_mblk) * ROPL;
-      if (buf) {
-        for (int pl = pl0; pl < pl1 && plane0 + pl < cout_planes; ++pl)
-#pragma unroll
-          for (int k = 0; k < NQ; ++k)
-            if (moves(k, pl))     // pixels outside the map carry BUF_OOB: the store is dropped by the hardware
-              store16_buf(rs_out, (uint32_t)qb[k], (uint32_t)((plane0 + pl) * HoWo) * 16u,
-                          *reinterpret_cast<const u32x4*>(ro + ((pl * PXCAP) + slot_of(k)) * 16));
-        return;
-      }
-      for (int pl = pl0; pl < pl1; ++pl)
+      for (int pl = pl0; pl < pl1 && plane0 + pl < cout_planes; ++pl)
 #pragma unroll
         for (int k = 0; k < NQ; ++k)
-          if (moves(k, pl) && qb[k] != ~(size_t)0 && plane0 + pl < cout_planes) {
-            const u32x4 v = *reinterpret_cast<const u32x4*>(ro + ((pl * PXCAP) + slot_of(k)) * 16);
-            *reinterpret_cast<u32x4*>(static_cast<char*>(p.out) + qb[k] + (size_t)(plane0 + pl) * HoWo * 16) = v;
-          }
+          if (moves(k, pl))     // pixels outside the map carry BUF_OOB: the store is dropped by the hardware
+            store16_buf(rs_out, (uint32_t)qb[k], (uint32_t)((plane0 + pl) * HoWo) * 16u,
+                        *reinterpret_cast<const u32x4*>(ro + ((pl * PXCAP) + slot_of(k)) * 16));
     };
 
     // memory instructions ahead of the consumers' MFMA stream -- for the 32x32x16 consumers (a 32-cycle MFMA leaves the issue port free
@@ -336,7 +293,7 @@ __global__ __launch_bounds__(512, 2) void conv_m32p_kernel(const ConvLaunch p) {
     if constexpr (!(C16 != 0 && M16 == 0)) __builtin_amdgcn_s_setprio(3);
     size_t qb_cur[NQ], qb_prev[NQ];
 #pragma unroll
-    for (int k = 0; k < NQ; ++k) qb_cur[k] = qb_prev[k] = buf ? (size_t)BUF_OOB : ~(size_t)0;
+    for (int k = 0; k < NQ; ++k) qb_cur[k] = qb_prev[k] = (size_t)BUF_OOB;
     int wc = 0, xb = 0;
     if (it_begin < it_end) {
       if (w_resident) {   // every chunk, in storage order, once per launch
@@ -992,24 +949,14 @@ __global__ __launch_bounds__(512, 2) void conv_m32p_kernel(const ConvLaunch p) {
   }
 }
 
-template <int DT, int STRIDE, int MR, int NR, int WREG = 0, int C16 = 0, int M16 = 0, int ADDR = 2>
-int32_t m32p_launch_addr(const ConvLaunch& L, size_t lds, hipStream_t st) {
-  auto kern = conv_m32p_kernel<DT, 3, STRIDE, MR, NR, WREG, C16, M16, ADDR>;
+template <int DT, int STRIDE, int MR, int NR, int WREG = 0, int C16 = 0, int M16 = 0>
+int32_t m32p_launch_one(const ConvLaunch& L, size_t lds, hipStream_t st) {
+  auto kern = conv_m32p_kernel<DT, 3, STRIDE, MR, NR, WREG, C16, M16>;
   static LdsOptIn big_lds;   // per device (common.h)
   { const int32_t rc = lds_opt_in(reinterpret_cast<const void*>(kern), 160 * 1024, &big_lds); if (rc != SCPOSE_OK) return rc; }
   hipLaunchKernelGGL(kern, dim3(L.grid), dim3(512), lds, st, L);
   SCP_CHECK_HIP(hipGetLastError());
   return SCPOSE_OK;
-}
-
-template <int DT, int STRIDE, int MR, int NR, int WREG = 0, int C16 = 0, int M16 = 0>
-int32_t m32p_launch_one(const ConvLaunch& L, size_t lds, hipStream_t st) {
-  if constexpr (C16 != 0) {   // one addressing mode per kernel (see ADDR)
-    return L.in_bytes != 0 ? m32p_launch_addr<DT, STRIDE, MR, NR, WREG, C16, M16, 0>(L, lds, st)
-                           : m32p_launch_addr<DT, STRIDE, MR, NR, WREG, C16, M16, 1>(L, lds, st);
-  } else {
-    return m32p_launch_addr<DT, STRIDE, MR, NR, WREG, C16, M16, 2>(L, lds, st);
-  }
 }
 
 template <int DT>

@@ -196,33 +196,18 @@ __global__ __launch_bounds__(256, OCC) void conv_pipe_kernel(const ConvLaunch p)
     if (img < 0 || SCP_DBG(p, 4)) return;
     const int planes = c == p.nchunks - 1 ? planes_last : p.cp;
     const int iy0 = oy0 * STRIDE - (KS / 2), ix0 = ox0 * STRIDE - (KS / 2);
-    const char* inb = static_cast<const char*>(p.in) + ((size_t)img * p.cin_planes + (size_t)(c * p.cp)) * HW * 16;
     char* xl = xl0 + (grp * 2 + xb) * p.lds_x;
-    if (p.in_bytes) {   // buffer addressing (tensors < 4 GiB): image / chunk / plane displacement in an SGPR, padding out of range
-      const buf_rsrc_t rs = make_buf(p.in, p.in_bytes);
-      const uint32_t sbase = (uint32_t)((img * p.cin_planes + c * p.cp) * HW) * 16u;
-#pragma unroll
-      for (int i = 0; i < MAXP; ++i) {
-        if (hy[i] >= 0) {
-          const int iy = iy0 + hy[i], ix = ix0 + hx[i];
-          const bool ok = iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-          const uint32_t voff = ok ? (uint32_t)(iy * p.W + ix) * 16u : BUF_OOB;
-          for (int pl = 0; pl < planes; ++pl)
-            dma16_buf(rs, voff, sbase + (uint32_t)(pl * HW) * 16u, xl + pl * p.plane_stride + (i * 256 + wave * 64) * 16);
-        }
-      }
-      return;
-    }
+    // buffer addressing: image / chunk / plane displacement in an SGPR, padding out of range
+    const buf_rsrc_t rs = make_buf(p.in, p.in_bytes);
+    const uint32_t sbase = (uint32_t)((img * p.cin_planes + c * p.cp) * HW) * 16u;
 #pragma unroll
     for (int i = 0; i < MAXP; ++i) {
       if (hy[i] >= 0) {
         const int iy = iy0 + hy[i], ix = ix0 + hx[i];
         const bool ok = iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-        const size_t g = ok ? (size_t)(iy * p.W + ix) * 16 : 0;
-        for (int pl = 0; pl < planes; ++pl) {
-          const char* src = ok ? inb + (size_t)pl * HW * 16 + g : static_cast<const char*>(p.zero16);
-          dma16(src, xl + pl * p.plane_stride + (i * 256 + wave * 64) * 16);
-        }
+        const uint32_t voff = ok ? (uint32_t)(iy * p.W + ix) * 16u : BUF_OOB;
+        for (int pl = 0; pl < planes; ++pl)
+          dma16_buf(rs, voff, sbase + (uint32_t)(pl * HW) * 16u, xl + pl * p.plane_stride + (i * 256 + wave * 64) * 16);
       }
     }
   };

@@ -343,12 +343,8 @@ int32_t fuse_down_launch(const FuseDownPacked& fd, const void* x0, int N, int H,
   SCP_REQUIRE(H % 8 == 0 && W % 8 == 0, "fuse_down: branch 0 is %dx%d (multiples of 8: the coarsest term is 1/8 of it)", H, W);
   const int Ho = H / 2, Wo = W / 2;
   const size_t in_frame = blocked_bytes(1, planes, H, W);
-  SCP_REQUIRE(fits_buf(in_frame), "fuse_down: one %dx%d frame does not fit a 32-bit buffer descriptor", H, W);
-  // batches whose branch-0 tensor (the largest) does not fit a buffer descriptor run as several launches (common.h: buf_max_frames)
-  static const char* cap = dev_env("SCPOSE_FD_MAXN");   // tests: force the split on a small batch
-  const int max_n = buf_max_frames(in_frame, cap ? atoi(cap) : 0);
-  for (int n0 = 0; n0 < N; n0 += max_n) {
-    const int n = N - n0 < max_n ? N - n0 : max_n;
+  // branch 0's tensor is the largest
+  return for_frame_ranges(N, in_frame, [&](int n0, int n) -> int32_t {
     FdLaunch L{};
     L.in = static_cast<const char*>(x0) + (size_t)n0 * in_frame;
     L.y = static_cast<char*>(y) + (size_t)n0 * in_frame;
@@ -379,10 +375,8 @@ int32_t fuse_down_launch(const FuseDownPacked& fd, const void* x0, int N, int H,
     if (grid > L.tiles_total) grid = L.tiles_total;
     L.tiles_per_wg = (L.tiles_total + grid - 1) / grid;
     L.grid = (L.tiles_total + L.tiles_per_wg - 1) / L.tiles_per_wg;
-    const int32_t rc = fd.dtype == SCPOSE_DT_BF16 ? fd_dispatch<0>(c0, nb, L, stream) : fd_dispatch<1>(c0, nb, L, stream);
-    if (rc != SCPOSE_OK) return rc;
-  }
-  return SCPOSE_OK;
+    return fd.dtype == SCPOSE_DT_BF16 ? fd_dispatch<0>(c0, nb, L, stream) : fd_dispatch<1>(c0, nb, L, stream);
+  }, "fuse_down %d x%d %dx%d", c0, nb, H, W);
 }
 
 }  // namespace scpose

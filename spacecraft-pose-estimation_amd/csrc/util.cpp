@@ -32,9 +32,13 @@ const char* dev_env(const char* name) {
   return enabled ? getenv(name) : nullptr;
 }
 
-uint32_t buf_bytes_or_64bit(size_t bytes) {
-  static const char* e = dev_env("SCPOSE_M32_BUF");
-  return (fits_buf(bytes) && !(e && atoi(e) == 0)) ? (uint32_t)bytes : 0;
+const FrameRangeSwitches& frame_range_switches() {
+  static const FrameRangeSwitches sw = [] {
+    const char* cap = dev_env("SCPOSE_MAXN");   // tests: force the frame-range split on a small batch
+    const char* dbg = dev_env("SCPOSE_DBG");    // bit 32, the host's lines, also in the shipped library (common.h: ConvLaunch::dbg)
+    return FrameRangeSwitches{cap ? atoi(cap) : 0, dbg && (atoi(dbg) & 32)};
+  }();
+  return sw;
 }
 
 int32_t lds_opt_in(const void* kernel, int bytes, LdsOptIn* memo) {

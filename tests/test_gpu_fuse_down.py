@@ -75,12 +75,13 @@ def test_fuse_down_returns_the_bits_of_the_unfused_rows(gpu_ops, tmp_path, name)
 def test_fuse_down_frame_range_split(gpu_ops, tmp_path):
     """Tensors are addressed through 32-bit buffer descriptors, so a batch whose branch-0 tensor reaches 4 GiB (about 4 850 frames
     at 96 x 96) runs as several launches over frame ranges, every pointer advanced by its own frame size.  The development switch
-    SCPOSE_FD_MAXN forces that split on five frames (ranges of 2, 2 and 1): same bits as one launch."""
+    SCPOSE_MAXN forces that split, here and in every other launch that splits, on five frames (ranges of 2, 2 and 1): same bits as
+    one launch."""
     from importlib import import_module
     nat = import_module("spacecraft-pose-estimation_amd._native")
     name = "w48_256_f16"
     whole = _run(tmp_path, name, {})
-    split = _run(tmp_path, name, {"SCPOSE_DEV": "1", "SCPOSE_FD_MAXN": "2", "SCPOSE_LIB": nat.LIB_PATH})
+    split = _run(tmp_path, name, {"SCPOSE_DEV": "1", "SCPOSE_MAXN": "2", "SCPOSE_LIB": nat.LIB_PATH})
     assert int(whole["launches"]) == int(split["launches"])
     for key in ["heat"] + TAPS:
         assert np.array_equal(whole[key], split[key]), key

@@ -397,6 +397,65 @@ def test_fused_bottleneck_matches_oracle(gpu_ops, h, w, n, dt):
     eng.close()
 
 
+BNECK_SPLIT_CODE = r"""
+import sys
+sys.path.insert(0, %(root)r)
+import numpy as np, torch, scpose
+from importlib import import_module
+from oracle import hrnet_ref as R
+ops = import_module('spacecraft-pose-estimation_amd.ops')
+cfg = R.tiny_cfg()
+sd = R.make_state_dict(cfg, seed=23)
+u8 = torch.randint(0, 256, (5, 64, 64, 3), generator=torch.Generator().manual_seed(29), dtype=torch.uint8).cuda()
+out = {}
+for dt in ('bf16', 'f16'):
+    eng = ops.HrnetEngine(cfg, sd, dtype=dt)
+    for tap in ('layer1.0', 'layer1.1'):
+        for run in range(2):   # back to back: the second launch of an op finds the tile-queue words its first one restored
+            out['%%s_%%s_%%d' %% (tap, dt, run)] = eng.forward_tap(u8, tap).cpu().numpy()
+    eng.close()
+np.savez(%(dst)r, **out)
+"""
+
+
+def test_fused_bottleneck_frame_range_split(gpu_ops, tmp_path):
+    """csrc/bottleneck.hip addresses its tensors through 32-bit buffer descriptors, so a batch whose 256-channel tensor reaches
+    4 GiB runs as several launches over frame ranges, which share the op's tile-queue words: each launch leaves them zero for the
+    next.  The development switch SCPOSE_MAXN forces that split on five 16 x 16 frames (ranges of 2, 2 and 1) for both forms --
+    layer1.0 (Cin = 64, projection folded into conv3) and layer1.1 (Cin = 256, identity residual): same bits as one launch,
+    twice in a row (sub-processes: switches are read once per process)."""
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    from importlib import import_module
+    nat = import_module("spacecraft-pose-estimation_amd._native")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(tag, extra_env):
+        dst = str(tmp_path / (tag + ".npz"))
+        env = {k: v for k, v in os.environ.items() if not k.startswith("SCPOSE_")}
+        env.update(extra_env)
+        r = subprocess.run([sys.executable, "-c", BNECK_SPLIT_CODE % dict(root=root, dst=dst)], capture_output=True, text=True, env=env,
+                           cwd=root, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        return np.load(dst), [ln for ln in r.stderr.splitlines() if ln.startswith("bottleneck ")]
+
+    whole, _ = run("whole", {})
+    split, ranges = run("split", {"SCPOSE_DEV": "1", "SCPOSE_MAXN": "2", "SCPOSE_DBG": "32", "SCPOSE_LIB": nat.LIB_PATH})
+    # the switch did switch: per dtype, layer1.0 twice (one Bottleneck), then layer1.1 twice (two), three launches each
+    fr = ("0..2", "2..4", "4..5")
+    per_dtype = 2 * ["bottleneck 64 16x16 N=5: frames " + f for f in fr] + \
+        2 * (["bottleneck 64 16x16 N=5: frames " + f for f in fr] + ["bottleneck 256 16x16 N=5: frames " + f for f in fr])
+    assert ranges == 2 * per_dtype, ranges
+    assert len(whole.files) == 8
+    for key in whole.files:
+        a, b = torch.from_numpy(whole[key]), torch.from_numpy(split[key])
+        assert a.shape == (5, 256, 16, 16) and torch.isfinite(a).all() and a.abs().max() > 0, key
+        assert torch.equal(a, b), "%s: %d of %d elements differ" % (key, int((a != b).sum()), a.numel())
+        assert torch.equal(a, torch.from_numpy(whole[key[:-1] + "0"])), "%s differs from run to run" % key
+
+
 @pytest.mark.parametrize("n", [1, 7, 9, 17])
 def test_layer1_is_batch_invariant_under_the_xcd_local_tile_queue(gpu_ops, n):
     """The Bottleneck kernels take their tiles from per-XCD queues (conv_device.h: tile_claim_xcd: XCD k owns the tiles of images

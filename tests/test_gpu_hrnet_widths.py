@@ -209,6 +209,65 @@ def test_w18_frames_are_batch_invariant_and_captured_and_fused_paths_agree(gpu_o
     eng.close()
 
 
+NET_SPLIT_CODE = r"""
+import sys
+sys.path.insert(0, %(root)r)
+import numpy as np, torch, scpose
+from importlib import import_module
+from oracle import hrnet_ref as R
+ops = import_module('spacecraft-pose-estimation_amd.ops')
+cfg = R.tiny_cfg(c=32)
+sd = R.make_state_dict(cfg, seed=6)
+x = torch.randn(5, 3, 64, 64, generator=torch.Generator().manual_seed(7)).cuda()
+center = torch.tensor([[80.0 + 3 * i, 60.0 - i] for i in range(5)]).cuda()
+scale = torch.tensor([[0.45 + 0.02 * i, 0.35] for i in range(5)]).cuda()
+eng = ops.HrnetEngine(cfg, sd, dtype=%(dt)r)
+out = {'heat': eng(x).cpu().numpy(), 'kp': eng.forward_decode(x, center, scale, True).cpu().numpy()}
+for tap in eng.tap_names():
+    out['tap:' + tap] = eng.forward_tap(x, tap).cpu().numpy()
+g = eng.capture(x.clone())
+out['heat_captured'] = g.replay().cpu().numpy()
+gd = eng.capture_decode(x.clone(), center.clone(), scale.clone(), True)
+out['kp_captured'] = gd.replay().cpu().numpy()
+out['nodes'] = np.array([g.nodes, gd.nodes])
+g.close(); gd.close(); eng.close()
+np.savez(%(dst)r, **out)
+"""
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+def test_whole_network_frame_range_split(gpu_ops, tmp_path, dt):
+    """Every launch that addresses a tensor through 32-bit buffer descriptors runs a batch of 4 GiB tensors as frame ranges
+    (csrc/common.h: for_frame_ranges).  The development switch SCPOSE_MAXN forces that on five frames of the widths 32 / 64 / 128 /
+    256 at 64 x 64 (ranges of 2, 2 and 1 in conv_launch, the fused Bottleneck, fuse_down and the fused BasicBlock): heat-maps, key
+    points and every tap carry the bits of the unsplit forward, eagerly and captured, where a launch that splits becomes several
+    graph nodes (sub-processes: switches are read once per process)."""
+    from importlib import import_module
+    nat = import_module("spacecraft-pose-estimation_amd._native")
+
+    def run(tag, extra_env):
+        dst = str(tmp_path / (tag + ".npz"))
+        env = {k: v for k, v in os.environ.items() if not k.startswith("SCPOSE_")}
+        env.update(extra_env)
+        r = subprocess.run([sys.executable, "-c", NET_SPLIT_CODE % dict(root=ROOT, dt=dt, dst=dst)], capture_output=True, text=True, env=env,
+                           cwd=ROOT, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        return np.load(dst)
+
+    whole = run("whole", {})
+    split = run("split", {"SCPOSE_DEV": "1", "SCPOSE_MAXN": "2", "SCPOSE_LIB": nat.LIB_PATH})
+    assert sorted(whole.files) == sorted(split.files) and sum(k.startswith("tap:") for k in whole.files) >= 40
+    assert (split["nodes"] > whole["nodes"]).all(), (whole["nodes"], split["nodes"])     # the switch did switch, under capture too
+    assert whole["heat"].shape == (5, 11, 16, 16) and whole["kp"].shape == (5, 11, 3)
+    for key in whole.files:
+        if key == "nodes":
+            continue
+        a, b = whole[key], split[key]
+        assert a.shape == b.shape and a.shape[0] == 5 and np.isfinite(a).all() and np.abs(a).max() > 0, key
+        assert np.array_equal(a.view(np.int32), b.view(np.int32)), "%s: %d of %d elements differ" % (key, int((a != b).sum()), a.size)
+    assert np.array_equal(whole["heat"], whole["heat_captured"]) and np.array_equal(whole["kp"], whole["kp_captured"])
+
+
 # ------------------------------------------------------------------------------------------ 4. stats
 def _with_blocks(cfg, stage2_blocks):
     out = {"MODEL": dict(cfg["MODEL"])}

@@ -16,10 +16,6 @@ const char* dev_env(const char* name) {   // as util.cpp, except that SCPOSE_DBG
   const char* e = getenv("SCPOSE_DEV");
   return e && atoi(e) != 0 ? getenv(name) : nullptr;
 }
-uint32_t buf_bytes_or_64bit(size_t bytes) {   // as util.cpp
-  const char* e = dev_env("SCPOSE_M32_BUF");
-  return (fits_buf(bytes) && !(e && atoi(e) == 0)) ? (uint32_t)bytes : 0;
-}
 int conv_device_cus() { return 256; }
 const void* conv_zero_page() { static const char z[256] = {0}; return z; }
 unsigned long long* conv_dbg_buffer(hipStream_t) { return nullptr; }
