@@ -119,6 +119,28 @@ int32_t scpose_hrnet_create(const scpose_hrnet_desc* desc, const char* const* na
                             int32_t allow_missing, scpose_hrnet_t* out);
 int32_t scpose_hrnet_destroy(scpose_hrnet_t h);
 
+/* pose_resnet (landmark_regression/lib/models/pose_resnet.py, the SimpleBaseline network): ResNet trunk, NUM_DECONV_LAYERS
+ * stride-2 ConvTranspose2d + BN + ReLU layers, a final 1x1 / 3x3 layer.  Returns the SAME handle type: every entry point
+ * that takes a scpose_hrnet_t works on it unchanged (scpose_hrnet_tail_fused reports 0: the tail is not fused, and
+ * scpose_hrnet_forward_decode runs forward + decode).  Heat-maps are H/32 * 2^L x W/32 * 2^L for L deconv layers.
+ * State-dict keys are the reference module's: conv1.weight, bn1.*, layerK.B.convN / bnN / downsample.0 / downsample.1,
+ * deconv_layers.{3i, 3i+1}.*, final_layer.*; allow_missing and unknown keys as for scpose_hrnet_create.  A deconv filter
+ * count that is no multiple of 16 is carried at the next multiple (zero planes). */
+typedef struct scpose_resnet_desc {
+  int32_t num_joints;          /* cfg.MODEL.NUM_JOINTS */
+  int32_t final_conv_kernel;   /* EXTRA.FINAL_CONV_KERNEL (1 or 3) */
+  int32_t num_layers;          /* EXTRA.NUM_LAYERS: 18, 34, 50, 101, 152 */
+  int32_t num_deconv_layers;   /* EXTRA.NUM_DECONV_LAYERS: 0..4 */
+  int32_t deconv_filters[4];   /* EXTRA.NUM_DECONV_FILTERS */
+  int32_t deconv_kernels[4];   /* EXTRA.NUM_DECONV_KERNELS: 4, 3 or 2 (padding / output_padding as _get_deconv_cfg) */
+  int32_t deconv_with_bias;    /* EXTRA.DECONV_WITH_BIAS */
+  int32_t dtype;               /* SCPOSE_DT_* */
+  float mean[3], std[3];       /* Normalize() constants for SCPOSE_IN_U8_NHWC */
+} scpose_resnet_desc;
+int32_t scpose_resnet_create(const scpose_resnet_desc* desc, const char* const* names,
+                             const float* const* ptrs, const int64_t* numels, int32_t count,
+                             int32_t allow_missing, scpose_hrnet_t* out);
+
 /* bytes of device workspace scpose_hrnet_forward needs for a batch of n frames of h x w. */
 int32_t scpose_hrnet_workspace_bytes(scpose_hrnet_t h, int32_t n, int32_t height, int32_t width,
                                      size_t* bytes);
@@ -752,6 +774,25 @@ int32_t scpose_basic_block_forward(scpose_conv_t conv1, scpose_conv_t conv2, con
 int32_t scpose_fuse_sum(const void* const* terms, const int32_t* shifts, int32_t nterms,
                         int32_t n, int32_t c, int32_t h, int32_t w, int32_t dtype, void* out,
                         void* stream);
+/* The two pose_resnet layers of conv_gather.hip.  y = [relu]( layer(x) + bias [+ residual] ), blocked 16-bit in and out.
+ * deconv: ConvTranspose2d(cin -> cout, k in {4, 3, 2}, stride 2, padding / output_padding of _get_deconv_cfg), out 2h x 2w;
+ *         weight is host f32 in ConvTranspose2d's own order (cin, cout, k, k).
+ * conv1x1s2: Conv2d(cin -> cout, 1x1, stride 2), out ceil(h/2) x ceil(w/2); weight host f32 (cout, cin).
+ * cin, cout multiples of 16; bias host f32[cout] or NULL. */
+typedef struct scpose_gather* scpose_gather_t;
+int32_t scpose_deconv_create(const float* weight, const float* bias, int32_t cin, int32_t cout, int32_t ksize, int32_t dtype,
+                             scpose_gather_t* out);
+int32_t scpose_conv1x1s2_create(const float* weight, const float* bias, int32_t cout, int32_t cin, int32_t dtype,
+                                scpose_gather_t* out);
+int32_t scpose_gather_destroy(scpose_gather_t g);
+int32_t scpose_gather_forward(scpose_gather_t g, const void* in, int32_t n, int32_t h, int32_t w, const void* residual,
+                              int32_t relu, void* out, void* stream);
+/* ResNet stem (resnet_stem.hip): relu(conv 7x7 s2 p3 (3 -> 64) + bias) -> max-pool 3x3 s2 p1, one launch.  weight: host f32
+ * (64, 3, 7, 7), BN-folded or plain; bias: host f32[64]; mean_std: host f32[6] (SCPOSE_IN_U8_NHWC) or NULL; in: device,
+ * uint8 NHWC or float32 NCHW; out: device, blocked 16-bit 64 x h/4 x w/4.  A unit-test entry point, not for a hot path: every call
+ * packs and uploads the weights, synchronises the stream and frees them again (the network's own stem does none of that). */
+int32_t scpose_resnet_stem_forward(const float* weight, const float* bias, const float* mean_std, const void* in, int32_t in_fmt,
+                                   int32_t n, int32_t h, int32_t w, int32_t dtype, void* out, void* stream);
 /* layout converters: float32 NCHW <-> blocked 16-bit (c multiple of 8). */
 int32_t scpose_nchw_f32_to_blocked(const float* src, int32_t n, int32_t c, int32_t h, int32_t w,
                                    int32_t dtype, void* dst, void* stream);

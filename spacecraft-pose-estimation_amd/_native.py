@@ -54,6 +54,21 @@ class HrnetDesc(ctypes.Structure):
     ]
 
 
+class ResnetDesc(ctypes.Structure):
+    _fields_ = [
+        ("num_joints", c_int32),
+        ("final_conv_kernel", c_int32),
+        ("num_layers", c_int32),
+        ("num_deconv_layers", c_int32),
+        ("deconv_filters", c_int32 * 4),
+        ("deconv_kernels", c_int32 * 4),
+        ("deconv_with_bias", c_int32),
+        ("dtype", c_int32),
+        ("mean", c_float * 3),
+        ("std", c_float * 3),
+    ]
+
+
 class DvsParams(ctypes.Structure):
     _fields_ = [
         ("h", c_int32),
@@ -78,6 +93,8 @@ SYMBOLS = {
     "scpose_is_dev_build": (c_int32, []),
     "scpose_hrnet_create": (c_int32, [POINTER(HrnetDesc), POINTER(c_char_p), POINTER(c_void_p),
                                       POINTER(c_int64), c_int32, c_int32, POINTER(c_void_p)]),
+    "scpose_resnet_create": (c_int32, [POINTER(ResnetDesc), POINTER(c_char_p), POINTER(c_void_p),
+                                       POINTER(c_int64), c_int32, c_int32, POINTER(c_void_p)]),
     "scpose_hrnet_destroy": (c_int32, [c_void_p]),
     "scpose_hrnet_workspace_bytes": (c_int32, [c_void_p, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
     "scpose_hrnet_heatmap_size": (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32)]),
@@ -180,6 +197,12 @@ SYMBOLS = {
     "scpose_conv_destroy": (c_int32, [c_void_p]),
     "scpose_conv_forward": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32,
                                       c_int32, c_void_p, c_void_p]),
+    "scpose_deconv_create": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, POINTER(c_void_p)]),
+    "scpose_conv1x1s2_create": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, POINTER(c_void_p)]),
+    "scpose_gather_destroy": (c_int32, [c_void_p]),
+    "scpose_gather_forward": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
+    "scpose_resnet_stem_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                             c_void_p, c_void_p]),
     "scpose_basic_block_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "scpose_fuse_sum": (c_int32, [POINTER(c_void_p), POINTER(c_int32), c_int32, c_int32, c_int32, c_int32,
                                   c_int32, c_int32, c_void_p, c_void_p]),

@@ -189,6 +189,13 @@ def _defaults():
     return c
 
 
+# The POSE_RESNET node of landmark_regression/lib/config/models.py:15-22 (MODEL.EXTRA of MODEL.NAME pose_resnet) and its lookup
+# table MODEL_EXTRAS (:56).  Like the reference's, they are offered for YAML authors and never merged into the default tree
+# (MODEL.EXTRA stays an empty new_allowed node).
+POSE_RESNET = CN({"NUM_LAYERS": 50, "DECONV_WITH_BIAS": False, "NUM_DECONV_LAYERS": 3, "NUM_DECONV_FILTERS": [256, 256, 256],
+                  "NUM_DECONV_KERNELS": [4, 4, 4], "FINAL_CONV_KERNEL": 1, "PRETRAINED_LAYERS": ["*"]})
+MODEL_EXTRAS = {"pose_resnet": POSE_RESNET}
+
 _C = _defaults()
 cfg = _C
 

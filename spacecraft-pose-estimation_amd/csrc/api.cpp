@@ -670,6 +670,79 @@ extern "C" int32_t scpose_basic_block_forward(scpose_conv_t conv1, scpose_conv_t
   return block_launch(conv1->pc, conv2->pc, in, n, h, w, out, static_cast<hipStream_t>(stream));
 }
 
+struct scpose_gather { GatherPacked gp; };
+
+extern "C" int32_t scpose_deconv_create(const float* weight, const float* bias, int32_t cin, int32_t cout, int32_t ksize,
+                                        int32_t dtype, scpose_gather_t* out) {
+  SCP_REQUIRE(weight && out, "deconv_create: null argument");
+  SCP_REQUIRE(cin > 0 && cout > 0 && ksize >= 2 && ksize <= 4, "deconv_create: cin=%d cout=%d kernel=%d", cin, cout, ksize);
+  const int kk = ksize * ksize;
+  std::vector<float> w((size_t)cout * cin * kk), b(cout, 0.f);   // (cin, cout, k, k) -> (cout, cin, k, k)
+  for (int ci = 0; ci < cin; ++ci)
+    for (int co = 0; co < cout; ++co)
+      for (int t = 0; t < kk; ++t) w[((size_t)co * cin + ci) * kk + t] = weight[((size_t)ci * cout + co) * kk + t];
+  if (bias) b.assign(bias, bias + cout);
+  scpose_gather* g = new (std::nothrow) scpose_gather();
+  if (!g) { set_error("deconv_create: out of host memory"); return SCPOSE_E_NOMEM; }
+  const int32_t rc = deconv_upload(w.data(), b.data(), cout, cin, ksize, dtype, &g->gp);
+  if (rc != SCPOSE_OK) { gather_free(&g->gp); delete g; return rc; }
+  *out = g;
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_conv1x1s2_create(const float* weight, const float* bias, int32_t cout, int32_t cin, int32_t dtype,
+                                           scpose_gather_t* out) {
+  SCP_REQUIRE(weight && out, "conv1x1s2_create: null argument");
+  SCP_REQUIRE(cin > 0 && cout > 0, "conv1x1s2_create: cin=%d cout=%d", cin, cout);
+  std::vector<float> b(cout, 0.f);
+  if (bias) b.assign(bias, bias + cout);
+  scpose_gather* g = new (std::nothrow) scpose_gather();
+  if (!g) { set_error("conv1x1s2_create: out of host memory"); return SCPOSE_E_NOMEM; }
+  const int32_t rc = conv1x1s2_upload(weight, b.data(), cout, cin, dtype, &g->gp);
+  if (rc != SCPOSE_OK) { gather_free(&g->gp); delete g; return rc; }
+  *out = g;
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_gather_destroy(scpose_gather_t g) {
+  if (!g) return SCPOSE_OK;
+  gather_free(&g->gp);
+  delete g;
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_gather_forward(scpose_gather_t g, const void* in, int32_t n, int32_t h, int32_t w, const void* residual,
+                                         int32_t relu, void* out, void* stream) {
+  SCP_REQUIRE(g && in && out, "gather_forward: null argument");
+  return gather_launch(g->gp, in, n, h, w, residual, relu, out, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t scpose_resnet_stem_forward(const float* weight, const float* bias, const float* mean_std, const void* in,
+                                              int32_t in_fmt, int32_t n, int32_t h, int32_t w, int32_t dtype, void* out, void* stream) {
+  SCP_REQUIRE(weight && bias && in && out, "resnet_stem_forward: null argument");
+  SCP_REQUIRE(dtype == SCPOSE_DT_BF16 || dtype == SCPOSE_DT_F16, "resnet_stem_forward: dtype %d", dtype);
+  SCP_REQUIRE(in_fmt != SCPOSE_IN_U8_NHWC || mean_std, "resnet_stem_forward: u8 input needs mean/std");
+  std::vector<uint16_t> pw;
+  resnet_stem_pack(weight, dtype, &pw);
+  void* d_w = nullptr; float* d_b = nullptr; float* d_ms = nullptr;
+  auto release = [&]() { if (d_w) (void)hipFree(d_w); if (d_b) (void)hipFree(d_b); if (d_ms) (void)hipFree(d_ms); };
+  int32_t rc = SCPOSE_OK;
+  if (hipMalloc(&d_w, pw.size() * 2) != hipSuccess || hipMalloc(&d_b, 64 * 4) != hipSuccess || hipMalloc(&d_ms, 6 * 4) != hipSuccess ||
+      hipMemcpy(d_w, pw.data(), pw.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d_b, bias, 64 * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      (mean_std && hipMemcpy(d_ms, mean_std, 6 * 4, hipMemcpyHostToDevice) != hipSuccess)) {
+    set_error("resnet_stem_forward: uploading the weights failed");
+    rc = SCPOSE_E_HIP;
+  }
+  if (rc == SCPOSE_OK) rc = resnet_stem_launch(in, in_fmt, d_w, d_b, mean_std ? d_ms : nullptr, n, h, w, dtype, out, static_cast<hipStream_t>(stream));
+  if (rc == SCPOSE_OK && hipStreamSynchronize(static_cast<hipStream_t>(stream)) != hipSuccess) {
+    set_error("resnet_stem_forward: the launch failed");
+    rc = SCPOSE_E_HIP;
+  }
+  release();
+  return rc;
+}
+
 extern "C" int32_t scpose_fuse_sum(const void* const* terms, const int32_t* shifts, int32_t nterms,
                                    int32_t n, int32_t c, int32_t h, int32_t w, int32_t dtype,
                                    void* out, void* stream) {

@@ -287,6 +287,37 @@ void fuse_down_free(FuseDownPacked* fd);
 int32_t fuse_down_launch(const FuseDownPacked& fd, const void* x0, int N, int H, int W, const void* const* terms, void* y,
                          void* const* outs, hipStream_t stream);
 
+// ---- pose_resnet: stem, transposed convolution, 1x1 stride-2 projection ----------------------
+// ResNet stem (resnet_stem.hip): conv 7x7 s2 p3 3 -> 64 + BN + ReLU + max-pool 3x3 s2 p1 in one launch
+void resnet_stem_pack(const float* w, int dtype, std::vector<uint16_t>* pw);
+int32_t resnet_stem_launch(const void* in, int in_fmt, const void* w, const float* bias, const float* mean_std, int N, int H, int W,
+                           int dtype, void* out, hipStream_t stream);
+// gather convolution (conv_gather.hip): ConvTranspose2d k 4 / 3 / 2 stride 2 by output parity class, Conv2d 1x1 stride 2
+struct GatherClass {
+  int32_t ntaps, dy[4], dx[4];   // input offsets of the class's taps relative to si * (my, mx)
+  int32_t py, px;                // the class's output position relative to so * (my, mx)
+  long long w_off;               // first A fragment of the class (16-byte units)
+};
+struct GatherLaunch {
+  const void* in; const void* w; const float* bias; const void* res; void* out;
+  int32_t N, H, W, Ho, Wo, Hb, Wb;   // input map, output map, base grid
+  int32_t cin, cout, nclass, si, so, relu;
+  GatherClass cls[4];
+};
+struct GatherPacked {
+  void* d_w = nullptr;
+  float* d_bias = nullptr;
+  int cin = 0, cout = 0, dtype = 0, nclass = 0, si = 1, so = 1, ks = 1;   // ks: the layer's kernel size (statistics only)
+  GatherClass cls[4];
+};
+// w: folded f32 [cout][cin][k][k] (a ConvTranspose2d weight transposed to the Conv2d order, NOT flipped), bias [cout]
+int32_t deconv_upload(const float* w, const float* bias, int cout, int cin, int k, int dtype, GatherPacked* gp);
+int32_t conv1x1s2_upload(const float* w, const float* bias, int cout, int cin, int dtype, GatherPacked* gp);
+void gather_free(GatherPacked* gp);
+void gather_out_size(const GatherPacked& gp, int H, int W, int* Ho, int* Wo);
+int32_t gather_launch(const GatherPacked& gp, const void* in, int N, int H, int W, const void* res, int relu, void* out,
+                      hipStream_t stream);
+
 // ---- elementwise ---------------------------------------------------------------------------
 int32_t fuse_sum_launch(const void* const* terms, const int32_t* shifts, int nterms, int N, int C,
                         int H, int W, int dtype, void* out, hipStream_t stream);

@@ -110,7 +110,7 @@ static bool fold(Weights& W, const std::string& conv, const std::string& bn, Cha
   return true;
 }
 
-enum OpKind { OP_CONV = 1, OP_FUSE = 2, OP_BLOCK = 3, OP_HEAD = 4, OP_STEM2 = 5, OP_BNECK = 6, OP_FDOWN = 8 };   // OP_FDOWN: fuse row 0 + first down hops of branch 0 (fuse_down.hip; 7 is the fused tail's profile signature)   // OP_STEM2: fused stem (stem_fused.hip); OP_BNECK: fused Bottleneck (bottleneck.hip)   // OP_BLOCK: fused BasicBlock (conv_block_kernel.h); OP_HEAD: head.hip
+enum OpKind { OP_CONV = 1, OP_FUSE = 2, OP_BLOCK = 3, OP_HEAD = 4, OP_STEM2 = 5, OP_BNECK = 6, OP_FDOWN = 8, OP_RSTEM = 9, OP_GATHER = 10 };   // OP_RSTEM: ResNet stem (resnet_stem.hip); OP_GATHER: transposed conv / 1x1 stride-2 projection (conv_gather.hip), conv = index into gathers   // OP_FDOWN: fuse row 0 + first down hops of branch 0 (fuse_down.hip; 7 is the fused tail's profile signature)   // OP_STEM2: fused stem (stem_fused.hip); OP_BNECK: fused Bottleneck (bottleneck.hip)   // OP_BLOCK: fused BasicBlock (conv_block_kernel.h); OP_HEAD: head.hip
 
 struct TensorDesc {
   int C, ds;       // channels (as carried: Chan::car), log2 spatial downscale w.r.t. the network input
@@ -159,6 +159,12 @@ struct scpose_hrnet {
   std::vector<Bneck> bnecks;
   std::vector<scpose::FuseDownPacked> fdowns;   // fuse row 0 + first down hops of branch 0 (fuse_down.hip), one per module that qualifies
   float* d_head_bias = nullptr; // [4][16] folded biases of the hrnet_cms heads
+  // pose_resnet (resnet_build): the stem's packed weights / bias, the deconv layers and stride-2 projections, and the heat-maps'
+  // log2 downscale (-1: an HRNet, whose heat-maps are H/4 * head_s)
+  void* d_rstem_w = nullptr;
+  float* d_rstem_b = nullptr;
+  std::vector<scpose::GatherPacked> gathers;
+  int out_ds = -1;
   uint32_t* d_sched = nullptr;  // 16 zero-initialised words per op: dynamic tile queues of the persistent kernels (conv_device.h: tile_claim)
   int head_k = 0, head_s = 1;   // transposed-conv kernel / stride of the heads (heat-map = S * branch-0 size)
   // fused tail (head_fused.hip): the last fuse sum and final_layer run as one kernel -- ops[fuse_op] is skipped and
@@ -371,6 +377,43 @@ struct Builder {
     snprintf(buf, sizeof(buf), "%s.%d.0.0", fp.c_str(), i);
     return buf;
   }
+  // pose_resnet: y = [relu](layer(x) [+ res]) on conv_gather.hip.  deconv_k == 0: `downsample` (Conv2d 1x1 stride 2 + BN);
+  // else deconv_layers (ConvTranspose2d(k, stride 2) [+ bias] + BN + ReLU, pose_resnet.py:166-191), whose weight is (in, out, k, k)
+  int gather(int x, const std::string& cname, const std::string& bname, Chan cout, int deconv_k, bool conv_bias, bool relu,
+             const std::string& tap) {
+    if (status != SCPOSE_OK) return -1;
+    const Chan cin = net->tensors[x].chan();
+    const int kk = deconv_k ? deconv_k * deconv_k : 1;
+    std::vector<float> w, b;
+    if (!deconv_k) {
+      if (!fold(*W, cname, bname, cout, cin, 1, conv_bias, &w, &b)) { status = SCPOSE_E_MISSING; return -1; }
+    } else {
+      const float* cw = W->get(cname + ".weight", cin, cout, kk);
+      const float* cb = conv_bias ? W->get(cname + ".bias", cout) : nullptr;
+      const float* g = W->get(bname + ".weight", cout, 1.f); const float* be = W->get(bname + ".bias", cout);
+      const float* mu = W->get(bname + ".running_mean", cout); const float* var = W->get(bname + ".running_var", cout, 1.f);
+      if (!W->missing.empty() && !W->allow_missing) { status = SCPOSE_E_MISSING; return -1; }
+      w.assign((size_t)cout.car * cin.car * kk, 0.f); b.assign(cout.car, 0.f);
+      for (int o = 0; o < cout.car; ++o) {
+        const double gg = g ? g[o] : 1.0, bb = be ? be[o] : 0.0, mm = mu ? mu[o] : 0.0, vv = var ? var[o] : 1.0;
+        const double s = gg / sqrt(vv + kBnEps), sh = bb - mm * s;
+        if (cw)
+          for (int i = 0; i < cin.car; ++i)
+            for (int t = 0; t < kk; ++t) w[((size_t)o * cin.car + i) * kk + t] = (float)((double)cw[((size_t)i * cout.car + o) * kk + t] * s);
+        b[o] = (float)((cb ? (double)cb[o] * s : 0.0) + sh);
+      }
+    }
+    GatherPacked gp;
+    const int32_t st = deconv_k ? deconv_upload(w.data(), b.data(), cout.car, cin.car, deconv_k, net->desc.dtype, &gp)
+                                : conv1x1s2_upload(w.data(), b.data(), cout.car, cin.car, net->desc.dtype, &gp);
+    net->gathers.push_back(gp);   // (pushed before the status check: hrnet_free releases whatever was allocated)
+    if (st != SCPOSE_OK) { status = st; return -1; }
+    Op op{};
+    op.kind = OP_GATHER; op.in = x; op.res = -1; op.conv = (int)net->gathers.size() - 1; op.relu = relu;
+    op.out = new_tensor(cout, net->tensors[x].ds + (deconv_k ? -1 : 1), tap);
+    push(op);
+    return op.out;
+  }
   int fuse(const std::vector<int>& terms, const std::vector<int>& shifts, Chan C, int ds, const std::string& name) {
     if (status != SCPOSE_OK) return -1;
     Op op{};
@@ -387,6 +430,71 @@ static std::string fmt(const char* f, ...) {
   char buf[256];
   va_list ap; va_start(ap, f); vsnprintf(buf, sizeof(buf), f, ap); va_end(ap);
   return buf;
+}
+
+static int32_t build_finish(scpose_hrnet* net, Weights& W, Builder& B);
+
+// pose_resnet.py:103-207: conv1 7x7 s2 + bn1 + relu + maxpool (one launch, resnet_stem.hip), layer1..layer4 of BasicBlocks
+// (:30-59; NUM_LAYERS 18, 34) or Bottlenecks (:62-100, stride on conv2; 50, 101, 152), deconv_layers, final_layer.
+// The first block of layer2..layer4 is stride 2 and projects its residual with `downsample` (:138-144).
+int32_t resnet_build(scpose_hrnet* net, Weights& W, const scpose_resnet_desc& d) {
+  Builder B{net, &W};
+  static const struct { int layers; bool bneck; int blocks[4]; } kSpec[5] = {
+    {18, false, {2, 2, 2, 2}}, {34, false, {3, 4, 6, 3}}, {50, true, {3, 4, 6, 3}}, {101, true, {3, 4, 23, 3}}, {152, true, {3, 8, 36, 3}}};
+  int si = -1;
+  for (int i = 0; i < 5; ++i) if (kSpec[i].layers == d.num_layers) si = i;
+  SCP_REQUIRE(si >= 0, "resnet_create: num_layers=%d (18, 34, 50, 101 or 152)", d.num_layers);
+  const bool bneck = kSpec[si].bneck;
+  int x;
+  {
+    SCP_CHECK_HIP(hipMalloc(&net->d_mean_std, 6 * 4));
+    float ms[6] = {d.mean[0], d.mean[1], d.mean[2], d.std[0], d.std[1], d.std[2]};
+    SCP_CHECK_HIP(hipMemcpy(net->d_mean_std, ms, sizeof(ms), hipMemcpyHostToDevice));
+    std::vector<float> w1, b1;
+    if (!fold(W, "conv1", "bn1", chan(64), chan_exact(3), 7, false, &w1, &b1)) return SCPOSE_E_MISSING;
+    std::vector<uint16_t> pw;
+    resnet_stem_pack(w1.data(), d.dtype, &pw);
+    SCP_CHECK_HIP(hipMalloc(&net->d_rstem_w, pw.size() * 2));
+    SCP_CHECK_HIP(hipMalloc(&net->d_rstem_b, 64 * 4));
+    SCP_CHECK_HIP(hipMemcpy(net->d_rstem_w, pw.data(), pw.size() * 2, hipMemcpyHostToDevice));
+    SCP_CHECK_HIP(hipMemcpy(net->d_rstem_b, b1.data(), 64 * 4, hipMemcpyHostToDevice));
+    Op stem{};
+    stem.kind = OP_RSTEM; stem.in = -2; stem.res = -1; stem.conv = -1; stem.relu = 1;
+    stem.out = B.new_tensor(chan(64), 2, "maxpool");
+    B.push(stem);
+    x = stem.out;
+  }
+  for (int L = 0; L < 4 && B.status == SCPOSE_OK; ++L) {
+    const int planes = 64 << L;
+    for (int b = 0; b < kSpec[si].blocks[L] && B.status == SCPOSE_OK; ++b) {
+      const std::string p = fmt("layer%d.%d", L + 1, b);
+      const int stride = (L > 0 && b == 0) ? 2 : 1;
+      if (bneck && L == 0) { x = B.bottleneck(x, p); continue; }   // 64 -> 64 -> 256 (+ projection in block 0): the fused layer1 kernel
+      if (!bneck && stride == 1) { x = B.basic_block(x, p, chan(planes)); continue; }
+      int res = x;
+      if (stride == 2) res = B.gather(x, p + ".downsample.0", p + ".downsample.1", chan(planes * (bneck ? 4 : 1)), 0, false, false, p + ".downsample");
+      int y;
+      if (bneck) {
+        y = B.conv(x, p + ".conv1", p + ".bn1", chan(planes), 1, 1, true);
+        y = B.conv(y, p + ".conv2", p + ".bn2", chan(planes), 3, stride, true);
+        y = B.conv(y, p + ".conv3", p + ".bn3", chan(4 * planes), 1, 1, true, res);
+      } else {
+        y = B.conv(x, p + ".conv1", p + ".bn1", chan(planes), 3, stride, true);
+        y = B.conv(y, p + ".conv2", p + ".bn2", chan(planes), 3, 1, true, res);
+      }
+      if (y >= 0) B.rename_tap(y, p);
+      x = y;
+    }
+  }
+  // deconv_layers: Sequential of (ConvTranspose2d, BatchNorm2d, ReLU) triples; layer i's output is named after its first module, 3i
+  for (int i = 0; i < d.num_deconv_layers && B.status == SCPOSE_OK; ++i)
+    x = B.gather(x, fmt("deconv_layers.%d", 3 * i), fmt("deconv_layers.%d", 3 * i + 1), chan(d.deconv_filters[i]), d.deconv_kernels[i],
+                 d.deconv_with_bias != 0, true, fmt("deconv_layers.%d", 3 * i));
+  if (B.status == SCPOSE_OK) {
+    net->out_ds = net->tensors[x].ds;
+    B.conv(x, "final_layer", "", chan_exact(d.num_joints), d.final_conv_kernel, 1, false, -1, true, true);
+  }
+  return build_finish(net, W, B);
 }
 
 int32_t hrnet_build(scpose_hrnet* net, Weights& W) {
@@ -576,6 +684,11 @@ int32_t hrnet_build(scpose_hrnet* net, Weights& W) {
       prev = B.head(ylist[b], name, b, net->head_k, net->head_s, prev, b == 0);
     }
   }
+  return build_finish(net, W, B);
+}
+
+// what every model's build ends with: the missing-key verdict, the tap-name check, the tile-queue words, liveness
+static int32_t build_finish(scpose_hrnet* net, Weights& W, Builder& B) {
   if (B.status == SCPOSE_E_MISSING || (!W.missing.empty() && !W.allow_missing)) {
     set_error("checkpoint tensor missing: %s", W.missing.c_str());
     return SCPOSE_E_MISSING;
@@ -696,6 +809,12 @@ struct HeadDecode {
   float* preds;
 };
 
+// H/4 (pose_hrnet), H / H/2 (the hrnet_cms heads), H/32 * 2^NUM_DECONV_LAYERS (pose_resnet)
+static void heatmap_hw(const scpose_hrnet* net, int h, int w, int32_t* hh, int32_t* hw) {
+  if (net->out_ds >= 0) { *hh = h >> net->out_ds; *hw = w >> net->out_ds; }
+  else { *hh = h / 4 * net->head_s; *hw = w / 4 * net->head_s; }
+}
+
 // does a forward of this shape run the fused tail (head_fused.hip)?
 bool hrnet_tail_fused(const scpose_hrnet* net, int n, int h, int w) {
   if (!net->headf.ok) return false;
@@ -776,6 +895,11 @@ int32_t hrnet_forward(scpose_hrnet* net, const void* in, int in_fmt, int n, int 
     } else if (op.kind == OP_STEM2) {
       rc = stem_fused_launch(in, in_fmt, net->d_stemf_w1, net->d_stemf_w2, net->d_stemf_b1, net->d_stemf_b2, net->d_mean_std,
                              n, h, w, net->desc.dtype, ptr(op.out), net->d_sched + 16 * oi, st);
+    } else if (op.kind == OP_RSTEM) {
+      rc = resnet_stem_launch(in, in_fmt, net->d_rstem_w, net->d_rstem_b, net->d_mean_std, n, h, w, net->desc.dtype, ptr(op.out), st);
+    } else if (op.kind == OP_GATHER) {
+      const TensorDesc& ti = net->tensors[op.in];
+      rc = gather_launch(net->gathers[op.conv], ptr(op.in), n, h >> ti.ds, w >> ti.ds, ptr(op.res), op.relu, ptr(op.out), st);
     } else if (op.kind == OP_CONV) {
       const TensorDesc& ti = net->tensors[op.in];
       void* out = op.out == -2 ? static_cast<void*>(heatmaps) : ptr(op.out);
@@ -816,7 +940,7 @@ int32_t hrnet_forward(scpose_hrnet* net, const void* in, int in_fmt, int n, int 
   st = st0;
   if (dec && !fused_tail && stop_tensor < 0) {   // unfused tail: decode.hip on the heat-maps
     int32_t hh = 0, hw = 0;
-    hh = h / 4 * net->head_s; hw = w / 4 * net->head_s;
+    heatmap_hw(net, h, w, &hh, &hw);
     const int32_t rc = decode_launch(heatmaps, n, net->desc.num_joints, hh, hw, dec->center, dec->scale, dec->post_process,
                                      dec->preds, nullptr, nullptr, st);
     if (rc != SCPOSE_OK) return rc;
@@ -857,6 +981,23 @@ static void op_work(const scpose_hrnet* net, const Op& op, int h, int w, double*
     *f = 2.0 * 27 * 64 * (h / 2) * (w / 2) + 2.0 * 64 * 64 * 9 * (h / 4) * (w / 4);
     *by = (double)64 * (h / 4) * (w / 4) * 2 + 3.0 * h * w + (unfused ? 2.0 * 64 * (h / 2) * (w / 2) * 2 : 0.0);
     sig[1] = 32; sig[2] = 3; sig[3] = 64;   // sig[0] stays OP_STEM2 (5): the fused stem is its own kernel class
+  } else if (op.kind == OP_RSTEM) {
+    // conv 7x7 s2 + max-pool: the launch reads the image and writes the H/4 x W/4 result (unfused accounting: + the H/2 x W/2
+    // convolution result written once and read once)
+    *f = 2.0 * 147 * 64 * (h / 2) * (w / 2);
+    *by = (double)64 * (h / 4) * (w / 4) * 2 + 3.0 * h * w + (unfused ? 2.0 * 64 * (h / 2) * (w / 2) * 2 : 0.0);
+    sig[1] = 72; sig[2] = 3; sig[3] = 64;
+  } else if (op.kind == OP_GATHER) {
+    // transposed conv: every input pixel meets all k x k taps (border taps that fall outside the output are not subtracted);
+    // 1x1 stride 2: only the pixels it keeps are read
+    const GatherPacked& gp = net->gathers[op.conv];
+    const TensorDesc& ti = net->tensors[op.in];
+    const double hi = h >> ti.ds, wi = w >> ti.ds, cin = ch(op.in), cout = ch(op.out);
+    const bool dc = gp.so == 2;
+    const double ho = dc ? 2 * hi : hi / 2, wo = dc ? 2 * wi : wi / 2;
+    *f = dc ? 2.0 * cin * cout * gp.ks * gp.ks * hi * wi : 2.0 * cin * cout * ho * wo;
+    *by = cin * (dc ? hi * wi : ho * wo) * 2 + cout * ho * wo * 2;
+    sig[1] = dc ? 200 + gp.ks * 10 + 2 : 12; sig[2] = gp.cin; sig[3] = gp.cout;
   } else if (op.kind == OP_CONV) {
     const PackedConv& pc = net->convs[op.conv];
     const TensorDesc& ti = net->tensors[op.in];
@@ -916,7 +1057,7 @@ void hrnet_stats(scpose_hrnet* net, int h, int w, int* launches, double* flops, 
   for (const Op& op : net->ops) {
     double of, ob; int32_t sig[4];
     op_work(net, op, h, w, &of, &ob, sig, true, real);   // whole-net figure in SURVEY.md 8(d)'s accounting (422 MB for W48 384^2)
-    if (op.kind == OP_STEM2) ob -= 3.0 * h * w;   // network input is not an inter-layer activation
+    if (op.kind == OP_STEM2 || op.kind == OP_RSTEM) ob -= 3.0 * h * w;   // network input is not an inter-layer activation
     f += of; by += ob;
   }
   const int skipped = hrnet_tail_fused(net, 1, h, w) ? 1 : 0;   // the fused tail absorbs the last fuse row
@@ -940,6 +1081,9 @@ void hrnet_free(scpose_hrnet* net) {
   if (net->d_stemf_b1) (void)hipFree(net->d_stemf_b1);
   if (net->d_stemf_b2) (void)hipFree(net->d_stemf_b2);
   if (net->d_head_bias) (void)hipFree(net->d_head_bias);
+  if (net->d_rstem_w) (void)hipFree(net->d_rstem_w);
+  if (net->d_rstem_b) (void)hipFree(net->d_rstem_b);
+  for (auto& g : net->gathers) gather_free(&g);
   if (net->d_sched) (void)hipFree(net->d_sched);
   if (net->headf.d_w) (void)hipFree(net->headf.d_w);
   if (net->headf.d_b) (void)hipFree(net->headf.d_b);
@@ -1003,6 +1147,42 @@ extern "C" int32_t scpose_hrnet_create(const scpose_hrnet_desc* desc, const char
   return SCPOSE_OK;
 }
 
+extern "C" int32_t scpose_resnet_create(const scpose_resnet_desc* desc, const char* const* names,
+                                        const float* const* ptrs, const int64_t* numels,
+                                        int32_t count, int32_t allow_missing, scpose_hrnet_t* out) {
+  SCP_REQUIRE(desc && out, "resnet_create: null argument");
+  SCP_REQUIRE(desc->num_joints > 0, "resnet_create: num_joints=%d", desc->num_joints);
+  SCP_REQUIRE(desc->final_conv_kernel == 1 || desc->final_conv_kernel == 3, "resnet_create: final_conv_kernel=%d (1 or 3)", desc->final_conv_kernel);
+  SCP_REQUIRE(desc->dtype == SCPOSE_DT_BF16 || desc->dtype == SCPOSE_DT_F16, "resnet_create: dtype=%d", desc->dtype);
+  SCP_REQUIRE(desc->num_layers == 18 || desc->num_layers == 34 || desc->num_layers == 50 || desc->num_layers == 101 || desc->num_layers == 152,
+              "resnet_create: num_layers=%d (18, 34, 50, 101 or 152)", desc->num_layers);
+  SCP_REQUIRE(desc->num_deconv_layers >= 0 && desc->num_deconv_layers <= 4, "resnet_create: num_deconv_layers=%d (0..4)", desc->num_deconv_layers);
+  for (int i = 0; i < desc->num_deconv_layers; ++i) {
+    SCP_REQUIRE(desc->deconv_kernels[i] >= 2 && desc->deconv_kernels[i] <= 4, "resnet_create: deconv_kernels[%d]=%d (4, 3 or 2)", i, desc->deconv_kernels[i]);
+    SCP_REQUIRE(desc->deconv_filters[i] > 0 && desc->deconv_filters[i] <= (1 << 16), "resnet_create: deconv_filters[%d]=%d must be positive", i, desc->deconv_filters[i]);
+  }
+  Weights W;
+  W.allow_missing = allow_missing != 0;
+  for (int i = 0; i < count; ++i)
+    if (names[i] && ptrs[i]) W.m[names[i]] = HostTensor{ptrs[i], numels[i]};
+  scpose_hrnet* net = new (std::nothrow) scpose_hrnet();
+  if (!net) { set_error("resnet_create: out of host memory"); return SCPOSE_E_NOMEM; }
+  net->desc = scpose_hrnet_desc{};   // the fields every entry point reads: joints, dtype, normalisation; head = final_layer
+  net->desc.num_joints = desc->num_joints; net->desc.final_conv_kernel = desc->final_conv_kernel; net->desc.dtype = desc->dtype;
+  for (int i = 0; i < 3; ++i) { net->desc.mean[i] = desc->mean[i]; net->desc.std[i] = desc->std[i]; }
+  net->desc.head = SCPOSE_HEAD_FINAL_LAYER;
+  (void)hipGetDevice(&net->device);
+  int32_t rc = resnet_build(net, W, *desc);
+  if (rc == SCPOSE_OK) {
+    net->events.assign(net->ops.size() + 1, nullptr);
+    for (auto& e : net->events)
+      if (hipEventCreate(&e) != hipSuccess) { set_error("resnet_create: hipEventCreate failed"); rc = SCPOSE_E_HIP; break; }
+  }
+  if (rc != SCPOSE_OK) { hrnet_free(net); delete net; return rc; }
+  *out = net;
+  return SCPOSE_OK;
+}
+
 extern "C" int32_t scpose_hrnet_destroy(scpose_hrnet_t h) {
   if (!h) return SCPOSE_OK;
   hrnet_free(h);
@@ -1024,8 +1204,7 @@ extern "C" int32_t scpose_hrnet_heatmap_size(scpose_hrnet_t h, int32_t height, i
   SCP_REQUIRE(h && out_h && out_w, "hrnet_heatmap_size: null argument");
   SCP_REQUIRE(height > 0 && width > 0 && height % 32 == 0 && width % 32 == 0,
               "hrnet_heatmap_size: H=%d W=%d (multiples of 32)", height, width);
-  *out_h = height / 4 * h->head_s;
-  *out_w = width / 4 * h->head_s;
+  heatmap_hw(h, height, width, out_h, out_w);
   return SCPOSE_OK;
 }
 

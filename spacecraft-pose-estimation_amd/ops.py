@@ -108,6 +108,59 @@ class Conv:
             pass
 
 
+class GatherConv:
+    """One pose_resnet layer of csrc/conv_gather.hip: y = [relu](layer(x) + b [+ res]), blocked 16-bit in and out.
+    deconv_kernel 4 / 3 / 2: ConvTranspose2d(stride 2), weight (cin, cout, k, k), out 2h x 2w; None: Conv2d 1x1 stride 2, weight
+    (cout, cin, 1, 1), out ceil(h / 2) x ceil(w / 2)."""
+
+    def __init__(self, weight, bias=None, deconv_kernel=None, dtype="bf16"):
+        w = weight.detach().float().cpu().contiguous()
+        self.deconv = deconv_kernel is not None
+        self.cin, self.cout = (w.shape[0], w.shape[1]) if self.deconv else (w.shape[1], w.shape[0])
+        b = bias.detach().float().cpu().contiguous() if bias is not None else None
+        pb = c_void_p(b.data_ptr()) if b is not None else c_void_p(0)
+        h = c_void_p()
+        if self.deconv:
+            nat.check(nat.lib().scpose_deconv_create(c_void_p(w.data_ptr()), pb, self.cin, self.cout, int(deconv_kernel), dtype_code(dtype),
+                                                     ctypes.byref(h)), "deconv_create")
+        else:
+            nat.check(nat.lib().scpose_conv1x1s2_create(c_void_p(w.data_ptr()), pb, self.cout, self.cin, dtype_code(dtype), ctypes.byref(h)),
+                      "conv1x1s2_create")
+        self._h = h
+
+    def __call__(self, xb, residual=None, relu=False):
+        _need_cuda(xb, residual)
+        n, cg, h, w, _ = xb.shape
+        assert cg * 8 == self.cin, (cg * 8, self.cin)
+        ho, wo = (2 * h, 2 * w) if self.deconv else ((h + 1) // 2, (w + 1) // 2)
+        out = torch.empty((n, self.cout // 8, ho, wo, 8), dtype=xb.dtype, device=xb.device)
+        nat.check(nat.lib().scpose_gather_forward(self._h, _ptr(xb), n, h, w, _ptr(residual), int(relu), _ptr(out), _stream()), "gather_forward")
+        return out
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                nat.lib().scpose_gather_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+def resnet_stem(x, weight, bias, dtype="bf16", mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
+    """relu(conv 7x7 s2 p3 (3 -> 64) + bias) -> max-pool 3x3 s2 p1 as one launch (csrc/resnet_stem.hip).  x: uint8 (N, H, W, 3), normalised
+    with mean / std, or float32 (N, 3, H, W); weight (64, 3, 7, 7) and bias (64,) BN-folded.  Returns blocked 16-bit 64 x H/4 x W/4."""
+    _need_cuda(x)
+    x = x.contiguous()
+    fmt, n, h, w = HrnetEngine._input_format(x, "resnet_stem")
+    wt = weight.detach().float().cpu().contiguous(); b = bias.detach().float().cpu().contiguous()
+    ms = torch.tensor(list(mean) + list(std), dtype=torch.float32)
+    dt = dtype_code(dtype)
+    out = torch.empty((n, 8, h // 4, w // 4, 8), dtype=_TORCH_DT[dt], device=x.device)
+    nat.check(nat.lib().scpose_resnet_stem_forward(c_void_p(wt.data_ptr()), c_void_p(b.data_ptr()), c_void_p(ms.data_ptr()), _ptr(x), fmt,
+                                                   n, h, w, dt, _ptr(out), _stream()), "resnet_stem_forward")
+    return out
+
+
 def fuse_sum(terms, shifts, out_hw):
     """relu(sum_t nearest_upsample(term_t, 2**shift_t)); terms blocked, out at (H, W)."""
     _need_cuda(*terms)
@@ -1178,10 +1231,12 @@ def desc_from_cfg(cfg, dtype="bf16", mean=(0.485, 0.456, 0.406), std=(0.229, 0.2
     MODEL.NAME in pose_hrnet / hrnet_cms / hrnet_cms_384 (the modules of landmark_regression/lib/models/)."""
     model = cfg["MODEL"]
     extra = model["EXTRA"]
-    d = nat.HrnetDesc()
     name = str(model["NAME"]) if "NAME" in model else "pose_hrnet"
+    if name == "pose_resnet":
+        return resnet_desc_from_cfg(cfg, dtype, mean, std)
+    d = nat.HrnetDesc()
     if name not in HEAD_CODES:
-        raise nat.NativeError("MODEL.NAME=%s: supported models are %s" % (name, ", ".join(HEAD_CODES)))
+        raise nat.NativeError("MODEL.NAME=%s: supported models are %s, pose_resnet" % (name, ", ".join(HEAD_CODES)))
     d.head = HEAD_CODES[name]
     d.num_joints = int(model["NUM_JOINTS"])
     d.final_conv_kernel = int(extra["FINAL_CONV_KERNEL"])
@@ -1196,6 +1251,34 @@ def desc_from_cfg(cfg, dtype="bf16", mean=(0.485, 0.456, 0.406), std=(0.229, 0.2
         for b in range(int(s["NUM_BRANCHES"])):
             d.num_blocks[si][b] = int(s["NUM_BLOCKS"][b])
             d.num_channels[si][b] = int(s["NUM_CHANNELS"][b])
+    d.dtype = dtype_code(dtype)
+    for i in range(3):
+        d.mean[i] = mean[i]
+        d.std[i] = std[i]
+    return d
+
+
+def resnet_desc_from_cfg(cfg, dtype="bf16", mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
+    """scpose_resnet_desc of MODEL.NAME pose_resnet: MODEL.EXTRA holds NUM_LAYERS, DECONV_WITH_BIAS, NUM_DECONV_LAYERS / FILTERS /
+    KERNELS and FINAL_CONV_KERNEL (the POSE_RESNET node of landmark_regression/lib/config/models.py).  The library judges the
+    values; only what the fixed-size descriptor cannot hold is refused here."""
+    model = cfg["MODEL"]
+    extra = model["EXTRA"]
+    d = nat.ResnetDesc()
+    d.num_joints = int(model["NUM_JOINTS"])
+    d.final_conv_kernel = int(extra["FINAL_CONV_KERNEL"])
+    d.num_layers = int(extra["NUM_LAYERS"])
+    n = int(extra["NUM_DECONV_LAYERS"])
+    filters, kernels = list(extra["NUM_DECONV_FILTERS"]), list(extra["NUM_DECONV_KERNELS"])
+    if n > 4:
+        raise nat.NativeError("EXTRA.NUM_DECONV_LAYERS=%d: at most 4 deconv layers" % n)
+    if n > len(filters) or n > len(kernels):
+        raise nat.NativeError("EXTRA.NUM_DECONV_LAYERS=%d but %d NUM_DECONV_FILTERS and %d NUM_DECONV_KERNELS" % (n, len(filters), len(kernels)))
+    d.num_deconv_layers = n
+    for i in range(n):
+        d.deconv_filters[i] = int(filters[i])
+        d.deconv_kernels[i] = int(kernels[i])
+    d.deconv_with_bias = int(bool(extra["DECONV_WITH_BIAS"]))
     d.dtype = dtype_code(dtype)
     for i in range(3):
         d.mean[i] = mean[i]
@@ -1228,8 +1311,10 @@ class HrnetEngine:
         c_numels = (c_int64 * n)(*numels)
         h = c_void_p()
         with torch.cuda.device(self.device):
-            nat.check(nat.lib().scpose_hrnet_create(ctypes.byref(self.desc), c_names, c_ptrs, c_numels, n,
-                                                    int(allow_missing), ctypes.byref(h)), "hrnet_create")
+            resnet = isinstance(self.desc, nat.ResnetDesc)     # MODEL.NAME pose_resnet: the same handle type from its own create
+            create = nat.lib().scpose_resnet_create if resnet else nat.lib().scpose_hrnet_create
+            nat.check(create(ctypes.byref(self.desc), c_names, c_ptrs, c_numels, n, int(allow_missing), ctypes.byref(h)),
+                      "resnet_create" if resnet else "hrnet_create")
         self._h = h
         self._ws = None
 

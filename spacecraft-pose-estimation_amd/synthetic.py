@@ -39,6 +39,45 @@ def hrnet_cfg(width=48, num_joints=11, image=384, modules=(1, 4, 3)):
                                 "STAGE3": stage(3, modules[1]), "STAGE4": stage(4, modules[2])}}}
 
 
+def pose_resnet_cfg(num_layers=50, num_joints=11, image=256, deconv_filters=(256, 256, 256), deconv_kernels=(4, 4, 4),
+                    deconv_with_bias=False, final_conv_kernel=1):
+    """Plain-dict cfg of MODEL.NAME pose_resnet in the shape of the reference's POSE_RESNET node (lib/config/models.py)."""
+    hm = image // 32 * 2 ** len(deconv_filters)
+    return {"MODEL": {"NAME": "pose_resnet", "NUM_JOINTS": num_joints, "INIT_WEIGHTS": False, "PRETRAINED": "",
+                      "IMAGE_SIZE": [image, image], "HEATMAP_SIZE": [hm, hm],
+                      "EXTRA": {"PRETRAINED_LAYERS": ["*"], "FINAL_CONV_KERNEL": final_conv_kernel, "NUM_LAYERS": num_layers,
+                                "DECONV_WITH_BIAS": deconv_with_bias, "NUM_DECONV_LAYERS": len(deconv_filters),
+                                "NUM_DECONV_FILTERS": list(deconv_filters), "NUM_DECONV_KERNELS": list(deconv_kernels)}}}
+
+
+def pose_resnet_checkpoint(cfg, seed=0):
+    """Seeded state_dict of pose_resnet in the style of random_checkpoint: fan-in-scaled weights and BN statistics near identity,
+    so that activations stay O(1) through 150 layers.  A Conv2d weight (out, in, k, k) has fan-in in * k * k; a stride-2
+    ConvTranspose2d weight (in, out, k, k) feeds each output from about k * k / 4 taps of every input channel."""
+    from importlib import import_module
+    net_cls = import_module(".models.pose_resnet", __package__).PoseResNet
+    with torch.device("meta"):
+        spec = net_cls(cfg).state_dict()
+    g = torch.Generator().manual_seed(seed)
+    sd = OrderedDict()
+    for name, meta in spec.items():
+        shape = tuple(meta.shape)
+        leaf = name.rsplit(".", 1)[1]
+        deconv_conv = name.startswith("deconv_layers") and len(shape) == 4
+        if leaf == "num_batches_tracked":
+            sd[name] = torch.tensor(0, dtype=torch.long)
+        elif len(shape) == 4:
+            fan_in = shape[0] * shape[2] * shape[3] / 4.0 if deconv_conv else shape[1] * shape[2] * shape[3]
+            sd[name] = (torch.rand(shape, generator=g) * 2 - 1) * (3.0 / fan_in) ** 0.5     # unit gain: var(w) = 1 / fan_in
+        elif leaf == "bias" and (name.startswith("final_layer") or (name.startswith("deconv_layers") and int(name.split(".")[1]) % 3 == 0)):
+            sd[name] = (torch.rand(shape, generator=g) * 2 - 1) * 0.05
+        elif leaf in ("weight", "running_var"):
+            sd[name] = 0.9 + 0.2 * torch.rand(shape, generator=g)
+        else:
+            sd[name] = 0.05 * torch.randn(shape, generator=g)
+    return sd
+
+
 def random_checkpoint(cfg, seed=0):
     """Random-init state_dict of the architecture: Conv2d default init (kaiming-uniform, a=sqrt 5 ==
     U(+-1/sqrt(fan_in))), BN gamma,var ~ U[.75,1.25], beta,mean ~ N(0,.1^2) so activations stay O(1)
@@ -321,6 +360,52 @@ def w48_chain_checkpoint(seed=0, eps=W48_CHAIN_EPS):
             scale_bn(name[:-len(".weight")], eps)                     # BasicBlocks of branch 0
         if p[0] in ("stage2", "stage3", "stage4") and p[2] == "fuse_layers" and p[3] == "0" and p[5] == "1" and p[6] == "weight":
             scale_bn(name[:-len(".weight")], eps)                     # up paths into branch 0 (fuse_layers.0.j = [conv1x1, bn, upsample])
+    w = sd["final_layer.weight"]; w *= eps
+    for j in range(11):
+        w[j, j, 0, 0] += 1.0
+    sd["final_layer.bias"].zero_()
+    return sd
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# A CONSTRUCTED pose_resnet (ResNet-18, 128 x 128) checkpoint whose heat-maps are peaked.  A ResNet has no high-resolution path, so
+# nothing short of training makes it LOCATE landmarks; the chain criterion only needs heat-maps whose arg-max and quarter-pixel
+# decisions have margin against 16-bit rounding noise, computed from the image by every kernel of the forward.
+# ---------------------------------------------------------------------------------------------------------------------------
+RESNET_CHAIN_FILTERS, RESNET_CHAIN_EPS = (32, 32, 32), 0.02
+RESNET_CHAIN_TAPS = (0.2, 0.8, 0.6, 0.1)     # 1-D profile of the k4 deconv kernels: a lone hot pixel becomes 0.2 0.8 0.6 0.1, one strict maximum
+
+
+def pose_resnet_chain_cfg(image=128):
+    return pose_resnet_cfg(18, 11, image, RESNET_CHAIN_FILTERS, (4, 4, 4), False, 1)
+
+
+def pose_resnet_chain_checkpoint(channels, seed=0, eps=RESNET_CHAIN_EPS):
+    """state_dict of pose_resnet_chain_cfg(): pose_resnet_checkpoint(seed) with the head turned into "take layer4 channel
+    channels[j] as joint j's coarse map and upsample it three times with a skewed tent kernel", everything else of the head kept
+    RANDOM but scaled by `eps` (the W48 chain checkpoint's recipe):
+
+      * deconv_layers.0: filter j reads trunk channel channels[j] through outer(RESNET_CHAIN_TAPS, RESNET_CHAIN_TAPS); deconv_layers.3 / .6:
+        filter j reads filter j the same way; all other weights random * eps; the BatchNorms of filters 0..10 are the identity, the
+        rest are scaled by eps (layer4's output is >= 0, so the ReLUs pass the eleven maps unchanged);
+      * final_layer: identity on filters 0..10 (+ eps * random), zero bias.
+
+    Heat-map j is then the 8x skewed-tent upsampling of one coarse 4 x 4 feature map of the random trunk: a smooth surface with one
+    strict maximum near the hottest coarse cell.  `channels` are chosen (tests/golden/make_pose_resnet_chain.py) as the trunk
+    channels whose maps keep the widest margins on the test's frames; the fixture stores the eleven indices and the seeds."""
+    cfg = pose_resnet_chain_cfg()
+    sd = pose_resnet_checkpoint(cfg, seed)
+    k2 = torch.outer(torch.tensor(RESNET_CHAIN_TAPS), torch.tensor(RESNET_CHAIN_TAPS))
+    for i in range(3):
+        w = sd["deconv_layers.%d.weight" % (3 * i)]      # (in, out, 4, 4)
+        w *= eps
+        for j in range(11):
+            w[:, j] = 0.0
+            w[int(channels[j]) if i == 0 else j, j] = k2
+        bn = "deconv_layers.%d" % (3 * i + 1)
+        sd[bn + ".weight"] *= eps; sd[bn + ".bias"] *= eps
+        sd[bn + ".weight"][:11] = 1.0; sd[bn + ".bias"][:11] = 0.0
+        sd[bn + ".running_mean"][:11] = 0.0; sd[bn + ".running_var"][:11] = 1.0 - 1e-5
     w = sd["final_layer.weight"]; w *= eps
     for j in range(11):
         w[j, j, 0, 0] += 1.0
