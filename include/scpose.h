@@ -454,6 +454,35 @@ int32_t scpose_events_aedat2_unpack(const uint8_t* records, int64_t n_records, i
                                     int64_t* t, int32_t* x, int32_t* y, int8_t* p, int64_t capacity,
                                     int64_t* count_status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* (ABI 7, additive) The polarity packets of an AEDAT-3.1 recording on the device (csrc/events_aedat3_read.hip, which states the
+ * format): the whole file and one descriptor per polarity packet -> the four columns, the valid events in file order.  The host
+ * reads the text header and walks the 28-byte packet headers (event_read.parse_aedat3).  Two calls on one workspace, in this order,
+ * and one small read-back between them:
+ *   _count     one workgroup per packet counts the events whose valid bit is set.  count_status device i64 [6] <- [n_events, status,
+ *              t of the first valid event, 0, 0, 0]; n_events = 0 unless status is 0.  Read back; allocate the columns.
+ *   _unpack    the valid events -> t = (eventTSOverflow << 31) | ts (minus the first t when rebase != 0), x = data bits 17..31,
+ *              y = data bits 2..16, p = data bit 1.  Adds to count_status [3] n_backward (events whose t is below their
+ *              predecessor's) and [4] n_out_of_range (x >= w or y >= h; sets SCPOSE_AEDAT3_RANGE).  Writes nothing unless status
+ *              was 0 and n_events <= capacity (else SCPOSE_AEDAT3_CAPACITY).  Read count_status back once more for the counters.
+ *   file       device u8, the recording, no alignment asked; packets: device i64 [n_packets][3], (payload offset in file,
+ *              eventNumber, eventTSOverflow) of each polarity packet, the payload's eventNumber * 8 bytes and the 28 header bytes
+ *              before it inside the file -- the caller's duty, the kernels check every read against eventNumber * 8 only
+ *   status     SCPOSE_AEDAT3_CORRUPT: an event (valid or not) with a negative ts, a descriptor with a payload offset below 4, an
+ *              eventNumber outside 0 .. 2^23 - 1 (256 counts are summed in an int32) or an eventTSOverflow outside 0 .. 2^31 - 1.
+ *              _VALID_MISMATCH: the valid bits of a packet do not add up to the eventValid its header states (the int32 4 bytes
+ *              before the payload).  The kernels detect and never interpret.
+ *   workspace  caller-owned, 16-byte aligned, scpose_events_aedat3_workspace_bytes(n_packets) (never 0), the SAME for both calls
+ * Argument errors (null pointers, n_packets < 0 or above 2^31 - 1, h or w outside 1 .. 32768, a misaligned or short workspace)
+ * return -1 with a message before anything is launched.  No allocation, no synchronisation, no atomics on the columns, integer
+ * work only; two runs on the same bytes give bitwise equal outputs. */
+enum { SCPOSE_AEDAT3_CORRUPT = 1, SCPOSE_AEDAT3_VALID_MISMATCH = 2, SCPOSE_AEDAT3_RANGE = 4, SCPOSE_AEDAT3_CAPACITY = 8 };
+int32_t scpose_events_aedat3_workspace_bytes(int64_t n_packets, size_t* bytes);
+int32_t scpose_events_aedat3_count(const uint8_t* file, const int64_t* packets, int64_t n_packets, int64_t* count_status,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+int32_t scpose_events_aedat3_unpack(const uint8_t* file, const int64_t* packets, int64_t n_packets, int32_t h, int32_t w, int32_t rebase,
+                                    int64_t* t, int32_t* x, int32_t* y, int8_t* p, int64_t capacity, int64_t* count_status,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* (ABI 7, additive) The event packets of an AEDAT-4.0 recording on the device (csrc/events_aedat4_read.hip, which states the format):
  * the whole file and one descriptor per event packet -> the four columns, events in file order.  The host reads the IOHeader and
  * walks the packet headers (event_read.parse_aedat4).  Four calls on one workspace, in this order; _measure and _decode only when

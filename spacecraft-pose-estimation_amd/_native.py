@@ -27,6 +27,7 @@ TEXT_CAPACITY = 1
 AEDAT2_RANGE, AEDAT2_TIME = 1, 2
 AEDAT2_LAYOUT_DAVIS, AEDAT2_LAYOUT_V2E = 0, 1
 AEDAT2_READ_RANGE, AEDAT2_READ_CAPACITY = 1, 2
+AEDAT3_CORRUPT, AEDAT3_VALID_MISMATCH, AEDAT3_RANGE, AEDAT3_CAPACITY = 1, 2, 4, 8
 AEDAT4_CORRUPT, AEDAT4_CHECKSUM, AEDAT4_FLATBUFFER, AEDAT4_RANGE, AEDAT4_CAPACITY = 1, 2, 4, 8, 16
 JPEG_GRAY, JPEG_444, JPEG_420 = 0, 1, 2
 JPEG_NOT_CONVERGED, JPEG_CORRUPT = 1, 2
@@ -155,6 +156,10 @@ SYMBOLS = {
     "scpose_events_aedat2_unpack": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_double,
                                               c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_size_t,
                                               c_void_p]),
+    "scpose_events_aedat3_workspace_bytes": (c_int32, [c_int64, POINTER(c_size_t)]),
+    "scpose_events_aedat3_count": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "scpose_events_aedat3_unpack": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "scpose_events_aedat4_workspace_bytes": (c_int32, [c_int64, POINTER(c_size_t)]),
     "scpose_events_aedat4_measure": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "scpose_events_aedat4_decode": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_size_t, c_void_p]),

@@ -266,6 +266,44 @@ extern "C" int32_t scpose_events_aedat2_unpack(const uint8_t* records, int64_t n
                                      capacity, count_status, static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
 }
 
+// n_packets in range, the workspace, then the pointers: the file and the descriptors are needed when there are packets
+static int32_t aedat3_args_ok(const char* who, int64_t n_packets, const void* file, const void* packets, const void* count_status,
+                              const void* workspace, size_t workspace_bytes) {
+  SCP_REQUIRE(n_packets >= 0 && n_packets <= 0x7fffffff, "%s: n_packets=%lld (0 .. 2^31 - 1)", who, (long long)n_packets);
+  if (int32_t rc = workspace_ok(who, workspace, workspace_bytes, events_aedat3_workspace_bytes(n_packets), 16)) return rc;
+  SCP_REQUIRE(count_status && (n_packets == 0 || (file && packets)), "%s: null argument", who);
+  SCP_REQUIRE(aligned(packets, 8) && aligned(count_status, 8), "%s: packets and count_status must be 8-byte aligned", who);
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_events_aedat3_workspace_bytes(int64_t n_packets, size_t* bytes) {
+  SCP_REQUIRE(bytes, "events_aedat3_workspace_bytes: null argument");
+  SCP_REQUIRE(n_packets >= 0 && n_packets <= 0x7fffffff, "events_aedat3_workspace_bytes: n_packets=%lld (0 .. 2^31 - 1)",
+              (long long)n_packets);
+  *bytes = events_aedat3_workspace_bytes(n_packets);
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_events_aedat3_count(const uint8_t* file, const int64_t* packets, int64_t n_packets, int64_t* count_status,
+                                              void* workspace, size_t workspace_bytes, void* stream) {
+  if (int32_t rc = aedat3_args_ok("events_aedat3_count", n_packets, file, packets, count_status, workspace, workspace_bytes)) return rc;
+  return events_aedat3_count_launch(file, packets, n_packets, count_status, static_cast<uint8_t*>(workspace),
+                                    static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t scpose_events_aedat3_unpack(const uint8_t* file, const int64_t* packets, int64_t n_packets, int32_t h, int32_t w,
+                                               int32_t rebase, int64_t* t, int32_t* x, int32_t* y, int8_t* p, int64_t capacity,
+                                               int64_t* count_status, void* workspace, size_t workspace_bytes, void* stream) {
+  // x and y are 15-bit fields
+  SCP_REQUIRE(h >= 1 && h <= 32768 && w >= 1 && w <= 32768, "events_aedat3_unpack: sensor %dx%d (HxW) not supported: each 1 .. 32768",
+              h, w);
+  SCP_REQUIRE(capacity >= 0, "events_aedat3_unpack: capacity=%lld", (long long)capacity);
+  SCP_REQUIRE((t && x && y && p) || capacity == 0, "events_aedat3_unpack: null argument");
+  if (int32_t rc = aedat3_args_ok("events_aedat3_unpack", n_packets, file, packets, count_status, workspace, workspace_bytes)) return rc;
+  return events_aedat3_unpack_launch(file, packets, n_packets, h, w, rebase != 0, t, x, y, p, capacity, count_status,
+                                     static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
 // n_packets in range, the workspace, then the pointers: `a` and `b` are needed when there are packets, `result` always
 static int32_t aedat4_args_ok(const char* who, int64_t n_packets, const void* a, const void* b, const void* result,
                               const void* workspace, size_t workspace_bytes) {

@@ -354,6 +354,13 @@ size_t events_aedat2_unpack_workspace_bytes(int64_t n);
 int32_t events_aedat2_unpack_launch(const uint8_t* records, int64_t n, int h, int w, int layout, int flip_x, int flip_y, int unwrap,
                                     double t_div, int64_t* t, int32_t* x, int32_t* y, int8_t* p, int64_t capacity, int64_t* count_status,
                                     uint8_t* ws, hipStream_t stream);
+// events_aedat3_read.hip: the polarity packets of an AEDAT-3.1 file -> (t, x, y, p)
+size_t events_aedat3_workspace_bytes(int64_t n_packets);
+int32_t events_aedat3_count_launch(const uint8_t* file, const int64_t* packets, int64_t n, int64_t* count_status, uint8_t* ws,
+                                   hipStream_t stream);
+int32_t events_aedat3_unpack_launch(const uint8_t* file, const int64_t* packets, int64_t n, int h, int w, int rebase, int64_t* t,
+                                    int32_t* x, int32_t* y, int8_t* p, int64_t capacity, int64_t* count_status, uint8_t* ws,
+                                    hipStream_t stream);
 // events_aedat4_read.hip: the event packets of an AEDAT-4.0 file -> (t, x, y, p)
 size_t events_aedat4_workspace_bytes(int64_t n_packets);
 int32_t events_aedat4_measure_launch(const uint8_t* file, const int64_t* packets, int64_t n, int64_t* total_status, uint8_t* ws,

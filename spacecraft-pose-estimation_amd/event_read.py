@@ -1,4 +1,4 @@
-"""Device columns from AEDAT-2.0 and AEDAT-4.0 event files: the mirror of event_write.py.
+"""Device columns from AEDAT-2.0, AEDAT-3.1 and AEDAT-4.0 event files: the mirror of event_write.py.
 
 An AEDAT-2.0 file is a text header, the run of lines that start with '#' and end with '\\n', whose first line is
 `#!AER-DAT2.0`, followed by 8-byte records of two big-endian 32-bit words (address, time stamp).  The header is split off on the
@@ -12,6 +12,14 @@ position of the file data table, an XML node that names the streams), then packe
 flatbuffer that is raw or one LZ4 frame.  parse_aedat4 reads the header and walks the packet headers on the host (eight bytes
 per packet); read_events_aedat4 uploads the file in one piece and the payloads of the event streams are decompressed and
 unpacked on the device (csrc/events_aedat4_read.hip, which states the format, through ops.unpack_events_aedat4).
+
+An AEDAT-3.1 file (a cAER / early DV recording of a DAVIS or DVS128 camera) is a '#' text header with '\\r\\n' line ends that
+starts with `#!AER-DAT3.1` and ends with `#!END-HEADER`, then packets: a 28-byte header and eventCapacity * eventSize payload bytes.
+parse_aedat3 reads the text and walks the packet headers on the host; read_events_aedat3 uploads the file in one piece and the
+polarity packets of one source are unpacked on the device (csrc/events_aedat3_read.hip, which states the format, through
+ops.unpack_events_aedat3).  Such a file usually carries the .aedat name: callers sniff it (is_aedat3_path) before the AEDAT-2.0
+entry points, which still refuse it by name, as parse_aedat4 does.  AEDAT-3.0, formats other than RAW and the decoding of frame,
+IMU and special events stay out; there is no 3.1 writer.
 """
 import re
 import struct
@@ -256,4 +264,184 @@ def read_events_aedat4(path_or_bytes, hw=None, stream=None, rebase=True, verify=
     t, x, y, p, info = ops.unpack_events_aedat4(buf, packets, head.compression, hw, rebase=rebase, verify=verify)
     info.update(compression=int(head.compression), hw=(int(hw[0]), int(hw[1])), streams=tuple(ids),
                 trailing_bytes=int(head.trailing_bytes))
+    return t, x, y, p, info
+
+
+# ------------------------------------------------------------------ AEDAT-3.1
+AEDAT3_MAGIC = b"#!AER-DAT3."
+AEDAT3_PACKET_HEADER = 28
+AEDAT3_TYPES = {0: "special", 1: "polarity", 2: "frame", 3: "IMU6", 4: "IMU9"}
+AEDAT3_POLARITY = 1
+# (prefix of the '#Source' name, (height, width)); the longest prefix that matches wins
+AEDAT3_SENSORS = (("DVS128", (128, 128)), ("DAVIS240", (180, 240)), ("DAVIS346", (260, 346)), ("DAVIS640", (480, 640)))
+
+
+class UnsupportedAedat3(ValueError):
+    """An AEDAT-3.1 file this reader does not take: AEDAT-3.0, a format other than RAW, a header that does not end, a packet
+    header that contradicts itself, a source whose sensor size is not known, several polarity sources and none chosen."""
+
+
+class Aedat3Header:
+    """What parse_aedat3 found: sources {id: name}, the packet table as NumPy arrays (packet_offset: payload offset in the file,
+    packet_events: eventNumber, packet_valid: eventValid, packet_overflow: eventTSOverflow, packet_source, packet_type) with one
+    row per packet of ANY type, other_packets {type: count} of the packets that are not polarity packets, trailing_bytes."""
+
+    def __init__(self, sources, packet_offset, packet_events, packet_valid, packet_overflow, packet_source, packet_type, other_packets,
+                 trailing_bytes):
+        self.sources = sources
+        self.packet_offset = packet_offset
+        self.packet_events = packet_events
+        self.packet_valid = packet_valid
+        self.packet_overflow = packet_overflow
+        self.packet_source = packet_source
+        self.packet_type = packet_type
+        self.other_packets = other_packets
+        self.trailing_bytes = trailing_bytes
+
+    def polarity_sources(self):
+        """The ids of the sources that carry polarity packets, ascending."""
+        return sorted(set(int(s) for s in self.packet_source[self.packet_type == AEDAT3_POLARITY]))
+
+
+def is_aedat3_path(path):
+    """True for a path that ends in .aedat3 or a file whose first bytes are '#!AER-DAT3.' (a 3.1 recording usually carries the
+    .aedat name of a 2.0 one: look here first)."""
+    if str(path).lower().endswith(".aedat3"):
+        return True
+    try:
+        with open(path, "rb") as f:
+            return f.read(len(AEDAT3_MAGIC)) == AEDAT3_MAGIC
+    except OSError:
+        return False
+
+
+def aedat3_sensor_hw(name):
+    """(height, width) of the camera a '#Source' line names: DVS128, DAVIS240*, DAVIS346*, DAVIS640; None for any other name."""
+    for prefix, hw in AEDAT3_SENSORS:
+        if str(name).strip().upper().startswith(prefix):
+            return hw
+    return None
+
+
+def _aedat3_header(buf):
+    """The text header of an AEDAT-3.1 file -> ({source id: name}, offset of the first packet)."""
+    first = bytes(buf[:64]).split(b"\n", 1)[0].rstrip(b"\r")
+    if not first.startswith(b"#!AER-DAT"):
+        raise UnsupportedAedat3("not an AEDAT-3.1 file: the first bytes are %r" % bytes(buf[:14]))
+    if first == b"#!AER-DAT3.0":
+        raise UnsupportedAedat3("AEDAT-3.0 is not supported (only AEDAT-3.1 is): its packet header differs")
+    if first != b"#!AER-DAT3.1":
+        raise UnsupportedAedat3("not an AEDAT-3.1 file: the first line is %r" % first[:40])
+    head = bytes(buf[:MAX_HEADER_BYTES])
+    mark = b"#!END-HEADER\r\n"
+    end = head.find(b"\r\n" + mark)
+    if end < 0:
+        raise UnsupportedAedat3("no '#!END-HEADER' line in the first %d bytes: not an AEDAT-3.1 file" % MAX_HEADER_BYTES)
+    sources, fmt = {}, None
+    for line in head[:end].split(b"\r\n")[1:]:
+        if not line.startswith(b"#"):
+            raise UnsupportedAedat3("a header line does not start with '#': %r" % line[:40])
+        text = line.decode("latin-1")
+        if text.startswith("#Format:"):
+            fmt = text[len("#Format:"):].strip()
+        m = re.match(r"#Source\s+(-?\d+):\s*(.*)$", text)
+        if m:
+            sources[int(m.group(1))] = m.group(2).strip()
+    if fmt != "RAW":
+        raise UnsupportedAedat3("the format is %s: only '#Format: RAW' is read" % ("%r" % fmt if fmt is not None else "not stated"))
+    if not sources:
+        raise UnsupportedAedat3("the header names no '#Source <id>: <name>'")
+    return sources, end + 2 + len(mark)
+
+
+def parse_aedat3(data):
+    """The header and packet table of an AEDAT-3.1 file (its bytes) -> Aedat3Header.  Packets run to the end of the file; a last
+    packet whose header or payload is cut off is dropped and reported as trailing_bytes, as parse_aedat4 does.  Packets that are not
+    polarity packets (special, frame, IMU6, IMU9, anything else) are stepped over by eventCapacity * eventSize and counted per type.
+    Raises UnsupportedAedat3 for AEDAT-3.0, a '#Format:' other than RAW, a header without '#!END-HEADER' in its first 1 MiB, and,
+    naming the packet's index, for a packet header with a negative field, eventSize <= 0, eventNumber > eventCapacity, eventValid >
+    eventNumber, a payload size beyond int64, or a polarity packet whose eventSize is not 8 or whose eventTSOffset is not 4."""
+    buf = data if isinstance(data, (bytes, bytearray, memoryview)) else bytes(data)       # a memoryview is walked, not copied
+    sources, pos = _aedat3_header(buf)
+    end = len(buf)
+    offs, nums, valids, overs, srcs, types, other, trailing = [], [], [], [], [], [], {}, 0
+    k = 0
+    while pos < end:
+        if pos + AEDAT3_PACKET_HEADER > end:
+            trailing = end - pos
+            break
+        etype, source, size, ts_at, overflow, capacity, number, valid = struct.unpack_from("<hhiiiiii", buf, pos)
+        fields = (("eventType", etype), ("eventSource", source), ("eventSize", size), ("eventTSOffset", ts_at),
+                  ("eventTSOverflow", overflow), ("eventCapacity", capacity), ("eventNumber", number), ("eventValid", valid))
+        for name, value in fields:
+            if value < 0:
+                raise UnsupportedAedat3("packet %d at byte %d: %s is negative (%d)" % (k, pos, name, value))
+        if size <= 0:
+            raise UnsupportedAedat3("packet %d at byte %d: eventSize is %d" % (k, pos, size))
+        if number > capacity:
+            raise UnsupportedAedat3("packet %d at byte %d: eventNumber %d exceeds eventCapacity %d" % (k, pos, number, capacity))
+        if valid > number:
+            raise UnsupportedAedat3("packet %d at byte %d: eventValid %d exceeds eventNumber %d" % (k, pos, valid, number))
+        payload = capacity * size                                        # Python integers: the product itself cannot wrap
+        if payload > (1 << 63) - 1:
+            raise UnsupportedAedat3("packet %d at byte %d: eventCapacity * eventSize does not fit in int64" % (k, pos))
+        if etype == AEDAT3_POLARITY and (size != 8 or ts_at != 4):
+            raise UnsupportedAedat3("packet %d at byte %d: a polarity packet with eventSize %d and eventTSOffset %d (8 and 4 are read)"
+                                    % (k, pos, size, ts_at))
+        if pos + AEDAT3_PACKET_HEADER + payload > end:
+            trailing = end - pos
+            break
+        offs.append(pos + AEDAT3_PACKET_HEADER)
+        nums.append(number)
+        valids.append(valid)
+        overs.append(overflow)
+        srcs.append(source)
+        types.append(etype)
+        if etype != AEDAT3_POLARITY:
+            other[etype] = other.get(etype, 0) + 1
+        pos += AEDAT3_PACKET_HEADER + payload
+        k += 1
+    i64 = lambda v: np.asarray(v, dtype=np.int64)
+    return Aedat3Header(sources, i64(offs), i64(nums), i64(valids), i64(overs), np.asarray(srcs, dtype=np.int32),
+                        np.asarray(types, dtype=np.int32), other, int(trailing))
+
+
+def read_events_aedat3(path_or_bytes, hw=None, source=None, rebase=True, device=None):
+    """An AEDAT-3.1 file (a path, or its bytes) -> (t int64, x int32, y int32, p int8, info) on `device` (default: the current
+    one), the valid polarity events of one source in file order, t in microseconds.  hw defaults to the size of the camera the
+    '#Source' line names (aedat3_sensor_hw); source: the source id, needed only when several sources carry polarity packets;
+    rebase: subtract the first event's time stamp, as the AEDAT-4.0 reader does.  The file is uploaded once and the device gets one
+    descriptor per polarity packet of the source (csrc/events_aedat3_read.hip through ops.unpack_events_aedat3).  info: n_events,
+    n_packets, n_invalid (events dropped because their valid bit is clear), t0, n_backward, n_out_of_range, sources (the ids
+    read), other_packets {type: count}, trailing_bytes, hw.  Raises UnsupportedAedat3 (parse_aedat3, the source, the size) and
+    ValueError (ops.unpack_events_aedat3).  Frame, IMU and special events are counted and not decoded."""
+    import torch
+    from . import ops
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        host = np.frombuffer(path_or_bytes, dtype=np.uint8)
+    else:
+        host = np.fromfile(path_or_bytes, dtype=np.uint8)
+    head = parse_aedat3(memoryview(host))
+    carrying = head.polarity_sources()
+    if source is None:
+        if len(carrying) > 1:
+            raise UnsupportedAedat3("sources %s all carry polarity packets: give source, one of them (%s)" % (
+                ", ".join(str(s) for s in carrying), ", ".join("%d: %s" % (s, head.sources.get(s, "?")) for s in carrying)))
+        sid = carrying[0] if carrying else min(head.sources)
+    else:
+        sid = int(source)
+        if sid not in head.sources and sid not in carrying:
+            raise UnsupportedAedat3("no source %r: the header names %s" % (source, sorted(head.sources.items())))
+    if hw is None:
+        hw = aedat3_sensor_hw(head.sources.get(sid, ""))
+        if hw is None:
+            raise UnsupportedAedat3("source %d is %r, a camera whose sensor size is not known here (DVS128, DAVIS240, DAVIS346, "
+                                    "DAVIS640 are): give the size, hw = (height, width)" % (sid, head.sources.get(sid)))
+    keep = (head.packet_type == AEDAT3_POLARITY) & (head.packet_source == sid)
+    packets = np.stack([head.packet_offset[keep], head.packet_events[keep], head.packet_overflow[keep]], axis=1)
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    buf = torch.from_numpy(host.copy() if not host.flags.writeable else host).to(dev)
+    t, x, y, p, info = ops.unpack_events_aedat3(buf, packets, hw, rebase=rebase)
+    info.update(n_invalid=int(packets[:, 1].sum()) - info["n_events"], sources=(sid,), other_packets=dict(head.other_packets),
+                trailing_bytes=int(head.trailing_bytes), hw=(int(hw[0]), int(hw[1])))
     return t, x, y, p, info

@@ -89,7 +89,9 @@ def read_events_device(path, device=None, host_csv=False, hw=None, aedat_layout=
 
     A path that ends in .aedat4, or a file whose first 14 bytes are the AEDAT-4.0 version line, is looked at first and goes
     through event_read.read_events_aedat4 (rebased time stamps in microseconds): hw defaults to the size the file states, and
-    every flag that describes text or a time-stamp unit is refused by name."""
+    every flag that describes text or a time-stamp unit is refused by name.  A path that ends in .aedat3, or a file that starts
+    with '#!AER-DAT3.', is an AEDAT-3.1 recording and is looked at before the AEDAT-2.0 test (it usually carries the .aedat name):
+    event_read.read_events_aedat3 with the same rules, hw defaulting to the size of the camera the file names."""
     import torch
     from . import event_read, ops
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -98,6 +100,14 @@ def read_events_device(path, device=None, host_csv=False, hw=None, aedat_layout=
             if on:
                 raise ValueError("%s describes a text file and cannot be used with the AEDAT-4.0 input %s" % (name, path))
         t, x, y, _, info = event_read.read_events_aedat4(path, hw=hw, device=dev)
+        if info["n_backward"] > 0:
+            raise ValueError("the event stream must be sorted by time")
+        return t, x, y
+    if event_read.is_aedat3_path(path):
+        for name, on in [("host_csv", host_csv)] + sorted(csv_flags.items()):
+            if on:
+                raise ValueError("%s describes a text file and cannot be used with the AEDAT-3.1 input %s" % (name, path))
+        t, x, y, _, info = event_read.read_events_aedat3(path, hw=hw, device=dev)
         if info["n_backward"] > 0:
             raise ValueError("the event stream must be sorted by time")
         return t, x, y
@@ -196,6 +206,14 @@ def scene_aedat4(scene_dir):
     return os.path.join(scene_dir, found[0]) if len(found) == 1 else None
 
 
+def scene_aedat3(scene_dir):
+    """The scene's one AEDAT-3.1 recording among its *.aedat and *.aedat3 files, None when it has none or several."""
+    from . import event_read
+    found = sorted(f for f in os.listdir(scene_dir) if f.lower().endswith((".aedat", ".aedat3")))
+    found = [f for f in found if event_read.is_aedat3_path(os.path.join(scene_dir, f))]
+    return os.path.join(scene_dir, found[0]) if len(found) == 1 else None
+
+
 def render_scene(scene_dir, hw, K=None, dist=None, interval=10000.0, full_scale=2, write_distorted=True, device=None,
                  chunk_frames=256, exposure=None, host_csv=False, aedat_layout="davis", **csv_flags):
     """scene_dir/events.csv -> scene_dir/event-frames/<t>.bmp (undistorted when K / dist are given) and, with
@@ -205,7 +223,8 @@ def render_scene(scene_dir, hw, K=None, dist=None, interval=10000.0, full_scale=
     exposure: None (DURATION over `interval`) or ops.render_events keyword arguments (exposure_kwargs) that replace it.
     A scene that holds events.aedat (AEDAT-2.0, address layout aedat_layout, sensor size hw) and no events.csv is rendered from
     that file; when both exist, events.csv wins.  A scene with neither, but exactly one *.aedat4 file (an AEDAT-4.0 recording), is
-    rendered from that file.  Returns the list of frame names."""
+    rendered from that file; failing that, exactly one AEDAT-3.1 recording (*.aedat or *.aedat3 that starts with '#!AER-DAT3.'),
+    with hw as the sensor size.  Returns the list of frame names."""
     import torch
     from . import ops
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -214,6 +233,8 @@ def render_scene(scene_dir, hw, K=None, dist=None, interval=10000.0, full_scale=
         src = os.path.join(scene_dir, "events.aedat")
     elif not os.path.exists(src) and scene_aedat4(scene_dir) is not None:
         src = scene_aedat4(scene_dir)
+    elif not os.path.exists(src) and scene_aedat3(scene_dir) is not None:
+        src = scene_aedat3(scene_dir)
     t, x, y = read_events_device(src, dev, host_csv=host_csv, hw=hw, aedat_layout=aedat_layout, **csv_flags)
     out_dir = os.path.join(scene_dir, "event-frames"); dis_dir = os.path.join(scene_dir, "event-frames-distorted")
     os.makedirs(out_dir, exist_ok=True)

@@ -563,6 +563,65 @@ def unpack_events_aedat2(records, hw, layout="davis", flip_x=True, flip_y=True, 
     return t[:rows].clone(), x[:rows].clone(), y[:rows].clone(), p[:rows].clone(), info
 
 
+AEDAT3_MAX_PACKET_EVENTS = (1 << 23) - 1
+
+
+def unpack_events_aedat3(buf, packets, hw, rebase=True):
+    """The polarity packets of an AEDAT-3.1 file -> (t int64, x int32, y int32, p int8, info), the valid events in file order,
+    unpacked on the device (csrc/events_aedat3_read.hip), in the dtypes render_events takes.  buf: a uint8 device tensor, the whole
+    file.  packets: (n, 3) int64, payload offset, eventNumber and eventTSOverflow of each polarity packet
+    (event_read.parse_aedat3 finds them).  hw = (height, width) of the sensor.  rebase: t minus the first event's t.  One small
+    read-back sizes the columns, a second brings the counters.  info: n_events, n_packets, t0, n_backward, n_out_of_range.  Raises
+    ValueError for a negative time stamp, valid bits that contradict the packet's header and an event outside the sensor."""
+    if not torch.is_tensor(buf) or buf.dtype != torch.uint8:
+        raise ValueError("unpack_events_aedat3: the file must be a uint8 device tensor")
+    _need_cuda(buf)
+    buf = buf.contiguous().view(-1)
+    pk = np.ascontiguousarray(packets, dtype=np.int64).reshape(-1, 3)
+    n = int(pk.shape[0])
+    if n and (pk.min() < 0 or int(pk[:, 0].min()) < 28 or int(pk[:, 1].max()) > AEDAT3_MAX_PACKET_EVENTS or
+              int((pk[:, 0] + 8 * pk[:, 1]).max()) > buf.numel()):
+        if pk.min() >= 0 and int(pk[:, 1].max()) > AEDAT3_MAX_PACKET_EVENTS:
+            raise ValueError("unpack_events_aedat3: a packet holds %d events: 2^23 or more in one packet are not read" % int(pk[:, 1].max()))
+        raise ValueError("unpack_events_aedat3: a packet does not lie inside the %d bytes of the file" % buf.numel())
+    if n and int(pk[:, 2].max()) > 0x7FFFFFFF:
+        raise ValueError("unpack_events_aedat3: eventTSOverflow %d is not an int32" % int(pk[:, 2].max()))
+    h, w = int(hw[0]), int(hw[1])
+    dev = buf.device
+    lib = nat.lib()
+    ws = _query_bytes("events_aedat3_workspace_bytes", n)
+    with torch.cuda.device(dev):
+        work = torch.empty(ws, dtype=torch.uint8, device=dev)
+        cs = torch.empty(6, dtype=torch.int64, device=dev)
+        pkd = torch.from_numpy(pk).to(dev)
+        nat.check(lib.scpose_events_aedat3_count(_ptr(buf), _ptr(pkd), n, _ptr(cs), _ptr(work), ws, _stream()), "events_aedat3_count")
+        rows, status, t0 = cs.tolist()[:3]                          # small read-back: the columns' size
+        _aedat3_raise(status, hw)
+        t, x, y, p = _empty_event_columns(int(rows), dev)
+        nat.check(lib.scpose_events_aedat3_unpack(_ptr(buf), _ptr(pkd), n, h, w, int(bool(rebase)), _ptr(t), _ptr(x), _ptr(y), _ptr(p),
+                                                  int(rows), _ptr(cs), _ptr(work), ws, _stream()), "events_aedat3_unpack")
+        got = cs.tolist()                                           # the counters
+    _aedat3_raise(got[1], hw)
+    return t, x, y, p, {"n_events": int(rows), "n_packets": n, "t0": int(t0) if rows else 0, "n_backward": int(got[3]),
+                        "n_out_of_range": int(got[4])}
+
+
+def _aedat3_raise(status, hw):
+    """ValueError for the status bits of the AEDAT-3.1 kernels."""
+    if status & nat.AEDAT3_CORRUPT:
+        raise ValueError("unpack_events_aedat3: a polarity event has a negative time stamp, or a packet descriptor is out of range "
+                         "(status CORRUPT)")
+    if status & nat.AEDAT3_VALID_MISMATCH:
+        raise ValueError("unpack_events_aedat3: the valid bits of a packet's events do not add up to the eventValid its header "
+                         "states (status VALID_MISMATCH)")
+    if status & nat.AEDAT3_RANGE:
+        raise ValueError("unpack_events_aedat3: an event lies outside the %d x %d sensor (status RANGE)" % (int(hw[1]), int(hw[0])))
+    if status & nat.AEDAT3_CAPACITY:
+        raise nat.NativeError("unpack_events_aedat3: the columns are shorter than the events counted (status CAPACITY)")
+    if status != 0:
+        raise nat.NativeError("unpack_events_aedat3: status %d" % status)
+
+
 def unpack_events_aedat4(buf, packets, compression, hw, rebase=True, verify=True):
     """The event packets of an AEDAT-4.0 file -> (t int64, x int32, y int32, p int8, info), events in file order, decompressed
     and unpacked on the device (csrc/events_aedat4_read.hip), in the dtypes render_events takes.  buf: a uint8 device tensor, the

@@ -1,0 +1,254 @@
+"""AEDAT-3.1 on the host: event_read.parse_aedat3 against the restated reader (tests/events_aedat3_restated.py) on files from
+tests/aedat3_stream_writer.py, every file it refuses with its message, the camera-name table, the entry points of the other two
+versions unmoved, and scpose_events_aedat3_* through the C ABI: argument errors answered before anything is launched.  No device."""
+import ctypes
+import importlib.util
+import os
+import struct
+from importlib import import_module
+
+import numpy as np
+import pytest
+
+import aedat3_stream_writer as W
+import aedat4_stream_writer as W4
+import events_aedat3_restated as R
+
+er = import_module("spacecraft-pose-estimation_amd.event_read")
+nat = import_module("spacecraft-pose-estimation_amd._native")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HW = (260, 346)
+
+
+def same_table(data):
+    """parse_aedat3's packet table equals the restated walk; -> (header, restated table)."""
+    head = er.parse_aedat3(data)
+    sources, table, other, trailing = R.packets(data)
+    assert head.sources == sources and head.other_packets == other and head.trailing_bytes == trailing
+    assert len(head.packet_offset) == len(table)
+    for name, col in (("packet_type", 0), ("packet_source", 1), ("packet_overflow", 2), ("packet_events", 3), ("packet_valid", 4),
+                      ("packet_offset", 5)):
+        assert [int(v) for v in getattr(head, name)] == [row[col] for row in table], name
+    assert head.packet_offset.dtype == head.packet_events.dtype == head.packet_overflow.dtype == np.int64
+    return head, table
+
+
+def test_one_packet():
+    cols = W.random_events(70, HW, 0)
+    data = W.write_aedat3(W.split(cols, (70,)))
+    head, table = same_table(data)
+    assert head.sources == {1: "DAVIS346"} and len(table) == 1 and head.trailing_bytes == 0 and head.other_packets == {}
+    assert int(head.packet_offset[0]) == len(W.header()) + 28 and int(head.packet_events[0]) == 70
+    assert head.polarity_sources() == [1]
+    assert er.parse_aedat3(memoryview(data)).packet_offset.tolist() == head.packet_offset.tolist()
+
+
+def test_300_packets():
+    rng = np.random.default_rng(1)
+    counts = rng.integers(0, 12, 300)
+    cols = W.random_events(int(counts.sum()), HW, 1)
+    head, table = same_table(W.write_aedat3(W.split(cols, counts)))
+    assert len(table) == 300 and head.packet_events.tolist() == counts.tolist()
+
+
+def test_other_packet_types_are_stepped_over_and_counted():
+    cols = W.random_events(60, HW, 2)
+    packets = W.split(cols, (10, 20, 30, 0, 0, 0), fillers=True) + [W.filler_packet(W.IMU9, 1, 2), W.filler_packet(9, 1, 3, size=5)]
+    head, table = same_table(W.write_aedat3(packets))
+    assert head.other_packets == {W.SPECIAL: 2, W.FRAME: 2, W.IMU6: 2, W.IMU9: 1, 9: 1}
+    assert head.packet_events[head.packet_type == 1].tolist() == [10, 20, 30, 0, 0, 0]
+
+
+def test_two_sources():
+    a, b = W.random_events(30, HW, 3), W.random_events(20, (180, 240), 4)
+    packets = [W.split(a, (30,), source=1)[0], W.split(b, (20,), source=2)[0], W.filler_packet(W.IMU6, 2, 1)]
+    head, _ = same_table(W.write_aedat3(packets, sources={1: "DAVIS346", 2: "DAVIS240C"}))
+    assert head.sources == {1: "DAVIS346", 2: "DAVIS240C"} and head.polarity_sources() == [1, 2]
+    assert head.packet_source.tolist() == [1, 2, 2]
+
+
+def test_capacity_above_number_with_a_garbage_tail():
+    cols = W.random_events(25, HW, 5)
+    tail = bytes(range(1, 81))                                        # ten events' worth that are not the packet's
+    packets = [W.polarity_packet(*(c[:10] for c in cols), tail=tail), W.polarity_packet(*(c[10:] for c in cols))]
+    head, table = same_table(W.write_aedat3(packets))
+    assert head.packet_events.tolist() == [10, 15]
+    assert int(head.packet_offset[1]) == int(head.packet_offset[0]) + 80 + 80 + 28
+
+
+@pytest.mark.parametrize("cut", [1, 27, 28, 29, "payload - 1"])
+def test_a_cut_off_tail_is_dropped_and_reported(cut):
+    cols = W.random_events(50, HW, 6)
+    whole = W.write_aedat3(W.split([c[:20] for c in cols], (20,)))
+    last = W.split([c[20:] for c in cols], (30,))[0]
+    keep = 28 + 30 * 8 - 1 if cut == "payload - 1" else cut           # bytes of the last packet that are still there
+    head, table = same_table(whole + last[:keep])
+    assert len(table) == 1 and head.trailing_bytes == keep
+    head, table = same_table(whole + last)
+    assert len(table) == 2 and head.trailing_bytes == 0
+
+
+def test_header_lines_with_extra_comment_lines():
+    extra = (b"#-Source 1: a line that is not a source", b"# free text: #!END-HEADER is not on a line of its own here", b"#")
+    cols = W.random_events(5, HW, 7)
+    data = W.write_aedat3(W.split(cols, (5,)), sources={0: "DVS128", 7: "DAVIS346B rev 2"}, extra=extra)
+    head, _ = same_table(data)
+    assert head.sources == {0: "DVS128", 7: "DAVIS346B rev 2"}
+    assert int(head.packet_offset[0]) == len(W.header({0: "DVS128", 7: "DAVIS346B rev 2"}, extra=extra)) + 28
+
+
+def refused(data, words, **kw):
+    with pytest.raises(ValueError):
+        R.read(data, **kw) if kw else R.packets(data)
+    with pytest.raises(er.UnsupportedAedat3, match=words):
+        er.parse_aedat3(data)
+
+
+def test_refusals():
+    cols = W.random_events(12, HW, 8)
+    one = W.split(cols, (12,))
+    refused(W.write_aedat3(one, version=b"3.0"), "AEDAT-3.0 is not supported")
+    refused(W.write_aedat3(one, fmt=b"SERIALIZED"), "'SERIALIZED': only '#Format: RAW' is read")
+    refused(W.write_aedat3(one, fmt=None), "not stated")
+    refused(W.write_aedat3(one, end=False), "no '#!END-HEADER' line in the first 1048576 bytes")
+    refused(W.write_aedat3(one, extra=(b"#" + b"x" * (1 << 20),)), "no '#!END-HEADER' line")
+    good = W.filler_packet(W.IMU6, 1, 2)
+    refused(W.write_aedat3([good, W.polarity_packet(*cols, capacity=11)]), "packet 1 at byte .*eventNumber 12 exceeds eventCapacity 11")
+    refused(W.write_aedat3([W.polarity_packet(*cols, event_valid=13)]), "packet 0 at byte .*eventValid 13 exceeds eventNumber 12")
+    refused(W.write_aedat3([good, good, W.polarity_packet(*cols, size=16)]), "packet 2 at byte .*eventSize 16 and eventTSOffset 4")
+    refused(W.write_aedat3([W.polarity_packet(*cols, ts_offset=0)]), "packet 0 at byte .*eventSize 8 and eventTSOffset 0")
+    refused(W.write_aedat3([W.packet(W.FRAME, 1, b"", 0, size=0)]), "packet 0 at byte .*eventSize is 0")
+    at = len(W.header())
+    for field, (offset, fmt) in {"eventType": (0, "<h"), "eventSource": (2, "<h"), "eventSize": (4, "<i"), "eventTSOffset": (8, "<i"),
+                                 "eventTSOverflow": (12, "<i"), "eventCapacity": (16, "<i"), "eventNumber": (20, "<i"),
+                                 "eventValid": (24, "<i")}.items():
+        data = bytearray(W.write_aedat3(one))
+        struct.pack_into(fmt, data, at + offset, -3)
+        refused(bytes(data), "packet 0 at byte %d: %s is negative \\(-3\\)" % (at, field))
+    with pytest.raises(er.UnsupportedAedat3, match="not an AEDAT-3.1 file"):
+        er.parse_aedat3(b"#!AER-DAT2.0\r\n" + b"\0" * 40)
+    assert not issubclass(er.UnsupportedAedat3, er.UnsupportedAedat) and issubclass(er.UnsupportedAedat3, ValueError)
+
+
+class _NoDevice(Exception):
+    pass
+
+
+def test_refusals_of_the_reader_come_before_any_device_work(monkeypatch):
+    """An unknown camera without hw and two polarity sources without `source` are refused by read_events_aedat3 on the host."""
+    ops = import_module("spacecraft-pose-estimation_amd.ops")
+
+    def no_device(*a, **k):
+        raise _NoDevice()
+    monkeypatch.setattr(ops, "unpack_events_aedat3", no_device)
+    cols = W.random_events(12, HW, 9)
+    data = W.write_aedat3(W.split(cols, (12,)), sources={1: "eDVS4337"})
+    with pytest.raises(ValueError):
+        R.read(data)
+    with pytest.raises(er.UnsupportedAedat3, match="source 1 is 'eDVS4337'.*give the size, hw = \\(height, width\\)"):
+        er.read_events_aedat3(data)
+    two = W.write_aedat3(W.split(cols, (12,), source=1) + W.split(cols, (12,), source=4), sources={1: "DAVIS346", 4: "DAVIS240C"})
+    with pytest.raises(ValueError):
+        R.read(two)
+    with pytest.raises(er.UnsupportedAedat3, match="sources 1, 4 all carry polarity packets: give source"):
+        er.read_events_aedat3(two)
+    with pytest.raises(er.UnsupportedAedat3, match="no source 3"):
+        er.read_events_aedat3(two, source=3)
+
+
+@pytest.mark.parametrize("name, hw", [("DVS128", (128, 128)), ("DAVIS240A", (180, 240)), ("DAVIS240B", (180, 240)),
+                                      ("DAVIS240C", (180, 240)), ("DAVIS240", (180, 240)), ("DAVIS346", (260, 346)),
+                                      ("DAVIS346B", (260, 346)), ("DAVIS346Cbsi", (260, 346)), ("davis346", (260, 346)),
+                                      ("DAVIS640", (480, 640)), ("DAVIS128", None), ("DVS132S", None), ("eDVS4337", None),
+                                      ("DAVIS", None), ("", None)])
+def test_source_name_table(name, hw):
+    assert er.aedat3_sensor_hw(name) == hw == R.sensor_hw(name)
+
+
+def test_sniffing(tmp_path):
+    cols = W.random_events(5, HW, 10)
+    data = W.write_aedat3(W.split(cols, (5,)))
+    (tmp_path / "rec.aedat").write_bytes(data)
+    (tmp_path / "empty.aedat3").write_bytes(b"")
+    (tmp_path / "two.aedat").write_bytes(b"#!AER-DAT2.0\r\n")
+    (tmp_path / "four.aedat4").write_bytes(W4.MAGIC)
+    assert er.AEDAT3_MAGIC == b"#!AER-DAT3."
+    assert er.is_aedat3_path(tmp_path / "rec.aedat") and er.is_aedat3_path(tmp_path / "empty.aedat3")
+    assert er.is_aedat3_path(str(tmp_path / "missing.AEDAT3")) and not er.is_aedat3_path(tmp_path / "missing.aedat")
+    assert not er.is_aedat3_path(tmp_path / "two.aedat") and not er.is_aedat3_path(tmp_path / "four.aedat4")
+    assert er.is_aedat_path(tmp_path / "rec.aedat") and not er.is_aedat4_path(tmp_path / "rec.aedat")    # as before
+    spec = importlib.util.spec_from_file_location("e2v_sniff", os.path.join(ROOT, "v2e", "e2v.py"))
+    e2v = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(e2v)                                       # the sniff functions work without importing the package
+    assert e2v.is_aedat3(str(tmp_path / "rec.aedat")) and not e2v.is_aedat3(str(tmp_path / "two.aedat")) and not e2v.is_aedat3(None)
+
+
+def test_the_other_versions_entry_points_refuse_a_3_1_file_as_before():
+    cols = W.random_events(5, HW, 11)
+    data = W.write_aedat3(W.split(cols, (5,)))
+    with pytest.raises(er.UnsupportedAedat, match=r"AEDAT-3\.1 is not supported \(only AEDAT-2\.0 is\)"):
+        er.split_aedat2_header(data)
+    with pytest.raises(er.UnsupportedAedat, match=r"AEDAT-3\.1 is not supported \(only AEDAT-2\.0 is\)"):
+        er.read_events_aedat2(data, HW)                                # refused on the host, before any device work
+    with pytest.raises(er.UnsupportedAedat4, match="not an AEDAT-4.0 file: the first 14 bytes are"):
+        er.parse_aedat4(data)
+
+
+# ------------------------------------------------------------------ the C ABI, without a device
+NAMES = ("scpose_events_aedat3_workspace_bytes", "scpose_events_aedat3_count", "scpose_events_aedat3_unpack")
+P = 4096                                       # aligned stand-in for device pointers, never touched
+N = 3
+
+
+def ws_bytes(n):
+    b = ctypes.c_size_t()
+    assert nat.lib().scpose_events_aedat3_workspace_bytes(n, ctypes.byref(b)) == 0
+    return b.value
+
+
+def test_symbols_are_exported_and_declared():
+    header = open(os.path.join(ROOT, "include", "scpose.h")).read()
+    handle = ctypes.CDLL(nat.LIB_PATH)
+    for name in NAMES:
+        assert hasattr(handle, name) and ("int32_t %s(" % name) in header and name in nat.SYMBOLS
+    assert nat.lib().scpose_abi_version() == 7 == nat.ABI_VERSION          # additive: the number does not move
+    assert "SCPOSE_AEDAT3_CORRUPT = 1, SCPOSE_AEDAT3_VALID_MISMATCH = 2, SCPOSE_AEDAT3_RANGE = 4, SCPOSE_AEDAT3_CAPACITY = 8" in header
+    assert (nat.AEDAT3_CORRUPT, nat.AEDAT3_VALID_MISMATCH, nat.AEDAT3_RANGE, nat.AEDAT3_CAPACITY) == (1, 2, 4, 8)
+
+
+def test_workspace_query():
+    assert ws_bytes(0) > 0                                                # never an empty workspace
+    assert ws_bytes(0) <= ws_bytes(1) <= ws_bytes(300) < ws_bytes(3000) < ws_bytes(2 ** 31 - 1)
+    assert ws_bytes(3000) >= 3000 * (4 * 4 + 3 * 8)                       # four int32 and three int64 words per packet
+    b = ctypes.c_size_t()
+    lib = nat.lib()
+    assert lib.scpose_events_aedat3_workspace_bytes(-1, ctypes.byref(b)) == -1 and b"n_packets=-1" in lib.scpose_last_error()
+    assert lib.scpose_events_aedat3_workspace_bytes(2 ** 31, ctypes.byref(b)) == -1
+    assert lib.scpose_events_aedat3_workspace_bytes(1, None) == -1 and b"null" in lib.scpose_last_error()
+
+
+def test_argument_errors():
+    lib = nat.lib()
+    err = lambda: lib.scpose_last_error()
+    need = ws_bytes(N)
+
+    def count(file=P, packets=P, n=N, out=P, ws=P, size=need):
+        return lib.scpose_events_aedat3_count(file, packets, n, out, ws, size, None)
+
+    def unpack(file=P, packets=P, n=N, h=260, w=346, cols=(P, P, P, P), capacity=10, out=P, ws=P, size=need):
+        return lib.scpose_events_aedat3_unpack(file, packets, n, h, w, 1, *cols, capacity, out, ws, size, None)
+
+    for call in (count, unpack):
+        assert call(n=-1) == -1 and b"n_packets=-1" in err()
+        assert call(n=2 ** 31) == -1 and b"n_packets" in err()
+        assert call(ws=None) == -1 and b"workspace" in err()
+        assert call(size=need - 1) == -1 and b"workspace" in err()
+        assert call(ws=P + 8) == -1 and b"aligned" in err()
+        assert call(file=None) == -1 and b"null" in err()
+        assert call(packets=None) == -1 and b"null" in err()
+        assert call(out=None) == -1 and b"null" in err()
+        assert call(packets=P + 4) == -1 and b"aligned" in err()
+    assert unpack(cols=(P, None, P, P)) == -1 and b"null" in err()
+    assert unpack(capacity=-1) == -1 and b"capacity" in err()
+    for h, w in ((0, 346), (260, 0), (32769, 346), (260, 32769)):
+        assert unpack(h=h, w=w) == -1 and b"not supported" in err()

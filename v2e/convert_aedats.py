@@ -16,8 +16,10 @@ Extensions (optional): --no_distorted skips event-frames-distorted/; the CSV fla
 file outside the device parser's grammar (an exponent, a quoted field, ...) falls back to by itself; a scene's events.aedat
 is decoded on the device (csrc/events_aedat2_read.hip) with --image_height x --image_width as the sensor size and --aedat_layout
 as the address word, and events.csv wins when both exist; a scene with neither but exactly one *.aedat4 file (an AEDAT-4.0
-recording) is rendered from that file, decompressed and unpacked on the device (csrc/events_aedat4_read.hip).  Not reproduced:
-the AVI video and frame-times file e2v.py also writes, AEDAT-3 parsing."""
+recording) is rendered from that file, decompressed and unpacked on the device (csrc/events_aedat4_read.hip); failing that, a scene with exactly one AEDAT-3.1
+recording (a *.aedat or *.aedat3 file that starts with '#!AER-DAT3.', events.aedat included) is rendered from its polarity packets
+(csrc/events_aedat3_read.hip) with --image_height x --image_width as the sensor size.  Not reproduced: the AVI video and
+frame-times file e2v.py also writes, AEDAT-3.0, and the frame, IMU and special events of an AEDAT-3.1 recording."""
 import argparse
 import json
 import os
@@ -58,7 +60,8 @@ def main(argv=None):
     for scene in sorted(os.listdir(args.scenes_dir)):
         full = os.path.join(args.scenes_dir, scene)
         if os.path.isdir(full) and (os.path.exists(os.path.join(full, "events.csv")) or
-                                    os.path.exists(os.path.join(full, "events.aedat")) or er.scene_aedat4(full) is not None):
+                                    os.path.exists(os.path.join(full, "events.aedat")) or er.scene_aedat4(full) is not None or
+                                    er.scene_aedat3(full) is not None):
             names = er.render_scene(full, (args.image_height, args.image_width), K=K, dist=dist,
                                     write_distorted=not args.no_distorted, delim_whitespace=args.delim_whitespace,
                                     swap_xy=args.swap_xy, microseconds_timestamp=args.microseconds_timestamp,

@@ -19,7 +19,9 @@ An IN that ends in .aedat / .aedat2 is an AEDAT-2.0 file and is read by event_re
 DAVIS word, the default, or the word this tool and v2e.py --events_aedat2 write); the two text flags are refused.  An IN that
 ends in .aedat4 (or starts with the AEDAT-4.0 version line) is a DV recording and is read by event_read.read_events_aedat4
 (csrc/events_aedat4_read.hip): the sensor size comes from the file unless --width and --height say otherwise, and the text flags
-and --aedat_layout are refused.  With a .csv or
+and --aedat_layout are refused.  An IN that ends in .aedat3 (or starts with '#!AER-DAT3.', whatever its name) is an AEDAT-3.1
+recording and is read by event_read.read_events_aedat3 (csrc/events_aedat3_read.hip) under the same rules: the sensor size is
+that of the camera the file names unless --width and --height say otherwise.  With a .csv or
 .txt OUT this is the device counterpart of the reference's aedat_to_csv.py for AEDAT-2.0 files.
 """
 import argparse
@@ -59,13 +61,19 @@ def main(argv=None):
     if not aedat4_in and os.path.isfile(args.events_file):
         with open(args.events_file, "rb") as f:
             aedat4_in = f.read(14) == b"#!AER-DAT4.0\r\n"
-    if aedat4_in and (args.delim_whitespace or args.swap_xy or args.aedat_layout):
-        sys.exit("events_convert: --delim_whitespace, --swap_xy and --aedat_layout cannot be used with the AEDAT-4.0 input %s"
-                 % args.events_file)
-    if aedat4_in and (args.width is None) != (args.height is None):
-        sys.exit("events_convert: give --width and --height together, or neither (the AEDAT-4.0 file states its sensor size)")
+    aedat3_in = args.events_file.lower().endswith(".aedat3")
+    if not aedat4_in and not aedat3_in and os.path.isfile(args.events_file):
+        with open(args.events_file, "rb") as f:
+            aedat3_in = f.read(11) == b"#!AER-DAT3."
+    version = "AEDAT-4.0" if aedat4_in else "AEDAT-3.1"
+    if (aedat4_in or aedat3_in) and (args.delim_whitespace or args.swap_xy or args.aedat_layout):
+        sys.exit("events_convert: --delim_whitespace, --swap_xy and --aedat_layout cannot be used with the %s input %s"
+                 % (version, args.events_file))
+    if (aedat4_in or aedat3_in) and (args.width is None) != (args.height is None):
+        sys.exit("events_convert: give --width and --height together, or neither (the %s file states its sensor%s)"
+                 % (version, " size" if aedat4_in else ", and a known camera's size is taken from its name"))
     args.aedat_layout = args.aedat_layout or "davis"
-    aedat_in = args.events_file.lower().endswith((".aedat", ".aedat2")) and not aedat4_in
+    aedat_in = args.events_file.lower().endswith((".aedat", ".aedat2")) and not aedat4_in and not aedat3_in
     if aedat_in and (args.width is None or args.height is None):
         sys.exit("events_convert: an .aedat input needs --width and --height, the sensor size")
     if aedat_in and (args.delim_whitespace or args.swap_xy):
@@ -82,10 +90,11 @@ def main(argv=None):
         except ValueError as e:
             sys.exit("events_convert: %s" % e)
     ops = import_module("spacecraft-pose-estimation_amd.ops")
-    if aedat4_in:
+    if aedat4_in or aedat3_in:
         er = import_module("spacecraft-pose-estimation_amd.event_read")
+        read = er.read_events_aedat4 if aedat4_in else er.read_events_aedat3
         try:
-            t, x, y, p, info = er.read_events_aedat4(args.events_file, hw=None if args.width is None else (args.height, args.width))
+            t, x, y, p, info = read(args.events_file, hw=None if args.width is None else (args.height, args.width))
         except ValueError as e:
             sys.exit("events_convert: %s" % e)
         print("events_convert: %s: %s" % (args.events_file, ", ".join("%s=%s" % kv for kv in sorted(info.items()))))
