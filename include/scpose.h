@@ -633,6 +633,35 @@ int32_t scpose_png_decode_crop(const uint8_t* desc, const uint8_t* data, int64_t
                                int32_t channels, int32_t bgr, const double* minv, const int32_t* roi_xywh, int32_t out_h, int32_t out_w,
                                uint8_t* crops, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* (ABI 7, additive) Area resize for shrinking on the device (csrc/resize_area.hip): uint8 frames (F, H, W, C), C = 1 or 3, ->
+ * (F, h, w, C), or with gray != 0 and C = 3 -> (F, h, w) by OpenCV's 8-bit rule (4899 R + 9617 G + 1868 B + 8192) >> 14 on the
+ * rounded resized channels: what the DVS emulator takes.  The arithmetic is cv2.resize(.., interpolation=INTER_AREA) as
+ * resize_area.py restates it; the host builds one table per axis there and the kernel only applies them.
+ *   src          device u8 [F][H][W][C]
+ *   F, H, W, C   F >= 0 (0: nothing to do); H, W 1 .. 65535; C 1 or 3; H W C < 2^31
+ *   dst          device u8 [F][h][w][C], or [F][h][w] when gray != 0 or C = 1
+ *   h, w         1 .. H and 1 .. W: no axis grows
+ *   gray, bgr    gray != 0: reduce three channels to one; bgr != 0: plane 0 is B and plane 2 is R (else the reverse)
+ *   rule         SCPOSE_RESIZE_AREA_WEIGHTED: h = ((0 + p0 a0) + p1 a1) + .. along a source row in tap order, v = b0 h0, + b1 h1, ..
+ *                down the rows, every multiply and add one float32 rounding, then round-half-to-even saturated to 0 .. 255.
+ *                SCPOSE_RESIZE_AREA_BOX: W = cx w and H = cy h; s = the integer sum of the cx x cy box; (s + 2) >> 2 for 2 x 2, else
+ *                float32(s) * float32(1.0f / (cx cy)) rounded the same way; cx cy <= 2^23.  The weights of a box table are not read.
+ *   xtab, ytab   HOST i32 [w] and [h] records of SCPOSE_RESIZE_AREA_REC_WORDS words: first source index, tap count (>= 1), then the
+ *                float32 bits of the weight of the first tap, of every inner tap and of the last tap (a record with one tap uses the
+ *                first, with two the first and the last).  Checked before anything is launched -- every tap must lie inside the
+ *                source axis and `first` must not decrease; rule BOX: first = d c and count = c for every d -- and uploaded into the
+ *                workspace on `stream`: keep them unchanged until the stream has passed the call
+ *   workspace    caller-owned, 256-byte aligned, scpose_resize_area_workspace_bytes(h, w)
+ * No allocation, no synchronisation, no atomics; reads nothing outside src[0 .. F H W C) and writes nothing outside dst.  A batch
+ * is one launch: more than 2^31 - 1 blocks (strips of 8 x 256 output pixels) is an argument error, and so is every other bad
+ * argument: -1 with a message before anything is launched, without a device. */
+enum { SCPOSE_RESIZE_AREA_WEIGHTED = 0, SCPOSE_RESIZE_AREA_BOX = 1 };
+#define SCPOSE_RESIZE_AREA_REC_WORDS 5
+int32_t scpose_resize_area_workspace_bytes(int32_t h, int32_t w, size_t* bytes);
+int32_t scpose_resize_area_u8(const uint8_t* src, int32_t F, int32_t H, int32_t W, int32_t C, uint8_t* dst, int32_t h, int32_t w,
+                              int32_t gray, int32_t bgr, int32_t rule, const int32_t* xtab, const int32_t* ytab, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
 /* (ABI 7, additive) Baseline JPEG encoder on the device (csrc/jpeg_encode.hip): (N, H, W, 3) uint8 RGB frames of one size ->
  * N baseline JPEG byte streams, byte for byte what libjpeg's baseline encoder writes with the standard Huffman tables (PIL's
  * save(quality=q, subsampling=..) with its other defaults): jccolor.c, jcsample.c's h2v2 downsampling, jfdctint.c's forward

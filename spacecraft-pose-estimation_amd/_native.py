@@ -35,6 +35,8 @@ JPEG_SUBSEQ_BYTES, JPEG_DESC_BYTES = 128, 9216
 JPEG_ENC_CAPACITY, JPEG_ENC_TABLES = 1, 2
 PNG_CORRUPT, PNG_CHECKSUM, PNG_FILTER = 1, 2, 4
 PNG_DESC_BYTES = 832
+RESIZE_AREA_WEIGHTED, RESIZE_AREA_BOX = 0, 1
+RESIZE_AREA_REC_WORDS = 5
 ABI_VERSION = 7
 
 
@@ -176,6 +178,9 @@ SYMBOLS = {
                                     c_size_t, c_void_p]),
     "scpose_png_decode_crop": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                          c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "scpose_resize_area_workspace_bytes": (c_int32, [c_int32, c_int32, POINTER(c_size_t)]),
+    "scpose_resize_area_u8": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                        c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "scpose_jpeg_encode_workspace_bytes": (c_int32, [c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
     "scpose_jpeg_encode_capacity_bytes": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int64)]),
     "scpose_jpeg_encode": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p,

@@ -502,6 +502,48 @@ extern "C" int32_t scpose_png_decode_crop(const uint8_t* desc, const uint8_t* da
                                 static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
 }
 
+static int32_t resize_area_check_tab(const char* axis, const int32_t* tab, int32_t n_out, int32_t n_in, bool box) {
+  const int32_t c = n_in / n_out;
+  int32_t prev = 0;
+  for (int32_t d = 0; d < n_out; ++d) {
+    const int32_t first = tab[(size_t)d * SCPOSE_RESIZE_AREA_REC_WORDS], count = tab[(size_t)d * SCPOSE_RESIZE_AREA_REC_WORDS + 1];
+    SCP_REQUIRE(first >= prev && count >= 1 && first < n_in && count <= n_in - first,
+                "resize_area: %s table, record %d: taps [%d, +%d) do not lie inside 0 .. %d in increasing order", axis, d, first, count, n_in);
+    SCP_REQUIRE(!box || (first == d * c && count == c), "resize_area: %s table, record %d: a box table has taps [%d, +%d) there (got [%d, +%d))",
+                axis, d, d * c, c, first, count);
+    prev = first;
+  }
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_resize_area_workspace_bytes(int32_t h, int32_t w, size_t* bytes) {
+  SCP_REQUIRE(bytes, "resize_area_workspace_bytes: null argument");
+  SCP_REQUIRE(h >= 1 && h <= 65535 && w >= 1 && w <= 65535, "resize_area_workspace_bytes: output size %dx%d (HxW), 1 .. 65535 each", h, w);
+  *bytes = resize_area_workspace_bytes(h, w);
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_resize_area_u8(const uint8_t* src, int32_t F, int32_t H, int32_t W, int32_t C, uint8_t* dst, int32_t h, int32_t w,
+                                         int32_t gray, int32_t bgr, int32_t rule, const int32_t* xtab, const int32_t* ytab, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+  SCP_REQUIRE(F >= 0, "resize_area: F=%d", F);
+  if (F == 0) return SCPOSE_OK;
+  SCP_REQUIRE(H >= 1 && H <= 65535 && W >= 1 && W <= 65535, "resize_area: frame %dx%d (HxW), 1 .. 65535 each", H, W);
+  SCP_REQUIRE(C == 1 || C == 3, "resize_area: channels=%d (1 or 3)", C);
+  SCP_REQUIRE((int64_t)H * W * C < ((int64_t)1 << 31), "resize_area: frame %dx%dx%d: one frame must stay below 2^31 bytes", H, W, C);
+  SCP_REQUIRE(h >= 1 && w >= 1 && h <= H && w <= W, "resize_area: output size %dx%d (HxW) of a %dx%d frame: no axis may grow", h, w, H, W);
+  SCP_REQUIRE(rule == SCPOSE_RESIZE_AREA_WEIGHTED || rule == SCPOSE_RESIZE_AREA_BOX, "resize_area: rule=%d", rule);
+  const bool box = rule == SCPOSE_RESIZE_AREA_BOX;
+  SCP_REQUIRE(!box || (H % h == 0 && W % w == 0 && (int64_t)(H / h) * (W / w) <= (1 << 23)),
+              "resize_area: the box rule needs whole ratios with at most 2^23 pixels per box (%dx%d -> %dx%d)", H, W, h, w);
+  SCP_REQUIRE(src && dst && xtab && ytab, "resize_area: null argument");
+  if (int32_t rc = resize_area_check_tab("x", xtab, w, W, box)) return rc;
+  if (int32_t rc = resize_area_check_tab("y", ytab, h, H, box)) return rc;
+  if (int32_t rc = workspace_ok("resize_area", workspace, workspace_bytes, resize_area_workspace_bytes(h, w), 256)) return rc;
+  return resize_area_launch(src, F, H, W, C, dst, h, w, gray != 0, bgr != 0, box, xtab, ytab, static_cast<uint8_t*>(workspace),
+                            static_cast<hipStream_t>(stream));
+}
+
 static int32_t jpeg_encode_check_shape(int32_t n, int32_t h, int32_t w, int32_t mode, const char* who) {
   if (int32_t rc = jpeg_frame_ok(who, n, h, w, mode)) return rc;
   SCP_REQUIRE(jpeg_blocks(h, w, mode) * 2800 < ((int64_t)1 << 31),

@@ -395,6 +395,11 @@ int32_t jpeg_encode_launch(const uint8_t* frames, int n, int h, int w, int mode,
                            int header_bytes, uint8_t* out, int64_t capacity, int64_t* offsets, int32_t* status, uint8_t* ws,
                            hipStream_t stream);
 int32_t overlay_draw_launch(uint8_t* frames, int n, int h, int w, const int32_t* bboxes, const double* points, int j, hipStream_t stream);
+// resize_area.hip: uint8 frames -> area-resized frames or gray frames; the tables are host memory (w and h records of
+// SCPOSE_RESIZE_AREA_REC_WORDS words, checked by the caller), uploaded into the workspace on `stream`
+size_t resize_area_workspace_bytes(int h, int w);
+int32_t resize_area_launch(const uint8_t* src, int F, int H, int W, int C, uint8_t* dst, int h, int w, int gray, int bgr, int box,
+                           const int32_t* xtab_host, const int32_t* ytab_host, uint8_t* ws, hipStream_t stream);
 // dvs_emulator.hip: intensity frames -> event stream (v2e/v2ecore/emulator.py: EventEmulator.generate_events)
 size_t dvs_state_bytes(int h, int w);
 size_t dvs_workspace_bytes(int h, int w, int frames, int max_iters);

@@ -200,6 +200,29 @@ def frame_times_text(dvs_vid, times):
         "{}\t{:10.6f}\n".format(k, float(tk)) for k, tk in enumerate(times))
 
 
+def write_event_frames(output_folder, dvs_vid, t, x, y, hw, full_scale=2, chunk=256, **exposure):
+    """The output of e2v.py, which v2e.py --dvs_exposure writes too: the time-sorted device columns t, x, y rendered by
+    ops.render_events (polarity folded, frame times wanted) with the exposure keywords of exposure_kwargs, every frame as
+    <output_folder>/event-frames/<stem>.bmp in frame order -- a repeated stem keeps the later frame -- and the frame-times file of
+    dvs_vid.  An empty stream writes the times file's header alone.  -> the stems."""
+    from . import ops
+    h, w = hw
+    out_dir = os.path.join(output_folder, "event-frames")
+    os.makedirs(out_dir, exist_ok=True)
+    times, names = [], []
+    if len(t) > 0:
+        frames, names = ops.render_events(t, x, y, None, (h, w), full_scale=full_scale, fold_polarity=True, want_times=True, **exposure)
+        times = frames["times"]
+        img = frames["flat"].view(-1, h, w, 3)
+        for k0 in range(0, len(names), chunk):            # in frame order: a repeated stem keeps the later frame
+            host = img[k0:k0 + chunk].cpu().numpy()
+            for i, name in enumerate(names[k0:k0 + chunk]):
+                write_bmp(os.path.join(out_dir, name + ".bmp"), host[i])
+    with open(frame_times_path(output_folder, dvs_vid), "w") as f:
+        f.write(frame_times_text(dvs_vid, times))
+    return names
+
+
 def scene_aedat4(scene_dir):
     """The scene's one *.aedat4 file, None when it has none or several."""
     found = sorted(f for f in os.listdir(scene_dir) if f.lower().endswith(".aedat4"))

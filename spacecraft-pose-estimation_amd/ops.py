@@ -1038,6 +1038,40 @@ def draw_overlays(frames, bboxes, points):
     return frames
 
 
+def resize_area(frames, out_hw, gray=True, channels="rgb"):
+    """uint8 frames (F, H, W, 3) or (F, H, W) -> (F, h, w) gray frames, or with gray=False (F, h, w, 3) resized frames, on the device
+    (csrc/resize_area.hip): cv2.resize(.., interpolation=cv2.INTER_AREA) per channel as resize_area.py restates it, then OpenCV's
+    8-bit gray rule (4899 R + 9617 G + 1868 B + 8192) >> 14 on the rounded channels.  out_hw = (h, w) with h <= H and w <= W; the
+    input's own size means gray only.  frames: a device tensor, or a host array that is uploaded.  channels: "rgb" or "bgr", which
+    plane the R weight goes to.  One-channel frames are resized and `gray` is ignored.  The result is contiguous uint8, what
+    DvsEmulator.emulate takes.  ValueError for a wrong dtype, rank or channel count and for an axis that would grow."""
+    from . import resize_area as ra
+    if channels not in ("rgb", "bgr"):
+        raise ValueError("resize_area: channels=%r (rgb or bgr)" % (channels,))
+    fr = frames if torch.is_tensor(frames) else torch.from_numpy(np.ascontiguousarray(np.asarray(frames)))
+    if fr.dtype != torch.uint8 or fr.dim() not in (3, 4) or (fr.dim() == 4 and fr.shape[3] != 3):
+        raise ValueError("resize_area: frames must be uint8 of shape (F, H, W, 3) or (F, H, W) (got %s %s)" % (fr.dtype, tuple(fr.shape)))
+    f, H, W = (int(v) for v in fr.shape[:3])
+    c = 3 if fr.dim() == 4 else 1
+    if H < 1 or W < 1:
+        raise ValueError("resize_area: empty frames %s" % (tuple(fr.shape),))
+    rule, xrec, yrec = ra.plan((H, W), out_hw)                  # ValueError for a growing axis, before anything runs
+    h, w = int(out_hw[0]), int(out_hw[1])
+    if not fr.is_cuda:
+        fr = fr.to(torch.device("cuda", torch.cuda.current_device()))
+    fr = fr.contiguous()
+    dev = fr.device
+    with torch.cuda.device(dev):
+        out = torch.empty((f, h, w) if gray or c == 1 else (f, h, w, 3), dtype=torch.uint8, device=dev)
+        ws = _query_bytes("resize_area_workspace_bytes", h, w)
+        work = torch.empty(ws, dtype=torch.uint8, device=dev)
+        nat.check(nat.lib().scpose_resize_area_u8(_ptr(fr), f, H, W, c, _ptr(out), h, w, 1 if gray else 0, 1 if channels == "bgr" else 0, rule,
+                                                  c_void_p(xrec.ctypes.data), c_void_p(yrec.ctypes.data), _ptr(work), ws, _stream()),
+                  "resize_area_u8")
+        torch.cuda.current_stream().synchronize()               # the tables are host memory: they stay until the stream has read them
+    return out
+
+
 class DvsEmulator:
     """Device DVS emulator (csrc/dvs_emulator.hip): see dvs_emulator().  The state lives in device memory between calls."""
 

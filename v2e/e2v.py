@@ -135,7 +135,6 @@ def main(argv=None):
     import scpose  # noqa: F401
     from importlib import import_module
     er = import_module("spacecraft-pose-estimation_amd.event_render")
-    ops = import_module("spacecraft-pose-estimation_amd.ops")
     mode, value, dim = er.parse_dvs_exposure(args.dvs_exposure)
     kw = er.exposure_kwargs(mode, value, dim)
     print("e2v: the AVI video (%s) is not written: no video encoder is available; frames go to %s" %
@@ -162,19 +161,7 @@ def main(argv=None):
         if not aedat:
             raise
         sys.exit("e2v: %s" % e)
-    times, names = [], []
-    if len(t) > 0:
-        frames, names = ops.render_events(t, x, y, None, (h, w),
-                                          full_scale=args.dvs_vid_full_scale, fold_polarity=True, want_times=True, **kw)
-        times = frames["times"]
-        img = frames["flat"].view(-1, h, w, 3)
-        chunk = 256
-        for k0 in range(0, len(names), chunk):            # in frame order: a repeated stem keeps the later frame
-            host = img[k0:k0 + chunk].cpu().numpy()
-            for i, name in enumerate(names[k0:k0 + chunk]):
-                er.write_bmp(os.path.join(out_dir, name + ".bmp"), host[i])
-    with open(er.frame_times_path(args.output_folder, args.dvs_vid), "w") as f:
-        f.write(er.frame_times_text(args.dvs_vid, times))
+    names = er.write_event_frames(args.output_folder, args.dvs_vid, t, x, y, (h, w), full_scale=args.dvs_vid_full_scale, **kw)
     print("e2v: %d frames (%s)" % (len(names), " ".join(args.dvs_exposure)))
 
 
