@@ -523,6 +523,39 @@ int32_t scpose_events_aedat4_unpack(const uint8_t* src, int64_t n_packets, int32
                                     int32_t* y, int8_t* p, int64_t capacity, int64_t* count_status, void* workspace,
                                     size_t workspace_bytes, void* stream);
 
+/* (ABI 7, additive) The event packets of an AEDAT-4.0 recording, written on the device (csrc/events_aedat4_write.hip, which states
+ * what is written): the four columns and the packets' row boundaries -> the byte string `int32 streamID, int32 size, payload` of
+ * every packet, one after the other, as it stands in the file between the IOHeader and the file data table.  The host writes the
+ * rest (event_write.write_events_aedat4).
+ *   compression  SCPOSE_AEDAT4_NONE: a payload is the packet's size-prefixed "EVTS" flatbuffer, 48 + 16 * count bytes.
+ *                SCPOSE_AEDAT4_LZ4: one LZ4 frame of it -- independent blocks of 64 KiB, content checksum, no content size, no block
+ *                checksums; a block that does not compress is stored.  Valid LZ4, not liblz4's bytes.
+ *   bounds       device i64 [n_packets + 1], rows: packet k holds rows bounds[k] .. bounds[k + 1] - 1; bounds[0] = 0, bounds[n_packets]
+ *                = n, never decreasing (checked on the device: SCPOSE_AEDAT4_WRITE_BOUNDS).  An empty packet is written as one.
+ *   out          device u8, 8-byte aligned, `capacity` bytes; _pack_sizes gives the capacity that always suffices
+ *   table        device i64 [n_packets][5] <- per packet: byte offset of its record in `out`, payload size, events, first and last t
+ *   total_status device i64 [2] <- [bytes written, status].  Read back once.  With a status set NOTHING has been stored in `out`
+ *                and bytes is unspecified.  SCPOSE_AEDAT4_WRITE_RANGE: some x outside [0, w), y outside [0, h) or p outside {0, 1}.
+ *                _SIZE: a packet of more than 2^23 - 1 events or 2^23 - 16 flatbuffer bytes (what the reader takes).  _CAPACITY:
+ *                `out` is too small.
+ *   workspace    caller-owned, 16-byte aligned, _pack_sizes' workspace_bytes (never 0): under LZ4 the flatbuffers and one slot of
+ *                the LZ4 bound per block
+ * scpose_events_aedat4_frame makes the same records (streamID 0) of arbitrary bytes: `bounds` (bytes) cuts src into payloads.
+ * Argument errors (null pointers, n < 0, n_packets < 0 or above 2^24, packets without events' bounds, h or w outside 1 .. 32767,
+ * an unknown compression, a misaligned or short workspace) return -1 with a message before anything is launched.  No allocation,
+ * no synchronisation, integer work only; two runs on the same columns give bitwise equal outputs. */
+enum { SCPOSE_AEDAT4_NONE = 0, SCPOSE_AEDAT4_LZ4 = 1 };
+enum { SCPOSE_AEDAT4_WRITE_RANGE = 1, SCPOSE_AEDAT4_WRITE_SIZE = 2, SCPOSE_AEDAT4_WRITE_BOUNDS = 4, SCPOSE_AEDAT4_WRITE_CAPACITY = 8 };
+int32_t scpose_events_aedat4_pack_sizes(int64_t n, int64_t n_packets, int32_t compression, size_t* workspace_bytes, size_t* out_bytes);
+int32_t scpose_events_aedat4_pack(const int64_t* t, const int32_t* x, const int32_t* y, const int8_t* p, int64_t n,
+                                  const int64_t* bounds, int64_t n_packets, int32_t h, int32_t w, int32_t stream_id, int32_t compression,
+                                  uint8_t* out, int64_t capacity, int64_t* table, int64_t* total_status, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+int32_t scpose_events_aedat4_frame_sizes(int64_t n_bytes, int64_t n_packets, size_t* workspace_bytes, size_t* out_bytes);
+int32_t scpose_events_aedat4_frame(const uint8_t* src, int64_t n_bytes, const int64_t* bounds, int64_t n_packets, uint8_t* out,
+                                   int64_t capacity, int64_t* table, int64_t* total_status, void* workspace, size_t workspace_bytes,
+                                   void* stream);
+
 /* (ABI 7, additive) Baseline JPEG files on the device (csrc/jpeg_decode.hip): the bytes of N files of one geometry -> (N, H, W, 3)
  * uint8 frames, bit for bit what libjpeg's baseline decoder returns (Huffman decoding, jidctint.c's ISLOW inverse DCT, jdsample.c's
  * fancy h2v2 upsampling, jdcolor.c's YCbCr -> RGB).  Decoded: SOF0, 8 bits, one interleaved scan, one component (SCPOSE_JPEG_GRAY)

@@ -29,6 +29,8 @@ AEDAT2_LAYOUT_DAVIS, AEDAT2_LAYOUT_V2E = 0, 1
 AEDAT2_READ_RANGE, AEDAT2_READ_CAPACITY = 1, 2
 AEDAT3_CORRUPT, AEDAT3_VALID_MISMATCH, AEDAT3_RANGE, AEDAT3_CAPACITY = 1, 2, 4, 8
 AEDAT4_CORRUPT, AEDAT4_CHECKSUM, AEDAT4_FLATBUFFER, AEDAT4_RANGE, AEDAT4_CAPACITY = 1, 2, 4, 8, 16
+AEDAT4_NONE, AEDAT4_LZ4 = 0, 1
+AEDAT4_WRITE_RANGE, AEDAT4_WRITE_SIZE, AEDAT4_WRITE_BOUNDS, AEDAT4_WRITE_CAPACITY = 1, 2, 4, 8
 JPEG_GRAY, JPEG_444, JPEG_420 = 0, 1, 2
 JPEG_NOT_CONVERGED, JPEG_CORRUPT = 1, 2
 JPEG_SUBSEQ_BYTES, JPEG_DESC_BYTES = 128, 9216
@@ -168,6 +170,12 @@ SYMBOLS = {
     "scpose_events_aedat4_count": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
     "scpose_events_aedat4_unpack": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                               c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "scpose_events_aedat4_pack_sizes": (c_int32, [c_int64, c_int64, c_int32, POINTER(c_size_t), POINTER(c_size_t)]),
+    "scpose_events_aedat4_pack": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32,
+                                            c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "scpose_events_aedat4_frame_sizes": (c_int32, [c_int64, c_int64, POINTER(c_size_t), POINTER(c_size_t)]),
+    "scpose_events_aedat4_frame": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                             c_size_t, c_void_p]),
     "scpose_jpeg_decode_workspace_bytes": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_size_t)]),
     "scpose_jpeg_decode": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                      c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

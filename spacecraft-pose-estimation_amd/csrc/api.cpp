@@ -362,6 +362,78 @@ extern "C" int32_t scpose_events_aedat4_unpack(const uint8_t* src, int64_t n_pac
                                      static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
 }
 
+static const int64_t kMaxWritePackets = (int64_t)1 << 24;     // one wavefront per packet and per block in one grid
+
+static int32_t aedat4_pack_shape_ok(const char* who, int64_t n, int64_t n_packets, int32_t compression) {
+  SCP_REQUIRE(n >= 0 && n <= kMaxWriteEvents, "%s: n=%lld (0 .. 2^38)", who, (long long)n);
+  SCP_REQUIRE(n_packets >= 0 && n_packets <= kMaxWritePackets, "%s: n_packets=%lld (0 .. 2^24)", who, (long long)n_packets);
+  SCP_REQUIRE(n == 0 || n_packets > 0, "%s: n=%lld events in no packet", who, (long long)n);
+  SCP_REQUIRE(compression == SCPOSE_AEDAT4_NONE || compression == SCPOSE_AEDAT4_LZ4,
+              "%s: compression=%d: the compressions are 0 (NONE) and 1 (LZ4)", who, compression);
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_events_aedat4_pack_sizes(int64_t n, int64_t n_packets, int32_t compression, size_t* workspace_bytes,
+                                                   size_t* out_bytes) {
+  SCP_REQUIRE(workspace_bytes && out_bytes, "events_aedat4_pack_sizes: null argument");
+  if (int32_t rc = aedat4_pack_shape_ok("events_aedat4_pack_sizes", n, n_packets, compression)) return rc;
+  const Aedat4WriteSizes s = events_aedat4_pack_sizes(n, n_packets, compression);
+  *workspace_bytes = s.workspace_bytes;
+  *out_bytes = s.out_bytes;
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_events_aedat4_pack(const int64_t* t, const int32_t* x, const int32_t* y, const int8_t* p, int64_t n,
+                                             const int64_t* bounds, int64_t n_packets, int32_t h, int32_t w, int32_t stream_id,
+                                             int32_t compression, uint8_t* out, int64_t capacity, int64_t* table, int64_t* total_status,
+                                             void* workspace, size_t workspace_bytes, void* stream) {
+  SCP_REQUIRE(h >= 1 && h <= 32767 && w >= 1 && w <= 32767, "events_aedat4_pack: sensor %dx%d (HxW) not supported: each 1 .. 32767",
+              h, w);
+  if (int32_t rc = aedat4_pack_shape_ok("events_aedat4_pack", n, n_packets, compression)) return rc;
+  SCP_REQUIRE(capacity >= 0, "events_aedat4_pack: capacity=%lld", (long long)capacity);
+  SCP_REQUIRE(total_status && ((t && x && y && p) || n == 0) && ((bounds && table) || n_packets == 0) && (out || capacity == 0),
+              "events_aedat4_pack: null argument");
+  SCP_REQUIRE(aligned(out, 8) && aligned(bounds, 8) && aligned(table, 8) && aligned(total_status, 8),
+              "events_aedat4_pack: out, bounds, table and total_status must be 8-byte aligned");
+  if (int32_t rc = workspace_ok("events_aedat4_pack", workspace, workspace_bytes,
+                                events_aedat4_pack_sizes(n, n_packets, compression).workspace_bytes, 16))
+    return rc;
+  return events_aedat4_pack_launch(t, x, y, p, n, bounds, n_packets, h, w, stream_id, compression, out, capacity, table, total_status,
+                                   static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+static int32_t aedat4_frame_shape_ok(const char* who, int64_t n_bytes, int64_t n_packets) {
+  SCP_REQUIRE(n_bytes >= 0 && n_bytes <= ((int64_t)1 << 42), "%s: n_bytes=%lld (0 .. 2^42)", who, (long long)n_bytes);
+  SCP_REQUIRE(n_packets >= 0 && n_packets <= kMaxWritePackets, "%s: n_packets=%lld (0 .. 2^24)", who, (long long)n_packets);
+  SCP_REQUIRE(n_bytes == 0 || n_packets > 0, "%s: n_bytes=%lld in no packet", who, (long long)n_bytes);
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_events_aedat4_frame_sizes(int64_t n_bytes, int64_t n_packets, size_t* workspace_bytes, size_t* out_bytes) {
+  SCP_REQUIRE(workspace_bytes && out_bytes, "events_aedat4_frame_sizes: null argument");
+  if (int32_t rc = aedat4_frame_shape_ok("events_aedat4_frame_sizes", n_bytes, n_packets)) return rc;
+  const Aedat4WriteSizes s = events_aedat4_frame_sizes(n_bytes, n_packets);
+  *workspace_bytes = s.workspace_bytes;
+  *out_bytes = s.out_bytes;
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_events_aedat4_frame(const uint8_t* src, int64_t n_bytes, const int64_t* bounds, int64_t n_packets, uint8_t* out,
+                                              int64_t capacity, int64_t* table, int64_t* total_status, void* workspace,
+                                              size_t workspace_bytes, void* stream) {
+  if (int32_t rc = aedat4_frame_shape_ok("events_aedat4_frame", n_bytes, n_packets)) return rc;
+  SCP_REQUIRE(capacity >= 0, "events_aedat4_frame: capacity=%lld", (long long)capacity);
+  SCP_REQUIRE(total_status && (src || n_bytes == 0) && ((bounds && table) || n_packets == 0) && (out || capacity == 0),
+              "events_aedat4_frame: null argument");
+  SCP_REQUIRE(aligned(bounds, 8) && aligned(table, 8) && aligned(total_status, 8),
+              "events_aedat4_frame: bounds, table and total_status must be 8-byte aligned");
+  if (int32_t rc = workspace_ok("events_aedat4_frame", workspace, workspace_bytes,
+                                events_aedat4_frame_sizes(n_bytes, n_packets).workspace_bytes, 16))
+    return rc;
+  return events_aedat4_frame_launch(src, n_bytes, bounds, n_packets, out, capacity, table, total_status,
+                                    static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
 // what the decoder, the encoder and the overlay draw ask of a batch of frames
 static int32_t frames_ok(const char* who, int32_t n, int32_t h, int32_t w) {
   SCP_REQUIRE(n >= 1 && n <= 65535, "%s: n=%d (1 .. 65535)", who, n);

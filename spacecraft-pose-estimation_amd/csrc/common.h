@@ -371,6 +371,20 @@ int32_t events_aedat4_count_launch(const uint8_t* src, const int64_t* packets, i
                                    hipStream_t stream);
 int32_t events_aedat4_unpack_launch(const uint8_t* src, int64_t n, int h, int w, int rebase, int64_t* t, int32_t* x, int32_t* y,
                                     int8_t* p, int64_t capacity, int64_t* count_status, uint8_t* ws, hipStream_t stream);
+// the limits of one packet that the reader holds its input to and the writer its output (events_aedat4_read.hip says why)
+constexpr int kAedat4MaxDecoded = (1 << 23) - 16;
+constexpr int kAedat4MaxCount = (1 << 23) - 1;
+// events_aedat4_write.hip: (t, x, y, p) -> the event packets of an AEDAT-4.0 file; bytes -> LZ4 frames
+struct Aedat4WriteSizes {
+  size_t workspace_bytes, out_bytes;
+};
+Aedat4WriteSizes events_aedat4_pack_sizes(int64_t n, int64_t n_packets, int compression);
+Aedat4WriteSizes events_aedat4_frame_sizes(int64_t n_bytes, int64_t n_packets);
+int32_t events_aedat4_pack_launch(const int64_t* t, const int32_t* x, const int32_t* y, const int8_t* p, int64_t n, const int64_t* bounds,
+                                  int64_t n_packets, int h, int w, int stream_id, int compression, uint8_t* out, int64_t capacity,
+                                  int64_t* table, int64_t* total_status, uint8_t* ws, hipStream_t stream);
+int32_t events_aedat4_frame_launch(const uint8_t* src, int64_t n_bytes, const int64_t* bounds, int64_t n_packets, uint8_t* out,
+                                   int64_t capacity, int64_t* table, int64_t* total_status, uint8_t* ws, hipStream_t stream);
 // jpeg_decode.hip: baseline JPEG files -> (N, H, W, 3) uint8 frames (jpeg_common.h: jpeg_blocks(h, w, mode), the blocks of one frame)
 size_t jpeg_decode_workspace_bytes(int n, int h, int w, int mode, int max_subs);
 int32_t jpeg_decode_launch(const uint8_t* desc, const int32_t* segs, int64_t n_rows, const uint8_t* data, int64_t n_bytes, int n, int h,

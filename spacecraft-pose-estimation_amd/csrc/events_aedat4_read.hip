@@ -39,6 +39,7 @@
 // output produced so far, every store against the measured size.  Integer work on fixed positions: two runs are bitwise equal.
 #include "common.h"
 #include "scan_device.h"
+#include "xxh32_wave.h"
 
 namespace scpose {
 
@@ -48,50 +49,9 @@ constexpr int kWave = 64;
 constexpr int kThreads = 256;
 static_assert(kThreads == kScanThreads, "the scan bodies of scan_device.h run in the workgroups of this file");
 constexpr int kInWin = 4096;                         // input window in LDS, bytes
-constexpr int kMaxDecoded = (1 << 23) - 16;          // decoded bytes of one packet: 256 of them, each rounded up to 16, sum within int32
+constexpr int kMaxDecoded = kAedat4MaxDecoded;      // decoded bytes of one packet: 256 of them, each rounded up to 16, sum within int32
 static_assert(256ll * ((kMaxDecoded + 15) & ~15) <= INT_MAX, "scan_tile_counts sums 256 padded sizes in an int32");
-constexpr int kMaxCount = (1 << 23) - 1;             // events of one packet, for the same reason
-constexpr uint32_t kP1 = 2654435761u, kP2 = 2246822519u, kP3 = 3266489917u, kP4 = 668265263u, kP5 = 374761393u;
-
-__device__ __forceinline__ uint32_t rotl(uint32_t v, int r) { return (v << r) | (v >> (32 - r)); }
-__device__ __forceinline__ uint32_t ld32(const uint8_t* p) {
-  uint32_t v;
-  __builtin_memcpy(&v, p, 4);
-  return v;
-}
-
-// xxh32 (seed 0) of n bytes at p, by one wavefront: lane l carries accumulator l & 3 over the 16-byte stripes, 64 stripes at a time
-// through `sw` (256 words of LDS); every lane returns the digest.
-__device__ uint32_t xxh32_wave(const uint8_t* p, long long n, uint32_t* sw) {
-  const int lane = threadIdx.x, a = lane & 3;
-  uint32_t acc = a == 0 ? kP1 + kP2 : (a == 1 ? kP2 : (a == 2 ? 0u : 0u - kP1));
-  const long long full = n >> 4;
-  for (long long s0 = 0; s0 < full; s0 += kWave) {
-    const int m = full - s0 < kWave ? (int)(full - s0) : kWave;
-    __syncthreads();
-    for (int k = 0; k < 4; ++k) {
-      const int wi = lane + kWave * k;
-      if (wi < 4 * m) sw[wi] = ld32(p + (s0 << 4) + 4 * wi);
-    }
-    __syncthreads();
-    for (int j = 0; j < m; ++j) acc = rotl(acc + sw[4 * j + a] * kP2, 13) * kP1;
-  }
-  uint32_t h = kP5;
-  if (n >= 16)
-    h = rotl((uint32_t)__shfl((int)acc, 0, kWave), 1) + rotl((uint32_t)__shfl((int)acc, 1, kWave), 7) +
-        rotl((uint32_t)__shfl((int)acc, 2, kWave), 12) + rotl((uint32_t)__shfl((int)acc, 3, kWave), 18);
-  h += (uint32_t)n;
-  const uint8_t* q = p + (full << 4);
-  int r = (int)(n & 15);
-  for (; r >= 4; r -= 4, q += 4) h = rotl(h + ld32(q) * kP3, 17) * kP4;
-  for (; r > 0; --r, ++q) h = rotl(h + (uint32_t)*q * kP5, 11) * kP1;
-  h ^= h >> 15;
-  h *= kP2;
-  h ^= h >> 13;
-  h *= kP3;
-  h ^= h >> 16;
-  return h;
-}
+constexpr int kMaxCount = kAedat4MaxCount;          // events of one packet, for the same reason
 
 // The input side: wave-uniform byte reads of the payload through an LDS window.  The CALLER checks a position against the payload;
 // the window zero-fills what lies past it.

@@ -688,6 +688,94 @@ def _aedat4_raise(status, hw):
         raise nat.NativeError("unpack_events_aedat4: status %d" % status)
 
 
+AEDAT4_COMPRESSIONS = {"none": nat.AEDAT4_NONE, "lz4": nat.AEDAT4_LZ4}
+AEDAT4_TABLE = ("offset", "size", "n_events", "t_first", "t_last")
+
+
+def _aedat4_compression(who, compression):
+    try:
+        return AEDAT4_COMPRESSIONS[compression]
+    except (KeyError, TypeError):
+        raise ValueError("%s: compression %r: the compressions are 'lz4' and 'none' (ZSTD and LZ4_HIGH are not written)"
+                         % (who, compression))
+
+
+def _packet_bounds(who, bounds, n, what):
+    b = np.ascontiguousarray(bounds, dtype=np.int64).reshape(-1)
+    if b.size == 0 or b[0] != 0 or b[-1] != n or (np.diff(b) < 0).any():
+        raise ValueError("%s: the packet boundaries must rise from 0 to the %d %s (got %d values, %s .. %s)"
+                         % (who, n, what, b.size, b[0] if b.size else None, b[-1] if b.size else None))
+    return b
+
+
+def _aedat4_write_raise(who, status, hw=None):
+    if status & nat.AEDAT4_WRITE_RANGE:
+        raise ValueError("%s: an event lies outside the %d x %d sensor, or a polarity is neither 0 nor 1" % (who, hw[1], hw[0]))
+    if status & nat.AEDAT4_WRITE_SIZE:
+        raise ValueError("%s: a packet is larger than the reader takes (2^23 - 16 bytes: 524284 events)" % who)
+    if status != 0:
+        raise nat.NativeError("%s: status %d" % (who, status))
+
+
+def pack_events_aedat4(t, x, y, p, hw, packet_rows, compression="lz4", stream_id=0):
+    """(t int64 microseconds, x int32, y int32, p int8 in {0, 1}) device tensors -> (uint8 device tensor, table): the event
+    packets of an AEDAT-4.0 file for a sensor of hw = (height, width), `int32 streamID, int32 size, payload` one after the
+    other (csrc/events_aedat4_write.hip).  packet_rows: n_packets + 1 row boundaries rising from 0 to n; packet k holds rows
+    packet_rows[k] .. packet_rows[k + 1] - 1, an empty one is written as an empty packet.  compression: 'none' (a payload is the
+    packet's size-prefixed EVTS flatbuffer) or 'lz4' (one LZ4 frame of it, compressed on the device).  table: int64 NumPy
+    (n_packets, 5), per packet AEDAT4_TABLE: byte offset of its record in the tensor, payload size, events, first and last time
+    stamp -- what the file data table needs.  Raises ValueError for an event outside the sensor, a polarity outside {0, 1} and
+    a packet above the reader's limits; nothing has been stored then.  One read-back: [bytes, status] and the table."""
+    who = "pack_events_aedat4"
+    comp = _aedat4_compression(who, compression)
+    h, w = int(hw[0]), int(hw[1])
+    t, x, y, p, dev, n = _event_columns(who, t, x, y, p)
+    bounds = _packet_bounds(who, packet_rows, n, "rows")
+    npk = int(bounds.size) - 1
+    lib = nat.lib()
+    ws, cap = c_size_t(), c_size_t()
+    nat.check(lib.scpose_events_aedat4_pack_sizes(n, npk, comp, ctypes.byref(ws), ctypes.byref(cap)), "events_aedat4_pack_sizes")
+    with torch.cuda.device(dev):
+        work = torch.empty(ws.value, dtype=torch.uint8, device=dev)
+        out = torch.empty(cap.value, dtype=torch.uint8, device=dev)
+        res = torch.empty(2 + 5 * max(npk, 1), dtype=torch.int64, device=dev)      # [bytes, status], then the table
+        bd = torch.from_numpy(bounds).to(dev)
+        nat.check(lib.scpose_events_aedat4_pack(_ptr(t), _ptr(x), _ptr(y), _ptr(p), n, _ptr(bd), npk, h, w, int(stream_id), comp,
+                                                _ptr(out), cap.value, _ptr(res[2:]), _ptr(res), _ptr(work), ws.value, _stream()),
+                  "events_aedat4_pack")
+        got = res.cpu().numpy()                                     # the one read-back
+    _aedat4_write_raise(who, int(got[1]), (h, w))
+    return out[:int(got[0])], got[2:2 + 5 * npk].reshape(npk, 5).copy()
+
+
+def lz4_frame_bytes(data, bounds=None):
+    """A uint8 device tensor -> (uint8 device tensor, table): the bytes between bounds[k] and bounds[k + 1] (default: all of
+    them, one piece) as records `int32 0, int32 size, LZ4 frame`, framed and compressed as pack_events_aedat4 frames a packet.
+    table: int64 NumPy (n_pieces, 5), the record's offset and the frame's size in its first two columns."""
+    who = "lz4_frame_bytes"
+    if not torch.is_tensor(data) or data.dtype != torch.uint8:
+        raise ValueError("%s: the bytes must be a uint8 device tensor" % who)
+    _need_cuda(data)
+    data = data.contiguous().view(-1)
+    n = int(data.numel())
+    bounds = _packet_bounds(who, (0, n) if bounds is None else bounds, n, "bytes")
+    npk = int(bounds.size) - 1
+    dev = data.device
+    lib = nat.lib()
+    ws, cap = c_size_t(), c_size_t()
+    nat.check(lib.scpose_events_aedat4_frame_sizes(n, npk, ctypes.byref(ws), ctypes.byref(cap)), "events_aedat4_frame_sizes")
+    with torch.cuda.device(dev):
+        work = torch.empty(ws.value, dtype=torch.uint8, device=dev)
+        out = torch.empty(cap.value, dtype=torch.uint8, device=dev)
+        res = torch.empty(2 + 5 * max(npk, 1), dtype=torch.int64, device=dev)
+        bd = torch.from_numpy(bounds).to(dev)
+        nat.check(lib.scpose_events_aedat4_frame(_ptr(data), n, _ptr(bd), npk, _ptr(out), cap.value, _ptr(res[2:]), _ptr(res),
+                                                 _ptr(work), ws.value, _stream()), "events_aedat4_frame")
+        got = res.cpu().numpy()
+    _aedat4_write_raise(who, int(got[1]))
+    return out[:int(got[0])], got[2:2 + 5 * npk].reshape(npk, 5).copy()
+
+
 # ------------------------------------------------------------------ image files (baseline JPEG, PNG) -> frames or network crops
 JPEG_MAX_ROUNDS = 96          # launches of the relaxation (DESIGN.md section 5b: measured distribution and head-room)
 _IMAGE_WORKSPACE = {}         # device index -> uint8 tensor, grown on demand (2 bytes per coefficient: too large to allocate per call)

@@ -2,7 +2,7 @@
 """events_convert: an event text / CSV / AEDAT-2.0 file into another event file, on the device.
 
     python v2e/events_convert.py --events_file IN [--delim_whitespace] [--swap_xy] --output OUT [--width W --height H]
-                                 [--aedat_layout {davis,v2e}]
+                                 [--aedat_layout {davis,v2e}] [--aedat4_compression {lz4,none}]
 
 IN is read by ops.parse_events_csv (csrc/events_csv.hip; --delim_whitespace and --swap_xy are e2v.py's flags of the same
 names) and the four columns go straight to one of the device writers (event_write), chosen by OUT's extension, without a host
@@ -12,6 +12,10 @@ copy of the columns:
     .txt     `t x y p` lines without a header: the --delim_whitespace grammar
     .aedat   AEDAT-2.0 for jAER; needs --width and --height, one of 346x260, 692x520, 1280x720, 640x480, 240x180, and time
              stamps in microseconds
+    .aedat4  AEDAT-4.0 for DV and dv-processing (event_write.write_events_aedat4, csrc/events_aedat4_write.hip): any sensor
+             size up to 32767 x 32767; needs --width and --height unless IN is an .aedat4 or .aedat3 file, which states its
+             sensor size; time stamps in microseconds, written as given; --aedat4_compression picks LZ4 packets (the default,
+             what DV writes) or raw ones
 The text forms write x before y whatever --swap_xy says: the flag describes IN.
 
 An IN that ends in .aedat / .aedat2 is an AEDAT-2.0 file and is read by event_read.read_events_aedat2
@@ -32,7 +36,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-FORMATS = (".csv", ".txt", ".aedat")
+FORMATS = (".csv", ".txt", ".aedat", ".aedat4")
 
 
 def convert_args(parser):
@@ -43,10 +47,12 @@ def convert_args(parser):
     parser.add_argument("--delim_whitespace", action="store_true", default=False, help="fields are separated by blanks, not commas")
     parser.add_argument("--swap_xy", action="store_true", default=False, help="the second column of the input is y, the third x")
     parser.add_argument("--output", type=str, required=True, help="file to write; the extension picks the format: %s" % ", ".join(FORMATS))
-    parser.add_argument("--width", type=int, default=None, help="sensor width in pixels (.aedat input or output only)")
-    parser.add_argument("--height", type=int, default=None, help="sensor height in pixels (.aedat input or output only)")
+    parser.add_argument("--width", type=int, default=None, help="sensor width in pixels (.aedat / .aedat4 input or output only)")
+    parser.add_argument("--height", type=int, default=None, help="sensor height in pixels (.aedat / .aedat4 input or output only)")
     parser.add_argument("--aedat_layout", choices=("davis", "v2e"), default=None,
                         help="address word of an .aedat input: jAER's DAVIS word (the default), or the word the .aedat output here has")
+    parser.add_argument("--aedat4_compression", choices=("lz4", "none"), default="lz4",
+                        help="packets of an .aedat4 output: LZ4 frames (the default, what DV writes) or raw flatbuffers")
     return parser
 
 
@@ -79,6 +85,8 @@ def main(argv=None):
     if aedat_in and (args.delim_whitespace or args.swap_xy):
         sys.exit("events_convert: --delim_whitespace and --swap_xy describe a text file and cannot be used with the AEDAT-2.0 "
                  "input %s" % args.events_file)
+    if ext == ".aedat4" and not (aedat4_in or aedat3_in) and (args.width is None or args.height is None):
+        sys.exit("events_convert: an .aedat4 output needs --width and --height, the sensor size, unless the input states it")
     if not os.path.isfile(args.events_file):
         sys.exit("events_convert: --events_file %s is not a file" % args.events_file)
     import scpose  # noqa: F401
@@ -113,6 +121,13 @@ def main(argv=None):
         except ValueError as e:
             sys.exit("events_convert: %s" % e)
         print("events_convert: %d events -> %d AEDAT-2.0 records in %s" % (int(t.numel()), n, args.output))
+    elif ext == ".aedat4":
+        hw = (args.height, args.width) if args.width is not None else info["hw"]
+        try:
+            n = ew.write_events_aedat4(args.output, t, x, y, p, hw, compression=args.aedat4_compression)
+        except ValueError as e:
+            sys.exit("events_convert: %s" % e)
+        print("events_convert: %d events -> %d AEDAT-4.0 packets (%s) in %s" % (int(t.numel()), n, args.aedat4_compression, args.output))
     else:
         n = ew.write_events_text(args.output, t, x, y, p, sep="," if ext == ".csv" else " ")
         print("events_convert: %d events -> %d bytes in %s" % (int(t.numel()), n, args.output))

@@ -2,7 +2,7 @@
 """v2e: DVS events from intensity frames, the emulator core of the reference's v2e/v2e.py on the MI355X HIP path.
 
     python v2e/v2e.py --input DIR --input_frame_rate 100 --dvs_params clean --output_folder OUT --dvs_text events [--events_aedat2 events]
-                      [--output_width W --output_height H] [--dvs_exposure duration 0.2] [--device_decode]
+                      [--events_aedat4 events] [--output_width W --output_height H] [--dvs_exposure duration 0.2] [--device_decode]
 
 reads the image files of DIR in name order (PIL; grayscale as is, RGB reduced with OpenCV's 8-bit BGR2GRAY weights
 (4899 R + 9617 G + 1868 B + 8192) >> 14, which is what the reference's cv2.imread + cvtColor gives), stamps frame k with
@@ -15,7 +15,9 @@ readers' cast to int64, and the real polarity is written.  The text is formatted
 (event_write.write_events_text); write_text below states the same bytes in Python.  --events_aedat2 NAME adds
 <output_folder>/<NAME>.aedat, the AEDAT-2.0 file the reference's AEDat2Output writes for jAER (same records, a header without
 date and user lines), for the reference's five sensor sizes; e2v.py --aedat_layout v2e reads such a file back (all sizes but
-1280x720, whose address word cannot be inverted).
+1280x720, whose address word cannot be inverted).  --events_aedat4 NAME adds <output_folder>/<NAME>.aedat4, the AEDAT-4.0 file
+that DV and dv-processing open (event_write.write_events_aedat4: LZ4 packets of 10 000 events made on the device, a file data
+table), at any sensor size, 1280x720 included; e2v.py, aedat_to_csv.py and events_convert.py read it back.
 
 Frames of another size than the sensor: --output_width W --output_height H (both or neither) resizes every frame on the device
 before the emulator sees it (csrc/resize_area.hip through ops.resize_area: cv2.resize's INTER_AREA on the three channels, then the
@@ -82,6 +84,8 @@ def v2e_args(parser):
     parser.add_argument("--events_aedat2", type=str, default=None,
                         help="name of an AEDAT-2.0 file for jAER ('.aedat' is added when the name has no extension); frames of "
                              "346x260, 692x520, 1280x720, 640x480 or 240x180 only")
+    parser.add_argument("--events_aedat4", type=str, default=None,
+                        help="name of an AEDAT-4.0 file for DV ('.aedat4' is added when the name has no extension); any frame size")
     parser.add_argument("--output_width", type=int, default=None, help="sensor width; frames of another size are area-resized on the device")
     parser.add_argument("--output_height", type=int, default=None, help="sensor height (give both or neither)")
     parser.add_argument("--dvs_exposure", nargs="+", type=str, default=None,
@@ -287,6 +291,10 @@ def main(argv=None, max_batch_frames=None):
         name = args.events_aedat2 if os.path.splitext(args.events_aedat2)[1] else args.events_aedat2 + ".aedat"
         path = os.path.join(args.output_folder, name)
         print("v2e: %d AEDAT-2.0 records in %s" % (ew.write_events_aedat2(path, t, x, y, pol, (h, w)), path))
+    if args.events_aedat4 is not None:
+        name = args.events_aedat4 if os.path.splitext(args.events_aedat4)[1] else args.events_aedat4 + ".aedat4"
+        path = os.path.join(args.output_folder, name)
+        print("v2e: %d AEDAT-4.0 packets in %s" % (ew.write_events_aedat4(path, t, x, y, pol, (h, w)), path))
     if args.avi_frame_rate is not None:
         print("v2e: no AVI is written (--avi_frame_rate %d): there is no video encoder here" % args.avi_frame_rate, file=sys.stderr)
     if exposure is not None and not args.skip_video_output:
