@@ -202,13 +202,15 @@ def crop_warp(frames, trans, out_wh, swap_rb=False, device=None, roi=None, frame
     frames: list of HxWx3 uint8 arrays/tensors (any sizes); trans: (N,2,3) forward affines as returned by
     get_affine_transform (frame -> crop).  Returns uint8 (N, H, W, 3) device crops.
     roi (N,4) [x0, y0, w, h] + frame_hw (N,2): frames[i] is only that WINDOW of a frame of size frame_hw[i] (warp_window below
-    computes one that contains every tap); same crops bit for bit (scpose_crop_warp_roi)."""
+    computes one that contains every tap); same crops bit for bit (scpose_crop_warp_roi).
+    ValueError, before anything is launched, for a transform with a non-finite entry."""
     import numpy as np
-    dev = device or torch.device("cuda", torch.cuda.current_device())
     packed = isinstance(frames, dict)      # pack_frames(): one flat uint8 tensor + offsets + sizes (what the data-loader workers send)
     if not packed:
         frames = pack_frames(frames)
     n = int(frames["hw"].shape[0])
+    _finite_affines("crop_warp", trans, n)
+    dev = device or torch.device("cuda", torch.cuda.current_device())
     w, h = int(out_wh[0]), int(out_wh[1])
     out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
     if n == 0:
@@ -1032,11 +1034,13 @@ def decode_crop(files, trans, out_wh, rgb=True, device=None, max_rounds=None, fa
     converged is decoded by PIL on the host when `fallback` and its row filled by crop_warp; a corrupt stream raises JpegError.
     png=True: a file parse_jpeg refuses is offered to png_read.parse_png; one it accepts is inflated, unfiltered and sampled by
     csrc/png_decode.hip (rounds 0), info gains "png": the indices decoded that way; a PNG whose status word is not 0 takes the PIL row
-    (PngError when PIL raises, or at once without `fallback`).  png=False: a PNG is just a file parse_jpeg refuses."""
+    (PngError when PIL raises, or at once without `fallback`).  png=False: a PNG is just a file parse_jpeg refuses.
+    ValueError for a transform with a non-finite entry."""
     from .utils.transforms import invert_affine_cv
     dev = _image_device(device, "decode_crop")
     files = _file_blobs(files, "decode_crop")
     trans = np.asarray(trans, dtype=np.float64).reshape(len(files), 2, 3)
+    _finite_affines("decode_crop", trans, len(files))           # ValueError naming the row, before anything is decoded
     ow, oh = int(out_wh[0]), int(out_wh[1])
 
     def crop(idx, frame_hw):
@@ -1277,21 +1281,52 @@ def dvs_emulator(h, w, pos_thres=0.2, neg_thres=0.2, cutoff_hz=0, leak_rate_hz=0
                        leak_jitter_fraction=leak_jitter_fraction, max_iters=max_iters)
 
 
-def warp_window(trans, out_wh, frame_hw):
-    """[x0, y0, w, h]: a window of the frame that contains every pixel crop_warp reads for this affine (host side, NumPy).  The
-    corners of the output grid go through the inverse map exactly as the kernel derives it; the fixed-point coordinates deviate
-    from the real ones by < 1 px and a bilinear tap reads (x, x + 1): two pixels of margin, three on the far side; clipped to the frame
-    (w or h may be 0: nothing of the frame is read)."""
+def _finite_affines(who, trans, n):
+    """ValueError naming the first of the rows trans[0 .. n) that holds a NaN or an infinity, or whose inverse map does: the device's
+    cast of a NaN to an integer and NumPy's differ, so such a row has no defined crop."""
     import numpy as np
     from .utils.transforms import invert_affine_cv
+    with np.errstate(all="ignore"):
+        for i in range(n):
+            t = np.asarray(trans[i], dtype=np.float64)
+            if not np.isfinite(t).all():
+                raise ValueError("%s: transform %d holds a non-finite entry: %s" % (who, i, t.tolist()))
+            if not np.isfinite(invert_affine_cv(t)).all():
+                raise ValueError("%s: the inverse map of transform %d is not finite: %s" % (who, i, t.tolist()))
+
+
+def warp_window(trans, out_wh, frame_hw):
+    """[x0, y0, w, h]: a window of the frame that contains every pixel crop_warp reads for this affine (host side, NumPy); clipped to the
+    frame (w or h may be 0: nothing of the frame is read).  The union of two boxes:
+      * the corners of the output grid through the inverse map as the kernel derives it, in real numbers, with two pixels of margin and
+        three on the far side.  While no term saturates, the fixed-point coordinate lies less than 1 px below the real one and a
+        bilinear tap reads (x, x + 1), so this box holds every tap; it is the window the loader and the decoders have always been given.
+      * the same corners in the kernel's own integers (csrc/bilinear_fixed.h: affine_source).  The row term sat((m1 y + m2) 1024) and
+        the column term sat(m0 x 1024) are each monotone, and so are >> 5, >> 5 and the int16 clip: the smallest and the largest first
+        tap of the whole grid are reached at x in {0, W - 1}, y in {0, H - 1}.  Once a term saturates at +-2^31 (2^21 px, as
+        cv::saturate_cast<int> does) or the index at int16, the taps are no longer near the real coordinates -- a saturated row term
+        plus a large negative column term lands inside the frame -- and only this box holds them.
+    ValueError for a transform with a non-finite entry."""
+    import numpy as np
+    from .utils.transforms import invert_affine_cv, _sat_int
+    _finite_affines("warp_window", [trans], 1)
     m = np.asarray(invert_affine_cv(trans), dtype=np.float64).reshape(2, 3)
     w, h = int(out_wh[0]), int(out_wh[1])
-    cx = np.array([0.0, w - 1.0, 0.0, w - 1.0]); cy = np.array([0.0, 0.0, h - 1.0, h - 1.0])
-    sx = m[0, 0] * cx + m[0, 1] * cy + m[0, 2]; sy = m[1, 0] * cx + m[1, 1] * cy + m[1, 2]
     fh, fw = int(frame_hw[0]), int(frame_hw[1])
-    x0 = min(max(int(np.floor(sx.min())) - 2, 0), fw); x1 = min(max(int(np.ceil(sx.max())) + 3, 0), fw)
-    y0 = min(max(int(np.floor(sy.min())) - 2, 0), fh); y1 = min(max(int(np.ceil(sy.max())) + 3, 0), fh)
-    return [x0, y0, max(x1 - x0, 0), max(y1 - y0, 0)]
+    ex = np.array([0.0, w - 1.0]); ey = np.array([0.0, h - 1.0])
+    cx = np.array([0.0, w - 1.0, 0.0, w - 1.0]); cy = np.array([0.0, 0.0, h - 1.0, h - 1.0])
+    win = []
+    for (mc, mr, mt), size in ((m[0], fw), (m[1], fh)):
+        with np.errstate(all="ignore"):
+            first = np.clip((_sat_int((mr * ey + mt) * 1024.0)[:, None] + 16 + _sat_int(mc * ex * 1024.0)[None, :]) >> 10, -32768, 32767)
+            real = mc * cx + mr * cy + mt
+        lo, hi = int(first.min()), int(first.max()) + 2
+        if np.isfinite(real).all():                     # (finite entries can still overflow in the sum: then the exact box alone)
+            real = np.clip(real, -2.0 ** 31, 2.0 ** 31)
+            lo = min(lo, int(np.floor(real.min())) - 2); hi = max(hi, int(np.ceil(real.max())) + 3)
+        lo = min(max(lo, 0), size); hi = min(max(hi, 0), size)
+        win.append((lo, max(hi - lo, 0)))
+    return [win[0][0], win[1][0], win[0][1], win[1][1]]
 
 
 def basic_block(conv1, conv2, xb):

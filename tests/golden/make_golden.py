@@ -24,7 +24,7 @@ container (it never ships; /root/reference does not exist on the GPU box):
     unpinned (no OpenCV here).
 
   * lib/utils/transforms.py (get_affine_transform, affine_transform :57-95) -- the crop's affine and the joints mapped through it
-    (affine_reference_outputs.npz).
+    (affine_reference_outputs.npz), and the same affine with rot != 0 (affine_rot_reference_outputs.npz).
 
   * lib/dataset/events.py (_xywh2cs :94-113) and lib/dataset/JointsDataset.py (generate_target :264-332), called unbound
     (dataset_reference_outputs.npz).
@@ -261,6 +261,24 @@ def affine_vectors():
     mapped = np.stack([np.stack([tr.affine_transform(pts[i, j], fwd[i]) for j in range(11)]) for i in range(n)])
     np.savez_compressed(os.path.join(HERE, "affine_reference_outputs.npz"), center=c, scale=s, sizes=sizes, points=pts, forward=fwd, inverse=inv, mapped=mapped)
     print("affine vectors", fwd.shape, float(np.abs(fwd).max()))
+
+
+def affine_rot_vectors():
+    """get_affine_transform of lib/utils/transforms.py:57-89 with rot != 0 (the branch through get_dir :103-110), made the way
+    affine_vectors makes the rot = 0 rows: forward and inverse for seeded centres / scales / output sizes at rot 30, -75, 90 and 180
+    (affine_rot_reference_outputs.npz)."""
+    install_cv2_stub()
+    tr = importlib.import_module("utils.transforms")
+    rng = np.random.default_rng(12)
+    n = 24
+    c = (rng.random((n, 2)) * np.array([1920, 1200]) * 1.2 - 100).astype(np.float32)
+    s = (rng.random((n, 2)) * 4.0 + 0.1).astype(np.float32)
+    sizes = np.array([(384, 384), (256, 256), (768, 768), (96, 128), (64, 48)])[rng.integers(0, 5, n)]
+    rot = np.array([30.0, -75.0, 90.0, 180.0])[np.arange(n) % 4]
+    fwd = np.stack([tr.get_affine_transform(c[i], s[i], rot[i], sizes[i]) for i in range(n)])
+    inv = np.stack([tr.get_affine_transform(c[i], s[i], rot[i], sizes[i], inv=1) for i in range(n)])
+    np.savez_compressed(os.path.join(HERE, "affine_rot_reference_outputs.npz"), center=c, scale=s, sizes=sizes, rot=rot, forward=fwd, inverse=inv)
+    print("affine rot vectors", fwd.shape, float(np.abs(fwd).max()))
 
 
 def dataset_vectors():
@@ -721,6 +739,7 @@ if __name__ == "__main__":
     decode_vectors()
     host_vectors()
     affine_vectors()
+    affine_rot_vectors()
     dataset_vectors()
     naming_vectors()
     driver_vectors()

@@ -284,15 +284,55 @@ def test_mat_v5_writer_and_reader_interoperate_with_scipy(tmp_path):
         M.savemat(tmp_path / "e.mat", {"s": np.array(["text"])})
 
 
-def test_warp_window_contains_every_tap_of_the_fixed_point_warp():
-    """ops.warp_window (what the loader ships to scpose_crop_warp_roi): every in-frame tap of cv2.warpAffine's fixed-point coordinate
-    computation (csrc/crop.hip: X = (round((M1 y + M2) 1024) + 16 + round(M0 x 1024)) >> 5, taps (X >> 5, X >> 5 + 1)) lies inside
-    the window, for boxes inside, across and outside the frame and for scales from 0.1 to 4."""
-    import numpy as np
+def _crop_modules():
     import scpose  # noqa: F401
     from importlib import import_module
-    T = import_module("spacecraft-pose-estimation_amd.utils.transforms")
-    ops = import_module("spacecraft-pose-estimation_amd.ops")
+    import affine_cases as A
+    return A, import_module("spacecraft-pose-estimation_amd.utils.transforms"), import_module("spacecraft-pose-estimation_amd.ops")
+
+
+def _affine_family():
+    """[(label, frame size, crop (W, H), forward matrix)]: tests/affine_cases.py at both frame sizes, and the tall crop at the small one"""
+    A = _crop_modules()[0]
+    return [("%s@%dx%d>%dx%d" % (name, size[1], size[0], wh[0], wh[1]), name, size, wh, t)
+            for size, wh in ((A.SIZES[0], A.CROP_WH), (A.SIZES[1], A.CROP_WH), (A.SIZES[1], A.TALL_WH)) for name, t in A.affines(size, wh).items()]
+
+
+def _window_before_saturation(T, t, ow, oh, fh, fw):
+    """ops.warp_window as it was before it learned of saturation: the real-valued corners with margins -2 / +3, clipped to the frame"""
+    m = np.asarray(T.invert_affine_cv(t), dtype=np.float64).reshape(2, 3)
+    cx = np.array([0.0, ow - 1.0, 0.0, ow - 1.0]); cy = np.array([0.0, 0.0, oh - 1.0, oh - 1.0])
+    sx = m[0, 0] * cx + m[0, 1] * cy + m[0, 2]; sy = m[1, 0] * cx + m[1, 1] * cy + m[1, 2]
+    x0 = min(max(int(np.floor(sx.min())) - 2, 0), fw); x1 = min(max(int(np.ceil(sx.max())) + 3, 0), fw)
+    y0 = min(max(int(np.floor(sy.min())) - 2, 0), fh); y1 = min(max(int(np.ceil(sy.max())) + 3, 0), fh)
+    return [x0, y0, max(x1 - x0, 0), max(y1 - y0, 0)]
+
+
+def _taps_outside_window(T, t, ow, oh, fh, fw, win):
+    """how many in-frame taps of the kernel's coordinate computation (csrc/bilinear_fixed.h: affine_source, with the int32 saturation
+    of both terms and the int16 clip of the pixel index) lie outside win = [x0, y0, w, h]"""
+    m = np.asarray(T.invert_affine_cv(t), dtype=np.float64).reshape(6)
+    xs = np.arange(ow, dtype=np.float64)[None, :]; ys = np.arange(oh, dtype=np.float64)[:, None]
+    X = (T._sat_int((m[1] * ys + m[2]) * 1024.0) + 16 + T._sat_int(m[0] * xs * 1024.0)) >> 5
+    Y = (T._sat_int((m[4] * ys + m[5]) * 1024.0) + 16 + T._sat_int(m[3] * xs * 1024.0)) >> 5
+    x0, y0 = np.clip(X >> 5, -32768, 32767), np.clip(Y >> 5, -32768, 32767)
+    rx, ry, rw, rh = win
+    missed = 0
+    for dx in (0, 1):
+        for dy in (0, 1):
+            xx, yy = x0 + dx, y0 + dy
+            inside = (xx >= 0) & (xx < fw) & (yy >= 0) & (yy < fh)
+            missed += int((~((xx[inside] >= rx) & (xx[inside] < rx + rw) & (yy[inside] >= ry) & (yy[inside] < ry + rh))).sum())
+    return missed
+
+
+def test_warp_window_contains_every_tap_of_the_fixed_point_warp():
+    """ops.warp_window (what the loader ships to scpose_crop_warp_roi): every in-frame tap of cv2.warpAffine's fixed-point coordinate
+    computation (csrc/crop.hip: X = (sat((M1 y + M2) 1024) + 16 + sat(M0 x 1024)) >> 5, taps (clip16(X >> 5), .. + 1)) lies inside
+    the window: for boxes inside, across and outside the frame at scales from 0.1 to 4; for the family of tests/affine_cases.py (cross
+    terms, reflections, a singular map, saturating coordinates); for seeded general affines (any rotation, shear in [-1, 1], either
+    sign, scales over e^+-2.5).  Wherever nothing saturates the window is the one warp_window returned before it knew of saturation."""
+    A, T, ops = _crop_modules()
     rng = np.random.default_rng(3)
     for k in range(200):
         fh, fw = int(rng.integers(40, 1300)), int(rng.integers(40, 2000))
@@ -300,18 +340,127 @@ def test_warp_window_contains_every_tap_of_the_fixed_point_warp():
         s = np.float32(rng.uniform(0.1, 4.0)) * np.ones(2, np.float32)
         ow, oh = (96, 128) if k % 2 else (384, 384)
         t = T.get_affine_transform(c, s, 0, np.array([ow, oh]))
-        m = np.asarray(T.invert_affine_cv(t), dtype=np.float64).reshape(6)
-        xs = np.arange(ow, dtype=np.float64)[None, :]; ys = np.arange(oh, dtype=np.float64)[:, None]
-        X = (np.rint((m[1] * ys + m[2]) * 1024.0).astype(np.int64) + 16 + np.rint(m[0] * xs * 1024.0).astype(np.int64)) >> 5
-        Y = (np.rint((m[4] * ys + m[5]) * 1024.0).astype(np.int64) + 16 + np.rint(m[3] * xs * 1024.0).astype(np.int64)) >> 5
-        x0, y0 = X >> 5, Y >> 5
-        rx, ry, rw, rh = ops.warp_window(t, (ow, oh), (fh, fw))
-        for dx in (0, 1):
-            for dy in (0, 1):
-                xx, yy = x0 + dx, y0 + dy
-                inside = (xx >= 0) & (xx < fw) & (yy >= 0) & (yy < fh)
-                assert ((xx[inside] >= rx) & (xx[inside] < rx + rw) & (yy[inside] >= ry) & (yy[inside] < ry + rh)).all(), (k, fh, fw, c, s)
+        win = ops.warp_window(t, (ow, oh), (fh, fw))
+        assert _taps_outside_window(T, t, ow, oh, fh, fw, win) == 0, (k, fh, fw, c, s)
+        rx, ry, rw, rh = win
         assert 0 <= rx <= fw and 0 <= ry <= fh and rx + rw <= fw and ry + rh <= fh
+        assert win == _window_before_saturation(T, t, ow, oh, fh, fw), (k, fh, fw, c, s)
+    for label, name, (fh, fw), (ow, oh), t in _affine_family():
+        win = ops.warp_window(t, (ow, oh), (fh, fw))
+        assert _taps_outside_window(T, t, ow, oh, fh, fw, win) == 0, label
+        assert 0 <= win[0] and 0 <= win[1] and win[0] + win[2] <= fw and win[1] + win[3] <= fh, label
+        assert (win[2] == 0 or win[3] == 0) == (name in A.EMPTY), (label, win)
+        if name not in A.SATURATING:
+            assert win == _window_before_saturation(T, t, ow, oh, fh, fw), label
+    rng = np.random.default_rng(31)
+    for k in range(300):
+        fh, fw = ((97, 131), (int(rng.integers(40, 1300)), int(rng.integers(40, 2000))))[k % 2]
+        ow, oh = ((96, 128), (64, 48), (33, 57))[k % 3]
+        sign = (1.0, -1.0)[int(rng.integers(0, 2))]
+        lin = A.rotation(rng.uniform(0.0, 360.0), np.exp(rng.uniform(-2.5, 2.5)), sign * np.exp(rng.uniform(-2.5, 2.5)))
+        lin = lin @ np.array([[1.0, rng.uniform(-1.0, 1.0)], [0.0, 1.0]])
+        t = A.forward(A.about(lin, ((ow - 1) / 2.0, (oh - 1) / 2.0), (rng.uniform(-0.2, 1.2) * fw, rng.uniform(-0.2, 1.2) * fh)))
+        win = ops.warp_window(t, (ow, oh), (fh, fw))
+        assert _taps_outside_window(T, t, ow, oh, fh, fw, win) == 0, (k, t.tolist())
+        assert 0 <= win[0] and 0 <= win[1] and win[0] + win[2] <= fw and win[1] + win[3] <= fh
+        assert win == _window_before_saturation(T, t, ow, oh, fh, fw), (k, t.tolist())
+
+
+def test_warp_restatement_equals_the_scalar_oracle_and_the_known_answers_on_general_affines():
+    """utils.transforms.warp_affine_bilinear on tests/affine_cases.py: equal to the scalar restatement oracle/warp_ref.py on every case, and
+    to the NumPy expression of the cases that have one (a transpose is frame.transpose, a half turn frame[::-1, ::-1], ...) -- answers
+    that depend on neither restatement.  The singular map reads frame[0, 0] everywhere; the fold cases read the frame, the others that
+    leave it are zero."""
+    from oracle import warp_ref as W
+    A, T, _ = _crop_modules()
+    frames = {size: A.random_frame(size, 5 + size[0]) for size in A.SIZES}
+    known = {}
+    for label, name, size, wh, t in _affine_family():
+        got = T.warp_affine_bilinear(frames[size], t, wh)
+        assert np.array_equal(got, W.warp_affine_linear_u8(frames[size], t, wh)), label
+        if name in A.KNOWN:
+            if (size, wh) not in known:
+                known[size, wh] = A.known_answers(frames[size], wh)
+            assert np.array_equal(got, known[size, wh][name]), label
+            assert got.all() or size == A.SIZES[1], label                        # the large frame holds the whole crop of each of them
+        if name == "singular":
+            assert (got == frames[size][0, 0]).all(), label
+        if name in A.EMPTY:
+            assert not got.any(), label
+        if name in A.FOLD:
+            assert got.any(), label
+    assert len(known) == 3 and all(sorted(v) == sorted(A.KNOWN) for v in known.values())
+
+
+def test_the_window_is_a_mask_the_warp_does_not_notice():
+    """what scpose_crop_warp_roi and the decoders' crop tail do with ops.warp_window: a tap outside the window counts as 0.  On every case
+    of tests/affine_cases.py the restatement on the frame zeroed outside the window (and on the frame set to 0xFF there: no tap reads it)
+    equals the restatement on the whole frame.  The fold cases need the window to follow the saturated integers."""
+    A, T, ops = _crop_modules()
+    frames = {size: A.random_frame(size, 9 + size[0]) for size in A.SIZES}
+    for label, name, size, wh, t in _affine_family():
+        x0, y0, rw, rh = ops.warp_window(t, wh, size)
+        want = T.warp_affine_bilinear(frames[size], t, wh)
+        for poison in (0x00, 0xFF):
+            f = np.full_like(frames[size], poison)
+            f[y0:y0 + rh, x0:x0 + rw] = frames[size][y0:y0 + rh, x0:x0 + rw]
+            assert np.array_equal(T.warp_affine_bilinear(f, t, wh), want), (label, poison)
+        assert want.any() == (name not in A.EMPTY), label
+
+
+def test_warp_window_refuses_a_non_finite_transform():
+    """the device's cast of a NaN and NumPy's differ: no defined window, ValueError naming the row"""
+    _, _, ops = _crop_modules()
+    for bad in (np.nan, np.inf, -np.inf):
+        for k in range(6):
+            t = np.array([[1.0, 0.0, 3.0], [0.0, 1.0, 4.0]])
+            t.flat[k] = bad
+            with pytest.raises(ValueError, match="warp_window: transform 0"):
+                ops.warp_window(t, (32, 24), (67, 130))
+    with pytest.raises(ValueError, match="warp_window: the inverse map of transform 0"):
+        ops.warp_window(np.array([[1e-160, 0.0, 1.0], [0.0, 1e-160, 1.0]]), (32, 24), (67, 130))     # 1 / determinant overflows
+    assert ops.warp_window(np.array([[1.0, 0.0, 3.0], [0.0, 1.0, 4.0]]), (32, 24), (67, 130)) == [0, 0, 31, 22]
+
+
+def test_get_affine_transform_with_rotation():
+    """utils.transforms.get_affine_transform (and the oracle's copy) for rot != 0: the three point pairs it constructs -- the centre, the
+    point half a box width above it turned by rot, and the third point at a right angle -- map onto their targets, which is what defines
+    cv2.getAffineTransform; inv=1 composes with the forward map to the identity; the two copies agree; and both equal the reference's own
+    lib/utils/transforms.py:57-89 (tests/golden/affine_rot_reference_outputs.npz, make_golden.py: affine_rot_vectors)."""
+    _, T, _ = _crop_modules()
+    from oracle import decode_ref as D
+    f32 = np.float32
+
+    def close(a, b):
+        return np.abs(np.asarray(a) - np.asarray(b)).max() <= 1e-9 * max(1.0, np.abs(b).max())
+
+    def third(a, b):
+        return b + np.array([-(a - b)[1], (a - b)[0]], dtype=f32)
+    for rot in (30, -75, 90, 180):
+        for c, s, size in (((960.0, 600.0), (1.2, 1.2), (384, 384)), ((31.5, 20.25), (0.3, 0.45), (96, 128)), ((-40.0, 1250.0), (4.0, 2.5), (64, 48)),
+                           ((1900.0, 3.0), (0.11, 0.11), (256, 256))):
+            c, s = np.array(c, f32), np.array(s, f32)
+            r = np.pi * rot / 180
+            half = float(s[0] * f32(200.0)) * -0.5
+            src, dst = np.zeros((3, 2), f32), np.zeros((3, 2), f32)
+            src[0] = c; src[1] = c + np.array([-half * np.sin(r), half * np.cos(r)]); src[2] = third(src[0], src[1])
+            dst[0] = [size[0] * 0.5, size[1] * 0.5]; dst[1] = np.array([size[0] * 0.5, size[1] * 0.5]) + np.array([0, size[0] * -0.5], f32)
+            dst[2] = third(dst[0], dst[1])
+            fwd, inv = T.get_affine_transform(c, s, rot, size), T.get_affine_transform(c, s, rot, size, inv=1)
+            for i in range(3):
+                assert close(fwd @ np.array([src[i, 0], src[i, 1], 1.0]), dst[i].astype(np.float64)), (rot, c, i)
+                assert close(inv @ np.array([dst[i, 0], dst[i, 1], 1.0]), src[i].astype(np.float64)), (rot, c, i)
+            both = np.vstack([fwd, [0, 0, 1]]) @ np.vstack([inv, [0, 0, 1]])
+            assert close(both, np.eye(3)), (rot, c)
+            assert close(D.get_affine_transform(c, s, rot, size), fwd) and close(D.get_affine_transform(c, s, rot, size, inv=1), inv)
+            assert abs(fwd[0, 1]) > 1e-3 or rot == 180                             # the cross terms act
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "affine_rot_reference_outputs.npz"))
+    assert sorted(set(g["rot"].tolist())) == [-75.0, 30.0, 90.0, 180.0]
+    for i in range(len(g["rot"])):
+        c, s, size, rot = g["center"][i], g["scale"][i], g["sizes"][i], float(g["rot"][i])
+        for mod in (T, D):
+            assert close(mod.get_affine_transform(c, s, rot, size), g["forward"][i]), (mod.__name__, i)
+            assert close(mod.get_affine_transform(c, s, rot, size, inv=1), g["inverse"][i]), (mod.__name__, i)
 
 
 def test_crop_affine_equals_the_reference_get_affine_transform():
