@@ -89,6 +89,17 @@ struct Carve {
   size_t bytes() const { return off; }
 };
 
+// Little-endian loads from a byte position of any alignment (file formats: payloads start wherever the bytes before them end)
+__device__ __forceinline__ uint32_t ld16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
+template <class T>
+__device__ __forceinline__ T ld_as(const uint8_t* p) {
+  T v;
+  __builtin_memcpy(&v, p, sizeof(T));
+  return v;
+}
+__device__ __forceinline__ uint32_t ld32(const uint8_t* p) { return ld_as<uint32_t>(p); }
+__device__ __forceinline__ int64_t ld64(const uint8_t* p) { return ld_as<int64_t>(p); }
+
 // ---- 32-bit buffer descriptors ---------------------------------------------------------------
 // The convolution kernels address their tensors through raw buffer descriptors (conv_pipe_kernel.h: make_buf): base + 32-bit
 // offset, num_records = the tensor's bytes, which must stay below kBufLimit -- the offset given to padding lanes (BUF_OOB) has

@@ -22,45 +22,28 @@
 //                          population count and summed per workgroup -> count, the t of the packet's first and last valid event,
 //                          status (a negative ts, a count that differs from the header's eventValid, which sits 4 bytes before
 //                          the payload).
-//   aedat3_counts_kernel   one workgroup, scan_device.h: event offsets, n_events, status, the first time stamp; the previous
-//                          packet that holds a valid event by a min-scan, as events_aedat4_read.hip finds it.
+//   aedat3_counts_kernel   one workgroup, packet_counts of events_packets.h: event offsets, n_events, status, the first time stamp,
+//                          the previous packet that holds a valid event.
 //   aedat3_unpack_kernel   one workgroup per packet, 256 events at a time: a lane's row is the packet's offset, plus the valid
 //                          events of the earlier 64-event groups, plus the population count of the ballot below the lane.
+// The counts step, the gate and the tally of the unpack step, the time before a packet and the workspace plan are the ones the
+// AEDAT-4.0 reader uses too: events_packets.h states them once.
 // The kernels DETECT a damaged packet and never interpret one: every read is checked against eventNumber * 8 bytes, every store
 // against the rows the count step gave the packet.  Integer work on fixed positions: two runs are bitwise equal.
-#include "common.h"
-#include "scan_device.h"
+#include "events_packets.h"
 
 namespace scpose {
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / kWave;
-static_assert(kThreads == kScanThreads, "the scan bodies of scan_device.h run in the workgroups of this file");
 constexpr int kMaxCount = (1 << 23) - 1;             // events of one packet: scan_tile_counts sums 256 counts in an int32
 static_assert(256ll * kMaxCount <= INT_MAX, "scan_tile_counts sums 256 counts in an int32");
 
 // event j of a payload; the payload starts wherever the header's text and the packets before it end, so no alignment is assumed
-__device__ __forceinline__ uint2 ld_event(const uint8_t* ev, int32_t j) {
-  uint2 v;
-  __builtin_memcpy(&v, ev + 8 * (int64_t)j, 8);
-  return v;
-}
+__device__ __forceinline__ uint2 ld_event(const uint8_t* ev, int32_t j) { return ld_as<uint2>(ev + 8 * (int64_t)j); }
 
 __device__ __forceinline__ int64_t event_t(int64_t overflow, uint32_t ts) { return (overflow << 31) | (int64_t)ts; }
-
-__device__ __forceinline__ int block_or(int v, int32_t* lds) {
-  __syncthreads();
-  if (threadIdx.x == 0) lds[0] = 0;
-  __syncthreads();
-  if (v) atomicOr(&lds[0], v);
-  __syncthreads();
-  const int r = lds[0];
-  __syncthreads();
-  return r;
-}
 
 // one workgroup per packet -> count[pk], first_t[pk], last_t[pk] (of the valid events; 0 without one), status[pk]
 __global__ __launch_bounds__(kThreads) void aedat3_count_kernel(const uint8_t* __restrict__ file, const int64_t* __restrict__ packets,
@@ -114,8 +97,7 @@ __global__ __launch_bounds__(kThreads) void aedat3_count_kernel(const uint8_t* _
   if (first_j != INT_MAX && first_j == s_first) first_t[pk] = event_t(overflow, first_ts);
   if (last_j >= 0 && last_j == s_last) last_t[pk] = event_t(overflow, last_ts);
   if (threadIdx.x == 0) {
-    int32_t stated;
-    __builtin_memcpy(&stated, ev - 4, 4);            // the header's eventValid
+    const int32_t stated = ld_as<int32_t>(ev - 4);   // the header's eventValid
     const int32_t s = s_status | (stated != s_count ? SCPOSE_AEDAT3_VALID_MISMATCH : 0);
     count[pk] = s ? 0 : s_count;
     status[pk] = s;
@@ -123,32 +105,12 @@ __global__ __launch_bounds__(kThreads) void aedat3_count_kernel(const uint8_t* _
   }
 }
 
-// one workgroup: event offsets, count_status <- [n_events, status, t0, 0, 0, 0]; prev[i] <- minus the index of the last packet
-// before i that holds a valid event (INT_MAX: none), an exclusive min-scan as events_aedat4_read.hip's; `scratch` serves the
-// min-scan whose total is the first packet that holds one
+// one workgroup: packet_counts of events_packets.h; t0 is 0 when the status is set
 __global__ __launch_bounds__(kThreads) void aedat3_counts_kernel(const int32_t* count, const int32_t* status, const int64_t* first_t,
                                                                  int64_t n, int64_t* ev_off, int32_t* prev, int32_t* scratch,
                                                                  int64_t* count_status) {
   __shared__ int32_t sc[kThreads];
-  int st = 0;
-  for (int64_t i = threadIdx.x; i < n; i += kThreads) {
-    st |= status[i];
-    prev[i] = count[i] ? -(int32_t)i : INT_MAX;
-    scratch[i] = count[i] ? (int32_t)i : INT_MAX;
-  }
-  __syncthreads();
-  const int64_t total = scan_tile_counts(count, n, ev_off, sc);
-  scan_aggregates<1>(prev, n, sc);
-  const int32_t first = scan_aggregates<1>(scratch, n, sc);
-  st = block_or(st, sc);
-  if (threadIdx.x == 0) {
-    count_status[0] = st ? 0 : total;
-    count_status[1] = st;
-    count_status[2] = (!st && first != INT_MAX) ? first_t[first] : 0;
-    count_status[3] = 0;
-    count_status[4] = 0;
-    count_status[5] = 0;
-  }
+  packet_counts(count, status, first_t, n, ev_off, prev, scratch, count_status, false, sc);
 }
 
 // one workgroup per packet; nothing is written unless the status word is 0 and the columns hold n_events rows
@@ -162,12 +124,7 @@ __global__ __launch_bounds__(kThreads) void aedat3_unpack_kernel(const uint8_t* 
   __shared__ int32_t s_cnt[2][kWaves];
   __shared__ int64_t s_last[2][kWaves];
   __shared__ int32_t s_red[2];
-  if ((count_status[1] & ~(int64_t)SCPOSE_AEDAT3_RANGE) != 0) return;
-  if (count_status[0] > capacity) {
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-      atomicOr(reinterpret_cast<unsigned long long*>(count_status) + 1, (unsigned long long)SCPOSE_AEDAT3_CAPACITY);
-    return;
-  }
+  if (!unpack_gate(count_status, capacity, SCPOSE_AEDAT3_RANGE, SCPOSE_AEDAT3_CAPACITY)) return;
   const int pk = blockIdx.x;
   const int32_t rows = count[pk];                    // the status is 0: eventNumber is within 0 .. kMaxCount
   if (rows == 0) return;
@@ -177,11 +134,9 @@ __global__ __launch_bounds__(kThreads) void aedat3_unpack_kernel(const uint8_t* 
   const int64_t row0 = ev_off[pk], sub = rebase ? count_status[2] : 0;
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
   const unsigned long long below_me = (1ull << lane) - 1;
-  if (threadIdx.x == 0) s_red[0] = s_red[1] = 0;
-  // the valid event before this packet's first: the last one of the previous packet that holds any
-  const int32_t q = prev[pk];
-  bool have_before = q != INT_MAX;                   // uniform, as `before` and `run` are
-  int64_t before = have_before ? last_t[-(int64_t)q] : 0;
+  const TimeBefore tb = time_before_packet(prev, last_t, pk);
+  bool have_before = tb.have;                        // uniform, as `before` and `run` are
+  int64_t before = tb.t;
   int32_t run = 0;                                   // valid events of the chunks done
   int32_t nback = 0, nout = 0;
   for (int32_t j0 = 0, buf = 0; j0 < num; j0 += kThreads, buf ^= 1) {
@@ -228,36 +183,16 @@ __global__ __launch_bounds__(kThreads) void aedat3_unpack_kernel(const uint8_t* 
       }
     }
   }
-  if (nback) atomicAdd(&s_red[0], nback);
-  if (nout) atomicAdd(&s_red[1], nout);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long* cs = reinterpret_cast<unsigned long long*>(count_status);
-    if (s_red[0]) atomicAdd(cs + 3, (unsigned long long)s_red[0]);
-    if (s_red[1]) {
-      atomicAdd(cs + 4, (unsigned long long)s_red[1]);
-      atomicOr(cs + 1, (unsigned long long)SCPOSE_AEDAT3_RANGE);
-    }
-  }
+  unpack_tally(nback, nout, s_red, count_status, SCPOSE_AEDAT3_RANGE);
 }
 
-struct Plan {
-  int32_t *count, *status, *prev, *scratch;
-  int64_t *ev_off, *first_t, *last_t;
+struct Plan : PacketPlan {
   size_t bytes;
 };
 
 Plan plan(int64_t n, uint8_t* wsp) {
-  Plan p{};
-  const size_t cnt = (size_t)(n > 0 ? n : 1);        // never an empty workspace
   Carve c{wsp};
-  p.count = c.take<int32_t>(cnt);
-  p.status = c.take<int32_t>(cnt);
-  p.prev = c.take<int32_t>(cnt);
-  p.scratch = c.take<int32_t>(cnt);
-  p.ev_off = c.take<int64_t>(cnt);
-  p.first_t = c.take<int64_t>(cnt);
-  p.last_t = c.take<int64_t>(cnt);
+  Plan p{packet_plan(c, packet_plan_count(n), true), 0};
   p.bytes = c.bytes();
   return p;
 }

@@ -33,21 +33,19 @@
 //                             before a match's loads the wave waits for its own stores (own_stores_done below).  Block and content
 //                             checksums are verified when asked.  Under NONE none of these three run: the staging buffer is the file.
 //   aedat4_count_kernel       one thread per packet: the flatbuffer walk down to the vector's count.
-//   aedat4_counts_kernel      one workgroup: event offsets, n_events, status, the first time stamp.
+//   aedat4_counts_kernel      one workgroup, packet_counts of events_packets.h: event offsets, n_events, status, the first time stamp.
 //   aedat4_unpack_kernel      one workgroup per packet: 16-byte struct loads, lane after lane, to the four columns in file order.
+// The counts step, the gate and the tally of the unpack step, the time before a packet and the shared part of the workspace plan are
+// the ones the AEDAT-3.1 reader uses too: events_packets.h states them once.
 // The kernels DETECT a damaged stream and never interpret one: every read is checked against the payload, every match against the
 // output produced so far, every store against the measured size.  Integer work on fixed positions: two runs are bitwise equal.
-#include "common.h"
-#include "scan_device.h"
+#include "events_packets.h"
 #include "xxh32_wave.h"
 
 namespace scpose {
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kThreads = 256;
-static_assert(kThreads == kScanThreads, "the scan bodies of scan_device.h run in the workgroups of this file");
 constexpr int kInWin = 4096;                         // input window in LDS, bytes
 constexpr int kMaxDecoded = kAedat4MaxDecoded;      // decoded bytes of one packet: 256 of them, each rounded up to 16, sum within int32
 static_assert(256ll * ((kMaxDecoded + 15) & ~15) <= INT_MAX, "scan_tile_counts sums 256 padded sizes in an int32");
@@ -215,17 +213,6 @@ __global__ __launch_bounds__(kWave) void aedat4_lz4_kernel(const uint8_t* __rest
   }
 }
 
-__device__ __forceinline__ int block_or(int v, int32_t* lds) {
-  __syncthreads();
-  if (threadIdx.x == 0) lds[0] = 0;
-  __syncthreads();
-  if (v) atomicOr(&lds[0], v);
-  __syncthreads();
-  const int r = lds[0];
-  __syncthreads();
-  return r;
-}
-
 // one workgroup: size[i] rounded up to 16 (in place), their exclusive scan -> off, total_status <- [staging bytes, status]
 __global__ __launch_bounds__(kThreads) void aedat4_sizes_kernel(int32_t* size, int32_t* padded, const int32_t* status, int64_t n,
                                                                 int64_t* off, int64_t* total_status) {
@@ -242,13 +229,6 @@ __global__ __launch_bounds__(kThreads) void aedat4_sizes_kernel(int32_t* size, i
     total_status[0] = total;
     total_status[1] = st;
   }
-}
-
-__device__ __forceinline__ uint32_t ld16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
-__device__ __forceinline__ int64_t ld64(const uint8_t* p) {
-  int64_t v;
-  __builtin_memcpy(&v, p, 8);
-  return v;
 }
 
 // one thread per packet.  The payload of packet i: (packets[2 i], packets[2 i + 1]) of `src` when size is null (NONE: src is the
@@ -303,33 +283,12 @@ __global__ __launch_bounds__(kThreads) void aedat4_count_kernel(const uint8_t* _
   status[i] = st0 | ((ok || st0) ? 0 : SCPOSE_AEDAT4_FLATBUFFER);
 }
 
-// one workgroup: event offsets, count_status <- [n_events, status, t0, 0, 0, 0]; prev[i] <- minus the index of the last packet
-// before i that holds an event (INT_MAX: none), an exclusive min-scan as events_aedat2_read.hip's; `scratch` serves the min-scan
-// whose total is the first packet that holds one
+// one workgroup: packet_counts of events_packets.h; t0 is the first event's time whatever the status
 __global__ __launch_bounds__(kThreads) void aedat4_counts_kernel(const int32_t* count, const int32_t* status, const int64_t* first_t,
                                                                  int64_t n, int64_t* ev_off, int32_t* prev, int32_t* scratch,
                                                                  int64_t* count_status) {
   __shared__ int32_t sc[kThreads];
-  int st = 0;
-  for (int64_t i = threadIdx.x; i < n; i += kThreads) {
-    st |= status[i];
-    prev[i] = count[i] ? -(int32_t)i : INT_MAX;
-    scratch[i] = count[i] ? (int32_t)i : INT_MAX;
-  }
-  __syncthreads();
-  const int64_t total = scan_tile_counts(count, n, ev_off, sc);
-  scan_aggregates<1>(prev, n, sc);
-  const int32_t first = scan_aggregates<1>(scratch, n, sc);
-  st = block_or(st, sc);
-  if (threadIdx.x == 0) {
-    const int64_t t0 = first != INT_MAX ? first_t[first] : 0;
-    count_status[0] = st ? 0 : total;
-    count_status[1] = st;
-    count_status[2] = t0;
-    count_status[3] = 0;
-    count_status[4] = 0;
-    count_status[5] = 0;
-  }
+  packet_counts(count, status, first_t, n, ev_off, prev, scratch, count_status, true, sc);
 }
 
 // one workgroup per packet; nothing is written unless the status word is 0 and the columns hold n_events rows
@@ -341,31 +300,20 @@ __global__ __launch_bounds__(kThreads) void aedat4_unpack_kernel(const uint8_t* 
                                                                  int32_t* __restrict__ y_out, int8_t* __restrict__ p_out,
                                                                  int64_t capacity, int64_t* count_status) {
   __shared__ int32_t s_red[2];
-  if ((count_status[1] & ~(int64_t)SCPOSE_AEDAT4_RANGE) != 0) return;
-  if (count_status[0] > capacity) {
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-      atomicOr(reinterpret_cast<unsigned long long*>(count_status) + 1, (unsigned long long)SCPOSE_AEDAT4_CAPACITY);
-    return;
-  }
+  if (!unpack_gate(count_status, capacity, SCPOSE_AEDAT4_RANGE, SCPOSE_AEDAT4_CAPACITY)) return;
   const int pk = blockIdx.x;
   const int32_t cnt = count[pk];
   if (cnt == 0) return;
   const uint8_t* ev = src + data[pk];
   const int64_t row0 = ev_off[pk], sub = rebase ? count_status[2] : 0;
-  if (threadIdx.x == 0) s_red[0] = s_red[1] = 0;
-  __syncthreads();
   int32_t nback = 0, nout = 0;
   for (int32_t j = threadIdx.x; j < cnt; j += kThreads) {
-    uint4 v;
-    __builtin_memcpy(&v, ev + 16 * (int64_t)j, 16);
+    const uint4 v = ld_as<uint4>(ev + 16 * (int64_t)j);
     const int64_t t = (int64_t)(((unsigned long long)v.y << 32) | v.x);
-    int64_t before;
-    if (j > 0) before = ld64(ev + 16 * (int64_t)(j - 1));
-    else {
-      const int32_t q = prev[pk];
-      before = q != INT_MAX ? last_t[-(int64_t)q] : t;
-    }
-    nback += t < before;
+    TimeBefore tb{true, 0};                          // the event before this one: the struct before it, or another packet's last
+    if (j > 0) tb.t = ld64(ev + 16 * (int64_t)(j - 1));
+    else tb = time_before_packet(prev, last_t, pk);
+    nback += tb.have && t < tb.t;
     const int32_t x = (int16_t)(v.z & 0xFFFFu), y = (int16_t)(v.z >> 16);
     nout += x < 0 || x >= w || y < 0 || y >= h;
     t_out[row0 + j] = t - sub;
@@ -373,39 +321,24 @@ __global__ __launch_bounds__(kThreads) void aedat4_unpack_kernel(const uint8_t* 
     y_out[row0 + j] = y;
     p_out[row0 + j] = (int8_t)((v.w & 0xFFu) != 0);
   }
-  if (nback) atomicAdd(&s_red[0], nback);
-  if (nout) atomicAdd(&s_red[1], nout);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long* cs = reinterpret_cast<unsigned long long*>(count_status);
-    if (s_red[0]) atomicAdd(cs + 3, (unsigned long long)s_red[0]);
-    if (s_red[1]) {
-      atomicAdd(cs + 4, (unsigned long long)s_red[1]);
-      atomicOr(cs + 1, (unsigned long long)SCPOSE_AEDAT4_RANGE);
-    }
-  }
+  unpack_tally(nback, nout, s_red, count_status, SCPOSE_AEDAT4_RANGE);
 }
 
-struct Plan {
-  int32_t *size, *padded, *status, *count, *prev;
-  int64_t *off, *data, *ev_off, *first_t, *last_t;
+// the shared arrays and the LZ4 side's; `scratch` is `padded`, which is free once the staging offsets are scanned
+struct Plan : PacketPlan {
+  int32_t *size, *padded;
+  int64_t *off, *data;
   size_t bytes;
 };
 
 Plan plan(int64_t n, uint8_t* wsp) {
-  Plan p{};
-  const size_t cnt = (size_t)(n > 0 ? n : 1);        // never an empty workspace
+  const size_t cnt = packet_plan_count(n);
   Carve c{wsp};
+  Plan p{packet_plan(c, cnt, false), nullptr, nullptr, nullptr, nullptr, 0};
   p.size = c.take<int32_t>(cnt);
-  p.padded = c.take<int32_t>(cnt);
-  p.status = c.take<int32_t>(cnt);
-  p.count = c.take<int32_t>(cnt);
-  p.prev = c.take<int32_t>(cnt);
+  p.scratch = p.padded = c.take<int32_t>(cnt);
   p.off = c.take<int64_t>(cnt);
   p.data = c.take<int64_t>(cnt);
-  p.ev_off = c.take<int64_t>(cnt);
-  p.first_t = c.take<int64_t>(cnt);
-  p.last_t = c.take<int64_t>(cnt);
   p.bytes = c.bytes();
   return p;
 }
@@ -444,7 +377,7 @@ int32_t events_aedat4_count_launch(const uint8_t* src, const int64_t* packets, i
     hipLaunchKernelGGL(aedat4_count_kernel, dim3(blocks_of(n)), dim3(kThreads), 0, stream, src, packets, pl.off,
                        staged ? pl.size : (const int32_t*)nullptr, n, pl.count, pl.data, pl.first_t, pl.last_t, pl.status, !staged);
   hipLaunchKernelGGL(aedat4_counts_kernel, dim3(1), dim3(kThreads), 0, stream, pl.count, pl.status, pl.first_t, n, pl.ev_off,
-                     pl.prev, pl.padded, count_status);
+                     pl.prev, pl.scratch, count_status);
   SCP_CHECK_HIP(hipGetLastError());
   return SCPOSE_OK;
 }

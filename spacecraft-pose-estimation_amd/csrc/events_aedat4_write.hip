@@ -104,17 +104,6 @@ Plan plan(int64_t src_bytes, int64_t np, int64_t staging_bytes, bool lz4, uint8_
   return p;
 }
 
-__device__ __forceinline__ int block_or(int v, int32_t* lds) {
-  __syncthreads();
-  if (threadIdx.x == 0) lds[0] = 0;
-  __syncthreads();
-  if (v) atomicOr(&lds[0], v);
-  __syncthreads();
-  const int r = lds[0];
-  __syncthreads();
-  return r;
-}
-
 // rows != 0: bounds are rows, a packet's source is its flatbuffer inside its record; else bounds are bytes of the caller's string.
 // direct != 0 (NONE): the records are the output, their total is checked against the capacity here.
 __global__ __launch_bounds__(kThreads) void aedat4w_plan_kernel(const int64_t* __restrict__ bounds, int64_t np, int64_t n, int rows,

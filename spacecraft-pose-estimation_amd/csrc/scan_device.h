@@ -1,4 +1,5 @@
-// Parallel-prefix primitives of the event kernels (events_exposure / events_csv / events_write / dvs_emulator): device
+// Parallel-prefix primitives and workgroup reductions of the event kernels (events_exposure / events_csv / events_write /
+// dvs_emulator / the AEDAT readers and writers; events_packets.h builds the packet readers' shared steps on them): device
 // functions only, the __global__ wrappers and their launches stay in the client files.
 //
 // Contract: every body below is called by ALL threads of a workgroup of exactly kScanThreads threads (it contains barriers),
@@ -36,6 +37,18 @@ __device__ int32_t block_inclusive_scan(int32_t v, int32_t* lds) {
     __syncthreads();
   }
   const int32_t r = lds[tid];
+  __syncthreads();
+  return r;
+}
+
+// ---- block OR: every thread gets the OR of the workgroup's v; lds[0] alone is used
+__device__ __forceinline__ int block_or(int v, int32_t* lds) {
+  __syncthreads();
+  if (threadIdx.x == 0) lds[0] = 0;
+  __syncthreads();
+  if (v) atomicOr(&lds[0], v);
+  __syncthreads();
+  const int r = lds[0];
   __syncthreads();
   return r;
 }

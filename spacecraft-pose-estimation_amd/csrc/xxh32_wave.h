@@ -4,19 +4,13 @@
 // Contract: xxh32_wave is called by ALL threads of a workgroup of exactly 64 threads (it contains barriers), with `sw` pointing
 // at 256 words of LDS that the caller does not use across the call.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "common.h"   // ld32
 
 namespace scpose {
 
 constexpr uint32_t kXxhP1 = 2654435761u, kXxhP2 = 2246822519u, kXxhP3 = 3266489917u, kXxhP4 = 668265263u, kXxhP5 = 374761393u;
 
 __device__ __forceinline__ uint32_t rotl(uint32_t v, int r) { return (v << r) | (v >> (32 - r)); }
-__device__ __forceinline__ uint32_t ld32(const uint8_t* p) {
-  uint32_t v;
-  __builtin_memcpy(&v, p, 4);
-  return v;
-}
 
 // xxh32 (seed 0) of n bytes at p, by one wavefront: lane l carries accumulator l & 3 over the 16-byte stripes, 64 stripes at a time
 // through `sw` (256 words of LDS); every lane returns the digest.

@@ -27,6 +27,8 @@ import struct
 import numpy as np
 
 AEDAT2_MAGIC = b"#!AER-DAT"
+AEDAT3_MAGIC = b"#!AER-DAT3."
+AEDAT4_MAGIC = b"#!AER-DAT4.0\r\n"
 MAX_HEADER_BYTES = 1 << 20
 
 
@@ -62,16 +64,68 @@ def split_aedat2_header(prefix):
     return off
 
 
-def is_aedat_path(path):
-    """True for a path that ends in .aedat / .aedat2 or a file whose first bytes are '#!AER-DAT'."""
-    name = str(path).lower()
-    if name.endswith(".aedat") or name.endswith(".aedat2"):
+# (key, name suffixes, first bytes), in the order they are tested: a suffix or the magic decides.  An AEDAT-3.1 recording usually
+# carries the .aedat name of a 2.0 one, so its magic is looked at before that suffix.
+EVENT_FORMATS = (("aedat4", (".aedat4",), AEDAT4_MAGIC),
+                 ("aedat3", (".aedat3",), AEDAT3_MAGIC),
+                 ("aedat2", (".aedat", ".aedat2"), AEDAT2_MAGIC))
+
+
+def _sniff(path, suffixes, magic):
+    if str(path).lower().endswith(suffixes):
         return True
     try:
         with open(path, "rb") as f:
-            return f.read(len(AEDAT2_MAGIC)) == AEDAT2_MAGIC
+            return f.read(len(magic)) == magic
     except OSError:
         return False
+
+
+def events_format(path):
+    """'aedat4', 'aedat3' or 'aedat2' for an event file of that format, by its name or its first bytes (EVENT_FORMATS, tested in
+    that order); None for anything else: text, or a path that cannot be read."""
+    return next((key for key, suffixes, magic in EVENT_FORMATS if _sniff(path, suffixes, magic)), None)
+
+
+def is_aedat_path(path):
+    """True for a path that ends in .aedat / .aedat2 or a file whose first bytes are '#!AER-DAT'."""
+    return _sniff(path, *EVENT_FORMATS[2][1:])
+
+
+def is_aedat4_path(path):
+    """True for a path that ends in .aedat4 or a file whose first 14 bytes are the AEDAT-4.0 version line."""
+    return _sniff(path, *EVENT_FORMATS[0][1:])
+
+
+def is_aedat3_path(path):
+    """True for a path that ends in .aedat3 or a file whose first bytes are '#!AER-DAT3.' (a 3.1 recording usually carries the
+    .aedat name of a 2.0 one: look here first)."""
+    return _sniff(path, *EVENT_FORMATS[1][1:])
+
+
+def _load(path_or_bytes):
+    """A path, or a file's bytes -> the file as a uint8 NumPy array (read-only when it views the caller's bytes)."""
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        return np.frombuffer(path_or_bytes, dtype=np.uint8)
+    return np.fromfile(path_or_bytes, dtype=np.uint8)
+
+
+def _device(device):
+    import torch
+    return torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def _upload(host, dev):
+    """The whole file to the device in one piece; only a read-only buffer is copied first."""
+    import torch
+    return torch.from_numpy(host.copy() if not host.flags.writeable else host).to(dev)
+
+
+def read_events_file(path, hw=None, device=None, **kw):
+    """An event file of any EVENT_FORMATS format -> the (t, x, y, p, info) of its reader (read_events_aedat4 / _aedat3 / _aedat2,
+    which takes kw); None for a path events_format does not know: text."""
+    fmt = events_format(path)
+    return READERS[fmt](path, hw=hw, device=device, **kw) if fmt else None
 
 
 def read_events_aedat2(path_or_bytes, hw, device=None, **unpack_kwargs):
@@ -79,24 +133,18 @@ def read_events_aedat2(path_or_bytes, hw, device=None, **unpack_kwargs):
     one), the kept events in file order.  hw = (height, width) of the sensor; unpack_kwargs are ops.unpack_events_aedat2's
     (layout, flip_x, flip_y, unwrap, t_divisor).  The body is uploaded in one piece, as ops.parse_events_csv uploads its text.
     A trailing partial record is ignored and reported as info['trailing_bytes']; info holds the decoder's counters as well."""
-    import torch
     from . import ops
-    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
-        host = np.frombuffer(path_or_bytes, dtype=np.uint8)
-    else:
-        host = np.fromfile(path_or_bytes, dtype=np.uint8)
+    host = _load(path_or_bytes)
     off = split_aedat2_header(host[:MAX_HEADER_BYTES + 1].tobytes())
     n = (len(host) - off) // 8
     body = host[off:off + 8 * n]
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    buf = torch.from_numpy(body.copy()).to(dev)                      # the copy starts the records on an aligned address
+    buf = _upload(body.copy(), _device(device))                      # the copy starts the records on an aligned address
     t, x, y, p, info = ops.unpack_events_aedat2(buf, hw, **unpack_kwargs)
     info["trailing_bytes"] = int(len(host) - off - 8 * n)
     return t, x, y, p, info
 
 
 # ------------------------------------------------------------------ AEDAT-4.0
-AEDAT4_MAGIC = b"#!AER-DAT4.0\r\n"
 AEDAT4_COMPRESSION = {0: "NONE", 1: "LZ4", 2: "LZ4_HIGH", 3: "ZSTD", 4: "ZSTD_HIGH"}
 
 
@@ -120,17 +168,6 @@ class Aedat4Header:
     def event_streams(self):
         """The ids of the EVTS streams, in the header's order."""
         return [sid for sid, s in self.streams.items() if s[0] == "EVTS"]
-
-
-def is_aedat4_path(path):
-    """True for a path that ends in .aedat4 or a file whose first 14 bytes are the AEDAT-4.0 version line."""
-    if str(path).lower().endswith(".aedat4"):
-        return True
-    try:
-        with open(path, "rb") as f:
-            return f.read(len(AEDAT4_MAGIC)) == AEDAT4_MAGIC
-    except OSError:
-        return False
 
 
 def _fb_field(buf, table, index):
@@ -239,12 +276,8 @@ def read_events_aedat4(path_or_bytes, hw=None, stream=None, rebase=True, verify=
     stamp, as the reference does; verify: check the LZ4 block and content checksums the file carries.  The file is uploaded
     once, as ops.parse_events_csv uploads its text.  info: n_events, n_packets, t0, n_backward, n_out_of_range, compression, hw,
     streams, trailing_bytes.  Raises UnsupportedAedat4 (parse_aedat4) and ValueError (ops.unpack_events_aedat4)."""
-    import torch
     from . import ops
-    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
-        host = np.frombuffer(path_or_bytes, dtype=np.uint8)
-    else:
-        host = np.fromfile(path_or_bytes, dtype=np.uint8)
+    host = _load(path_or_bytes)
     head = parse_aedat4(memoryview(host))
     if stream is None:
         ids = head.event_streams()
@@ -259,16 +292,13 @@ def read_events_aedat4(path_or_bytes, hw=None, stream=None, rebase=True, verify=
         hw = (sy, sx)
     keep = np.isin(head.packet_stream, ids)
     packets = np.stack([head.packet_offset[keep], head.packet_size[keep]], axis=1)
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    buf = torch.from_numpy(host.copy() if not host.flags.writeable else host).to(dev)
-    t, x, y, p, info = ops.unpack_events_aedat4(buf, packets, head.compression, hw, rebase=rebase, verify=verify)
+    t, x, y, p, info = ops.unpack_events_aedat4(_upload(host, _device(device)), packets, head.compression, hw, rebase=rebase, verify=verify)
     info.update(compression=int(head.compression), hw=(int(hw[0]), int(hw[1])), streams=tuple(ids),
                 trailing_bytes=int(head.trailing_bytes))
     return t, x, y, p, info
 
 
 # ------------------------------------------------------------------ AEDAT-3.1
-AEDAT3_MAGIC = b"#!AER-DAT3."
 AEDAT3_PACKET_HEADER = 28
 AEDAT3_TYPES = {0: "special", 1: "polarity", 2: "frame", 3: "IMU6", 4: "IMU9"}
 AEDAT3_POLARITY = 1
@@ -301,18 +331,6 @@ class Aedat3Header:
     def polarity_sources(self):
         """The ids of the sources that carry polarity packets, ascending."""
         return sorted(set(int(s) for s in self.packet_source[self.packet_type == AEDAT3_POLARITY]))
-
-
-def is_aedat3_path(path):
-    """True for a path that ends in .aedat3 or a file whose first bytes are '#!AER-DAT3.' (a 3.1 recording usually carries the
-    .aedat name of a 2.0 one: look here first)."""
-    if str(path).lower().endswith(".aedat3"):
-        return True
-    try:
-        with open(path, "rb") as f:
-            return f.read(len(AEDAT3_MAGIC)) == AEDAT3_MAGIC
-    except OSError:
-        return False
 
 
 def aedat3_sensor_hw(name):
@@ -415,12 +433,8 @@ def read_events_aedat3(path_or_bytes, hw=None, source=None, rebase=True, device=
     n_packets, n_invalid (events dropped because their valid bit is clear), t0, n_backward, n_out_of_range, sources (the ids
     read), other_packets {type: count}, trailing_bytes, hw.  Raises UnsupportedAedat3 (parse_aedat3, the source, the size) and
     ValueError (ops.unpack_events_aedat3).  Frame, IMU and special events are counted and not decoded."""
-    import torch
     from . import ops
-    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
-        host = np.frombuffer(path_or_bytes, dtype=np.uint8)
-    else:
-        host = np.fromfile(path_or_bytes, dtype=np.uint8)
+    host = _load(path_or_bytes)
     head = parse_aedat3(memoryview(host))
     carrying = head.polarity_sources()
     if source is None:
@@ -439,9 +453,10 @@ def read_events_aedat3(path_or_bytes, hw=None, source=None, rebase=True, device=
                                     "DAVIS640 are): give the size, hw = (height, width)" % (sid, head.sources.get(sid)))
     keep = (head.packet_type == AEDAT3_POLARITY) & (head.packet_source == sid)
     packets = np.stack([head.packet_offset[keep], head.packet_events[keep], head.packet_overflow[keep]], axis=1)
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    buf = torch.from_numpy(host.copy() if not host.flags.writeable else host).to(dev)
-    t, x, y, p, info = ops.unpack_events_aedat3(buf, packets, hw, rebase=rebase)
+    t, x, y, p, info = ops.unpack_events_aedat3(_upload(host, _device(device)), packets, hw, rebase=rebase)
     info.update(n_invalid=int(packets[:, 1].sum()) - info["n_events"], sources=(sid,), other_packets=dict(head.other_packets),
                 trailing_bytes=int(head.trailing_bytes), hw=(int(hw[0]), int(hw[1])))
     return t, x, y, p, info
+
+
+READERS = {"aedat4": read_events_aedat4, "aedat3": read_events_aedat3, "aedat2": read_events_aedat2}

@@ -95,23 +95,14 @@ def read_events_device(path, device=None, host_csv=False, hw=None, aedat_layout=
     import torch
     from . import event_read, ops
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    if event_read.is_aedat4_path(path):
+    fmt = event_read.events_format(path)
+    kw = {}
+    if fmt in ("aedat4", "aedat3"):
         for name, on in [("host_csv", host_csv)] + sorted(csv_flags.items()):
             if on:
-                raise ValueError("%s describes a text file and cannot be used with the AEDAT-4.0 input %s" % (name, path))
-        t, x, y, _, info = event_read.read_events_aedat4(path, hw=hw, device=dev)
-        if info["n_backward"] > 0:
-            raise ValueError("the event stream must be sorted by time")
-        return t, x, y
-    if event_read.is_aedat3_path(path):
-        for name, on in [("host_csv", host_csv)] + sorted(csv_flags.items()):
-            if on:
-                raise ValueError("%s describes a text file and cannot be used with the AEDAT-3.1 input %s" % (name, path))
-        t, x, y, _, info = event_read.read_events_aedat3(path, hw=hw, device=dev)
-        if info["n_backward"] > 0:
-            raise ValueError("the event stream must be sorted by time")
-        return t, x, y
-    if event_read.is_aedat_path(path):
+                raise ValueError("%s describes a text file and cannot be used with the %s input %s"
+                                 % (name, {"aedat4": "AEDAT-4.0", "aedat3": "AEDAT-3.1"}[fmt], path))
+    elif fmt == "aedat2":
         for name, on in (("host_csv", host_csv), ("delim_whitespace", csv_flags.get("delim_whitespace")),
                          ("swap_xy", csv_flags.get("swap_xy"))):
             if on:
@@ -119,8 +110,9 @@ def read_events_device(path, device=None, host_csv=False, hw=None, aedat_layout=
         if hw is None:
             raise ValueError("an AEDAT-2.0 input needs the sensor size hw = (height, width)")
         div = 1000000.0 if csv_flags.get("microseconds_timestamp") else (1000.0 if csv_flags.get("milliseconds_timestamp") else 0.0)
-        t, x, y, _, info = event_read.read_events_aedat2(path, hw, device=dev, layout=aedat_layout, flip_x=aedat_flip_x,
-                                                         flip_y=aedat_flip_y, t_divisor=div)
+        kw = dict(layout=aedat_layout, flip_x=aedat_flip_x, flip_y=aedat_flip_y, t_divisor=div)
+    if fmt is not None:
+        t, x, y, _, info = event_read.read_events_file(path, hw, dev, **kw)
         if info["n_backward"] > 0:
             raise ValueError("the event stream must be sorted by time")
         return t, x, y

@@ -575,53 +575,88 @@ def unpack_events_aedat3(buf, packets, hw, rebase=True):
     (event_read.parse_aedat3 finds them).  hw = (height, width) of the sensor.  rebase: t minus the first event's t.  One small
     read-back sizes the columns, a second brings the counters.  info: n_events, n_packets, t0, n_backward, n_out_of_range.  Raises
     ValueError for a negative time stamp, valid bits that contradict the packet's header and an event outside the sensor."""
-    if not torch.is_tensor(buf) or buf.dtype != torch.uint8:
-        raise ValueError("unpack_events_aedat3: the file must be a uint8 device tensor")
-    _need_cuda(buf)
-    buf = buf.contiguous().view(-1)
-    pk = np.ascontiguousarray(packets, dtype=np.int64).reshape(-1, 3)
-    n = int(pk.shape[0])
+    who = "unpack_events_aedat3"
+    buf, pk, n = _packet_descriptors(who, buf, packets, 3)
     if n and (pk.min() < 0 or int(pk[:, 0].min()) < 28 or int(pk[:, 1].max()) > AEDAT3_MAX_PACKET_EVENTS or
               int((pk[:, 0] + 8 * pk[:, 1]).max()) > buf.numel()):
         if pk.min() >= 0 and int(pk[:, 1].max()) > AEDAT3_MAX_PACKET_EVENTS:
             raise ValueError("unpack_events_aedat3: a packet holds %d events: 2^23 or more in one packet are not read" % int(pk[:, 1].max()))
-        raise ValueError("unpack_events_aedat3: a packet does not lie inside the %d bytes of the file" % buf.numel())
+        raise ValueError(_NOT_INSIDE % (who, buf.numel()))
     if n and int(pk[:, 2].max()) > 0x7FFFFFFF:
         raise ValueError("unpack_events_aedat3: eventTSOverflow %d is not an int32" % int(pk[:, 2].max()))
     h, w = int(hw[0]), int(hw[1])
-    dev = buf.device
     lib = nat.lib()
     ws = _query_bytes("events_aedat3_workspace_bytes", n)
-    with torch.cuda.device(dev):
-        work = torch.empty(ws, dtype=torch.uint8, device=dev)
-        cs = torch.empty(6, dtype=torch.int64, device=dev)
-        pkd = torch.from_numpy(pk).to(dev)
-        nat.check(lib.scpose_events_aedat3_count(_ptr(buf), _ptr(pkd), n, _ptr(cs), _ptr(work), ws, _stream()), "events_aedat3_count")
-        rows, status, t0 = cs.tolist()[:3]                          # small read-back: the columns' size
-        _aedat3_raise(status, hw)
-        t, x, y, p = _empty_event_columns(int(rows), dev)
-        nat.check(lib.scpose_events_aedat3_unpack(_ptr(buf), _ptr(pkd), n, h, w, int(bool(rebase)), _ptr(t), _ptr(x), _ptr(y), _ptr(p),
-                                                  int(rows), _ptr(cs), _ptr(work), ws, _stream()), "events_aedat3_unpack")
-        got = cs.tolist()                                           # the counters
-    _aedat3_raise(got[1], hw)
+    with torch.cuda.device(buf.device):
+        work = torch.empty(ws, dtype=torch.uint8, device=buf.device)
+        cs = torch.empty(6, dtype=torch.int64, device=buf.device)
+        pkd = torch.from_numpy(pk).to(buf.device)
+        return _count_then_unpack(
+            who, hw, _AEDAT3_STATUS, n, cs,
+            lambda: nat.check(lib.scpose_events_aedat3_count(_ptr(buf), _ptr(pkd), n, _ptr(cs), _ptr(work), ws, _stream()),
+                              "events_aedat3_count"),
+            lambda t, x, y, p, rows: nat.check(
+                lib.scpose_events_aedat3_unpack(_ptr(buf), _ptr(pkd), n, h, w, int(bool(rebase)), _ptr(t), _ptr(x), _ptr(y), _ptr(p),
+                                                rows, _ptr(cs), _ptr(work), ws, _stream()), "events_aedat3_unpack"))
+
+
+# ---- what the two packet readers (AEDAT-3.1, AEDAT-4.0) share on the host
+_NOT_INSIDE = "%s: a packet does not lie inside the %d bytes of the file"
+
+
+def _packet_descriptors(who, buf, packets, k):
+    """The whole file and its packet descriptors, checked -> (the file as a flat uint8 device tensor, the descriptors as an
+    (n, k) int64 NumPy array, n).  Whether each packet lies inside the file is the format's own expression, at the call site."""
+    if not torch.is_tensor(buf) or buf.dtype != torch.uint8:
+        raise ValueError("%s: the file must be a uint8 device tensor" % who)
+    _need_cuda(buf)
+    buf = buf.contiguous().view(-1)
+    pk = np.ascontiguousarray(packets, dtype=np.int64).reshape(-1, k)
+    return buf, pk, int(pk.shape[0])
+
+
+def _count_then_unpack(who, hw, table, n, cs, count, unpack):
+    """The tail of both readers, on the device of cs: count() leaves [n_events, status, t0, 0, 0, 0] in cs, a small read-back sizes
+    the columns, unpack(t, x, y, p, rows) fills them and adds its counters to cs, a second read-back brings those.
+    -> (t, x, y, p, info); a status bit raises what `table` says (_raise_status)."""
+    count()
+    rows, status, t0 = cs.tolist()[:3]                              # small read-back: the columns' size
+    _raise_status(who, status, hw, table)
+    t, x, y, p = _empty_event_columns(int(rows), cs.device)
+    unpack(t, x, y, p, int(rows))
+    got = cs.tolist()                                               # the counters
+    _raise_status(who, got[1], hw, table)
     return t, x, y, p, {"n_events": int(rows), "n_packets": n, "t0": int(t0) if rows else 0, "n_backward": int(got[3]),
                         "n_out_of_range": int(got[4])}
 
 
-def _aedat3_raise(status, hw):
-    """ValueError for the status bits of the AEDAT-3.1 kernels."""
-    if status & nat.AEDAT3_CORRUPT:
-        raise ValueError("unpack_events_aedat3: a polarity event has a negative time stamp, or a packet descriptor is out of range "
-                         "(status CORRUPT)")
-    if status & nat.AEDAT3_VALID_MISMATCH:
-        raise ValueError("unpack_events_aedat3: the valid bits of a packet's events do not add up to the eventValid its header "
-                         "states (status VALID_MISMATCH)")
-    if status & nat.AEDAT3_RANGE:
-        raise ValueError("unpack_events_aedat3: an event lies outside the %d x %d sensor (status RANGE)" % (int(hw[1]), int(hw[0])))
-    if status & nat.AEDAT3_CAPACITY:
-        raise nat.NativeError("unpack_events_aedat3: the columns are shorter than the events counted (status CAPACITY)")
+def _raise_status(who, status, hw, table):
+    """Raises for a status word of the event-file kernels: `table` is an ordered list of (bit, exception type, message); the first
+    bit that is set decides, any other non-zero status is a NativeError.  A message may name %(who)s and the sensor's %(w)d, %(h)d."""
+    for bit, exc, message in table:
+        if status & bit:
+            h, w = (None, None) if hw is None else (int(hw[0]), int(hw[1]))
+            raise exc(message % {"who": who, "w": w, "h": h})
     if status != 0:
-        raise nat.NativeError("unpack_events_aedat3: status %d" % status)
+        raise nat.NativeError("%s: status %d" % (who, status))
+
+
+_AEDAT3_STATUS = (
+    (nat.AEDAT3_CORRUPT, ValueError, "%(who)s: a polarity event has a negative time stamp, or a packet descriptor is out of range "
+                                     "(status CORRUPT)"),
+    (nat.AEDAT3_VALID_MISMATCH, ValueError, "%(who)s: the valid bits of a packet's events do not add up to the eventValid its header "
+                                            "states (status VALID_MISMATCH)"),
+    (nat.AEDAT3_RANGE, ValueError, "%(who)s: an event lies outside the %(w)d x %(h)d sensor (status RANGE)"),
+    (nat.AEDAT3_CAPACITY, nat.NativeError, "%(who)s: the columns are shorter than the events counted (status CAPACITY)"))
+_AEDAT4_STATUS = (
+    (nat.AEDAT4_CORRUPT, ValueError, "%(who)s: a packet is not a valid LZ4 frame (status CORRUPT: a bad magic, version or header "
+                                     "checksum, an offset of 0 or before the output's start, an input overrun, a size that differs)"),
+    (nat.AEDAT4_CHECKSUM, ValueError, "%(who)s: an LZ4 block or content checksum differs (status CHECKSUM)"),
+    (nat.AEDAT4_FLATBUFFER, ValueError, "%(who)s: an event packet's flatbuffer is damaged (status FLATBUFFER)"),
+    (nat.AEDAT4_RANGE, ValueError, "%(who)s: an event lies outside the %(w)d x %(h)d sensor (status RANGE)"))
+_AEDAT4_WRITE_STATUS = (
+    (nat.AEDAT4_WRITE_RANGE, ValueError, "%(who)s: an event lies outside the %(w)d x %(h)d sensor, or a polarity is neither 0 nor 1"),
+    (nat.AEDAT4_WRITE_SIZE, ValueError, "%(who)s: a packet is larger than the reader takes (2^23 - 16 bytes: 524284 events)"))
 
 
 def unpack_events_aedat4(buf, packets, compression, hw, rebase=True, verify=True):
@@ -632,62 +667,38 @@ def unpack_events_aedat4(buf, packets, compression, hw, rebase=True, verify=True
     event's t.  verify: check the checksums the LZ4 frames carry.  Two small read-backs size the staging buffer and the columns,
     a third brings the counters.  info: n_events, n_packets, t0, n_backward, n_out_of_range.  Raises ValueError for a damaged
     frame, a checksum that differs, a damaged flatbuffer and an event outside the sensor."""
-    if not torch.is_tensor(buf) or buf.dtype != torch.uint8:
-        raise ValueError("unpack_events_aedat4: the file must be a uint8 device tensor")
-    _need_cuda(buf)
+    who = "unpack_events_aedat4"
+    buf, pk, n = _packet_descriptors(who, buf, packets, 2)
     if compression not in (0, 1, 2):
         raise ValueError("unpack_events_aedat4: compression %r (0 NONE, 1 LZ4, 2 LZ4_HIGH)" % (compression,))
-    buf = buf.contiguous().view(-1)
-    pk = np.ascontiguousarray(packets, dtype=np.int64).reshape(-1, 2)
-    n = int(pk.shape[0])
     if n and (pk.min() < 0 or int((pk[:, 0] + pk[:, 1]).max()) > buf.numel()):
-        raise ValueError("unpack_events_aedat4: a packet does not lie inside the %d bytes of the file" % buf.numel())
+        raise ValueError(_NOT_INSIDE % (who, buf.numel()))
     h, w = int(hw[0]), int(hw[1])
-    dev = buf.device
     lib = nat.lib()
     ws = _query_bytes("events_aedat4_workspace_bytes", n)
-    with torch.cuda.device(dev):
-        work = torch.empty(ws, dtype=torch.uint8, device=dev)
-        cs = torch.empty(6, dtype=torch.int64, device=dev)
-        pkd = torch.from_numpy(pk).to(dev)
+    with torch.cuda.device(buf.device):
+        work = torch.empty(ws, dtype=torch.uint8, device=buf.device)
+        cs = torch.empty(6, dtype=torch.int64, device=buf.device)
+        pkd = torch.from_numpy(pk).to(buf.device)
         src = buf
         if compression:
             nat.check(lib.scpose_events_aedat4_measure(_ptr(buf), _ptr(pkd), n, _ptr(cs), _ptr(work), ws, _stream()),
                       "events_aedat4_measure")
             total, status = cs.tolist()[:2]                         # small read-back: the staging buffer's size
-            _aedat4_raise(status, hw)
+            _raise_status(who, status, hw, _AEDAT4_STATUS)
             if total < 0 or total % 16 or total > n * (1 << 23):
                 raise nat.NativeError("unpack_events_aedat4: events_aedat4_measure reports %d staging bytes for %d packets" % (total, n))
-            src = torch.empty(max(int(total), 16), dtype=torch.uint8, device=dev)
+            src = torch.empty(max(int(total), 16), dtype=torch.uint8, device=buf.device)
             nat.check(lib.scpose_events_aedat4_decode(_ptr(buf), _ptr(pkd), n, _ptr(src), int(total), int(bool(verify)), _ptr(work), ws,
                                                       _stream()),
                       "events_aedat4_decode")
-        nat.check(lib.scpose_events_aedat4_count(_ptr(src), _ptr(pkd), n, int(bool(compression)), _ptr(cs), _ptr(work), ws, _stream()),
-                  "events_aedat4_count")
-        rows, status, t0 = cs.tolist()[:3]                          # small read-back: the columns' size
-        _aedat4_raise(status, hw)
-        t, x, y, p = _empty_event_columns(int(rows), dev)
-        nat.check(lib.scpose_events_aedat4_unpack(_ptr(src), n, h, w, int(bool(rebase)), _ptr(t), _ptr(x), _ptr(y), _ptr(p), int(rows),
-                                                  _ptr(cs), _ptr(work), ws, _stream()), "events_aedat4_unpack")
-        got = cs.tolist()                                           # the counters
-    _aedat4_raise(got[1], hw)
-    return t, x, y, p, {"n_events": int(rows), "n_packets": n, "t0": int(t0) if rows else 0, "n_backward": int(got[3]),
-                        "n_out_of_range": int(got[4])}
-
-
-def _aedat4_raise(status, hw):
-    """ValueError for the status bits of the AEDAT-4.0 kernels."""
-    if status & nat.AEDAT4_CORRUPT:
-        raise ValueError("unpack_events_aedat4: a packet is not a valid LZ4 frame (status CORRUPT: a bad magic, version or header "
-                         "checksum, an offset of 0 or before the output's start, an input overrun, a size that differs)")
-    if status & nat.AEDAT4_CHECKSUM:
-        raise ValueError("unpack_events_aedat4: an LZ4 block or content checksum differs (status CHECKSUM)")
-    if status & nat.AEDAT4_FLATBUFFER:
-        raise ValueError("unpack_events_aedat4: an event packet's flatbuffer is damaged (status FLATBUFFER)")
-    if status & nat.AEDAT4_RANGE:
-        raise ValueError("unpack_events_aedat4: an event lies outside the %d x %d sensor (status RANGE)" % (int(hw[1]), int(hw[0])))
-    if status != 0:
-        raise nat.NativeError("unpack_events_aedat4: status %d" % status)
+        return _count_then_unpack(
+            who, hw, _AEDAT4_STATUS, n, cs,
+            lambda: nat.check(lib.scpose_events_aedat4_count(_ptr(src), _ptr(pkd), n, int(bool(compression)), _ptr(cs), _ptr(work), ws,
+                                                             _stream()), "events_aedat4_count"),
+            lambda t, x, y, p, rows: nat.check(
+                lib.scpose_events_aedat4_unpack(_ptr(src), n, h, w, int(bool(rebase)), _ptr(t), _ptr(x), _ptr(y), _ptr(p), rows,
+                                                _ptr(cs), _ptr(work), ws, _stream()), "events_aedat4_unpack"))
 
 
 AEDAT4_COMPRESSIONS = {"none": nat.AEDAT4_NONE, "lz4": nat.AEDAT4_LZ4}
@@ -708,15 +719,6 @@ def _packet_bounds(who, bounds, n, what):
         raise ValueError("%s: the packet boundaries must rise from 0 to the %d %s (got %d values, %s .. %s)"
                          % (who, n, what, b.size, b[0] if b.size else None, b[-1] if b.size else None))
     return b
-
-
-def _aedat4_write_raise(who, status, hw=None):
-    if status & nat.AEDAT4_WRITE_RANGE:
-        raise ValueError("%s: an event lies outside the %d x %d sensor, or a polarity is neither 0 nor 1" % (who, hw[1], hw[0]))
-    if status & nat.AEDAT4_WRITE_SIZE:
-        raise ValueError("%s: a packet is larger than the reader takes (2^23 - 16 bytes: 524284 events)" % who)
-    if status != 0:
-        raise nat.NativeError("%s: status %d" % (who, status))
 
 
 def pack_events_aedat4(t, x, y, p, hw, packet_rows, compression="lz4", stream_id=0):
@@ -746,7 +748,7 @@ def pack_events_aedat4(t, x, y, p, hw, packet_rows, compression="lz4", stream_id
                                                 _ptr(out), cap.value, _ptr(res[2:]), _ptr(res), _ptr(work), ws.value, _stream()),
                   "events_aedat4_pack")
         got = res.cpu().numpy()                                     # the one read-back
-    _aedat4_write_raise(who, int(got[1]), (h, w))
+    _raise_status(who, int(got[1]), (h, w), _AEDAT4_WRITE_STATUS)
     return out[:int(got[0])], got[2:2 + 5 * npk].reshape(npk, 5).copy()
 
 
@@ -774,7 +776,7 @@ def lz4_frame_bytes(data, bounds=None):
         nat.check(lib.scpose_events_aedat4_frame(_ptr(data), n, _ptr(bd), npk, _ptr(out), cap.value, _ptr(res[2:]), _ptr(res),
                                                  _ptr(work), ws.value, _stream()), "events_aedat4_frame")
         got = res.cpu().numpy()
-    _aedat4_write_raise(who, int(got[1]))
+    _raise_status(who, int(got[1]), None, _AEDAT4_WRITE_STATUS)
     return out[:int(got[0])], got[2:2 + 5 * npk].reshape(npk, 5).copy()
 
 

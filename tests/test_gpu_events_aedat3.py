@@ -156,6 +156,32 @@ def test_sensor_edges(er):
     assert info["n_events"] == 5 and info["n_invalid"] == 1
 
 
+def test_one_event_outside_the_sensor_is_tallied(er, gpu_ops):
+    """A recording whose only polarity packet holds exactly one valid event, outside the sensor: one chunk, one lane with anything
+    to add, so the tally's own barrier is all that orders the zeroing of its LDS pair before the one atomic."""
+    import torch
+    cols = (np.array([9], dtype=np.int64), np.array([64], dtype=np.int32), np.array([3], dtype=np.int32), np.array([1], dtype=np.int8))
+    data = W.write_aedat3(W.split(cols, (1,)), SOURCES)
+    with pytest.raises(ValueError, match=r"outside the 64 x 48 sensor \(status RANGE\)"):
+        er.read_events_aedat3(data, hw=HW)
+    ops, nat = gpu_ops, gpu_ops.nat
+    head = er.parse_aedat3(data)
+    pk = torch.from_numpy(np.stack([head.packet_offset, head.packet_events, head.packet_overflow], axis=1)).cuda()
+    buf = torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy()).cuda()
+    ws = ops._query_bytes("events_aedat3_workspace_bytes", 1)
+    work = torch.empty(ws, dtype=torch.uint8, device="cuda")
+    cs = torch.empty(6, dtype=torch.int64, device="cuda")
+    lib, P, S = nat.lib(), ops._ptr, ops._stream
+    nat.check(lib.scpose_events_aedat3_count(P(buf), P(pk), 1, P(cs), P(work), ws, S()), "count")
+    assert cs.tolist() == [1, 0, 9, 0, 0, 0]
+    t = torch.empty(1, dtype=torch.int64, device="cuda")
+    x, y, p = (torch.empty(1, dtype=d, device="cuda") for d in (torch.int32, torch.int32, torch.int8))
+    nat.check(lib.scpose_events_aedat3_unpack(P(buf), P(pk), 1, HW[0], HW[1], 0, P(t), P(x), P(y), P(p), 1, P(cs), P(work), ws, S()),
+              "unpack")
+    assert cs.tolist() == [1, nat.AEDAT3_RANGE, 9, 0, 1, 0]              # n_backward 0, n_out_of_range 1
+    assert (t.item(), x.item(), y.item(), p.item()) == (9, 64, 3, 1)
+
+
 def test_backward_time_stamps_are_counted(er):
     cols = list(W.random_events(700, HW, 7))
     t = cols[0].copy()

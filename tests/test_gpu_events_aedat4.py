@@ -254,6 +254,31 @@ def test_damaged_files_raise(er):
     check(er, good, "still fine")                                          # the device is in order after all of that
 
 
+def test_one_event_outside_the_sensor_is_tallied(er, gpu_ops):
+    """A NONE recording whose only packet holds exactly one event, outside the sensor: one lane with anything to add, so the
+    tally's own barrier is all that orders the zeroing of its LDS pair before the one atomic."""
+    import torch
+    cols = (np.array([9], dtype=np.int64), np.array([64], dtype=np.int32), np.array([3], dtype=np.int32), np.array([1], dtype=np.int8))
+    data = W.write_aedat4([(0, W.evts_payload(*cols))], STREAMS, W.NONE)
+    with pytest.raises(ValueError, match=r"outside the 64 x 48 sensor \(status RANGE\)"):
+        er.read_events_aedat4(data)
+    ops, nat = gpu_ops, gpu_ops.nat
+    head = er.parse_aedat4(data)
+    pk = torch.from_numpy(np.stack([head.packet_offset, head.packet_size], axis=1)).cuda()
+    buf = torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy()).cuda()
+    ws = ops._query_bytes("events_aedat4_workspace_bytes", 1)
+    work = torch.empty(ws, dtype=torch.uint8, device="cuda")
+    cs = torch.empty(6, dtype=torch.int64, device="cuda")
+    lib, P, S = nat.lib(), ops._ptr, ops._stream
+    nat.check(lib.scpose_events_aedat4_count(P(buf), P(pk), 1, 0, P(cs), P(work), ws, S()), "count")
+    assert cs.tolist() == [1, 0, 9, 0, 0, 0]
+    t = torch.empty(1, dtype=torch.int64, device="cuda")
+    x, y, p = (torch.empty(1, dtype=d, device="cuda") for d in (torch.int32, torch.int32, torch.int8))
+    nat.check(lib.scpose_events_aedat4_unpack(P(buf), 1, HW[0], HW[1], 0, P(t), P(x), P(y), P(p), 1, P(cs), P(work), ws, S()), "unpack")
+    assert cs.tolist() == [1, nat.AEDAT4_RANGE, 9, 0, 1, 0]              # n_backward 0, n_out_of_range 1
+    assert (t.item(), x.item(), y.item(), p.item()) == (9, 64, 3, 1)
+
+
 # ------------------------------------------------------------------ command lines
 def run(script, *args):
     return subprocess.run([sys.executable, os.path.join(ROOT, "v2e", script), *args], capture_output=True, text=True, timeout=120)

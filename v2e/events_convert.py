@@ -63,14 +63,11 @@ def main(argv=None):
         sys.exit("events_convert: --output %s: the extension must be one of %s" % (args.output, ", ".join(FORMATS)))
     if ext == ".aedat" and (args.width is None or args.height is None):
         sys.exit("events_convert: an .aedat output needs --width and --height")
-    aedat4_in = args.events_file.lower().endswith(".aedat4")
-    if not aedat4_in and os.path.isfile(args.events_file):
-        with open(args.events_file, "rb") as f:
-            aedat4_in = f.read(14) == b"#!AER-DAT4.0\r\n"
-    aedat3_in = args.events_file.lower().endswith(".aedat3")
-    if not aedat4_in and not aedat3_in and os.path.isfile(args.events_file):
-        with open(args.events_file, "rb") as f:
-            aedat3_in = f.read(11) == b"#!AER-DAT3."
+    import scpose  # noqa: F401
+    from importlib import import_module
+    er = import_module("spacecraft-pose-estimation_amd.event_read")
+    fmt = er.events_format(args.events_file)
+    aedat4_in, aedat3_in = fmt == "aedat4", fmt == "aedat3"
     version = "AEDAT-4.0" if aedat4_in else "AEDAT-3.1"
     if (aedat4_in or aedat3_in) and (args.delim_whitespace or args.swap_xy or args.aedat_layout):
         sys.exit("events_convert: --delim_whitespace, --swap_xy and --aedat_layout cannot be used with the %s input %s"
@@ -79,7 +76,7 @@ def main(argv=None):
         sys.exit("events_convert: give --width and --height together, or neither (the %s file states its sensor%s)"
                  % (version, " size" if aedat4_in else ", and a known camera's size is taken from its name"))
     args.aedat_layout = args.aedat_layout or "davis"
-    aedat_in = args.events_file.lower().endswith((".aedat", ".aedat2")) and not aedat4_in and not aedat3_in
+    aedat_in = fmt == "aedat2" and args.events_file.lower().endswith((".aedat", ".aedat2"))     # by its name alone, as ever
     if aedat_in and (args.width is None or args.height is None):
         sys.exit("events_convert: an .aedat input needs --width and --height, the sensor size")
     if aedat_in and (args.delim_whitespace or args.swap_xy):
@@ -89,8 +86,6 @@ def main(argv=None):
         sys.exit("events_convert: an .aedat4 output needs --width and --height, the sensor size, unless the input states it")
     if not os.path.isfile(args.events_file):
         sys.exit("events_convert: --events_file %s is not a file" % args.events_file)
-    import scpose  # noqa: F401
-    from importlib import import_module
     ew = import_module("spacecraft-pose-estimation_amd.event_write")
     if ext == ".aedat":
         try:
@@ -98,21 +93,14 @@ def main(argv=None):
         except ValueError as e:
             sys.exit("events_convert: %s" % e)
     ops = import_module("spacecraft-pose-estimation_amd.ops")
-    if aedat4_in or aedat3_in:
-        er = import_module("spacecraft-pose-estimation_amd.event_read")
-        read = er.read_events_aedat4 if aedat4_in else er.read_events_aedat3
+    if aedat4_in or aedat3_in or aedat_in:
+        hw = None if args.width is None else (args.height, args.width)
         try:
-            t, x, y, p, info = read(args.events_file, hw=None if args.width is None else (args.height, args.width))
+            t, x, y, p, info = er.read_events_file(args.events_file, hw, **({"layout": args.aedat_layout} if aedat_in else {}))
         except ValueError as e:
             sys.exit("events_convert: %s" % e)
-        print("events_convert: %s: %s" % (args.events_file, ", ".join("%s=%s" % kv for kv in sorted(info.items()))))
-    elif aedat_in:
-        er = import_module("spacecraft-pose-estimation_amd.event_read")
-        try:
-            t, x, y, p, info = er.read_events_aedat2(args.events_file, (args.height, args.width), layout=args.aedat_layout)
-        except ValueError as e:
-            sys.exit("events_convert: %s" % e)
-        print("events_convert: %s: %s" % (args.events_file, ", ".join("%s=%d" % kv for kv in sorted(info.items()))))
+        item = "%s=%d" if aedat_in else "%s=%s"
+        print("events_convert: %s: %s" % (args.events_file, ", ".join(item % kv for kv in sorted(info.items()))))
     else:
         t, x, y, p = ops.parse_events_csv(args.events_file, delim_whitespace=args.delim_whitespace, swap_xy=args.swap_xy)
     if ext == ".aedat":
