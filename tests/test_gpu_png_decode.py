@@ -74,7 +74,8 @@ def test_one_call_mixes_every_channel_count(gpu_ops):
 def test_six_frame_sizes_in_one_call(gpu_ops):
     """frames of different sizes share a call only through decode_crop: the identity warp into a crop that holds the whole frame"""
     cases = W.accepted_cases()
-    names = ["shape_1x1_type0", "shape_1x9_type3", "shape_9x1_type6", "shape_3x5_type2", "shape_63x7_type4", "shape_65x7_type3", "hand_fixed"]
+    names = ["shape_1x1_type0", "shape_1x9_type3", "shape_9x1_type6", "shape_3x5_type2", "shape_63x7_type4", "shape_65x7_type3", "hand_fixed",
+             "dyn_long_codes", "dyn_single_distance", "dyn_lone_eob"]
     names = [k for k in names if k in cases]
     assert len({pr.parse_png(cases[k]).geometry for k in names}) >= 6
     trans = np.tile(np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0]]), (len(names), 1, 1))

@@ -32,6 +32,8 @@ def test_restatement_equals_pil_and_zlib(name):
     raw, produced, status = R.inflate(stream, need)
     assert status == 0 and produced == need
     assert raw == zlib.decompress(stream)
+    if name.startswith("dyn_"):
+        assert raw == W.case_raw(name)                                  # the bytes the hand-made ops stand for
     px, status, _ = R.decode(data)
     assert status == 0
     assert np.array_equal(px, pil_rgb(data))
@@ -48,6 +50,72 @@ def test_the_cases_hold_what_they_claim():
     assert streams["hand_far_matches"][-4 - 8:-4] == W.fixed_block([(258, 32768), (258, 32758)]).done()
     assert len(pr.parse_png(c["split_every_byte"]).idat) == len(streams["split_every_byte"])
     assert any(s == e for s, e in pr.parse_png(c["split_empty_chunks"]).idat)
+    for k in ("dyn_long_codes", "dyn_single_distance"):
+        assert len(pr.parse_png(c[k + "_split_every_byte"]).idat) == len(streams[k]) and streams[k + "_split_every_byte"] == streams[k]
+    dynamic_cases_hold_what_they_claim()
+
+
+def crossing(rec, symbol):
+    """the items of a block's length sequence that are repeats of `symbol` begun in the literal/length slots and ended in the distance slots"""
+    return [item for item, first, end in rec["seq"] if isinstance(item, tuple) and item[0] == symbol and first < rec["hlit"] < end]
+
+
+def dynamic_cases_hold_what_they_claim():
+    """from the record of what tests/png_stream_writer.dynamic_block wrote: the code lengths the ops USED, not the ones merely declared"""
+    rec = W.case_records
+    for name in ("dyn_long_codes", "dyn_long_codes_split_every_byte", "dyn_counts_extremes_286_30"):
+        r, = rec(name)
+        assert sorted(v for v in r["lit_lens"] if v) == W.LADDER and sorted(v for v in r["dist_lens"] if v) == W.LADDER
+        assert {8, 10, 11, 14, 15} <= r["lit_used"]                      # 10: the last the device's first-level table holds; beyond: the walk
+        assert {8, 9, 12, 15} <= r["dist_used"]                          # 8: the last of the distance table
+        assert {(14, 63), (15, 0), (15, 63)} <= {m[2:] for m in r["matches"]}     # both ends of a distance symbol's range
+    a, b = rec("dyn_single_distance")
+    for r, symbol in ((a, 0), (b, 6)):
+        assert [(s, v) for s, v in enumerate(r["dist_lens"]) if v] == [(symbol, 1)] and r["dist_used"] == {1}
+    assert (285, 0, 0, 0) in a["matches"] and {m[3] for m in b["matches"]} == {0, 1, 2, 3}
+    for name, length in (("dyn_no_distance", 0), ("dyn_counts_extremes_257_1", 1)):
+        r, = rec(name)
+        assert (r["hlit"], r["hdist"], r["dist_lens"]) == (257, 1, [length]) and not r["matches"] and r["lit_used"]
+    a, b = rec("dyn_lone_eob")
+    assert [(s, v) for s, v in enumerate(a["lit_lens"]) if v] == [(256, 1)] and not any(a["dist_lens"]) and not a["op_at"] and not a["final"]
+    assert a["end_at"] - a["eob_at"] == 1 and b["final"] and len(b["op_at"]) == 40
+    a, b = rec("dyn_repeats")
+    assert crossing(a, 16) == [(16, 5)] and crossing(b, 18) == [(18, 56)]
+    items = [item for item, _, _ in a["seq"]]
+    assert (18, 138) in items and any(x == (16, 6) and y == (16, 6) for x, y in zip(items, items[1:]))
+    assert any(isinstance(x, tuple) and x[0] == 18 and isinstance(y, tuple) and y[0] == 16 for x, y in zip(items, items[1:]))
+    assert any(isinstance(x, tuple) and x[0] == 17 and isinstance(y, tuple) and y[0] == 16 for x, y in zip(items, items[1:]))
+    for r in (a, b):                                                      # the last item is a repeat and ends exactly at HLIT + HDIST
+        assert isinstance(r["seq"][-1][0], tuple) and r["seq"][-1][2] == r["hlit"] + r["hdist"]
+        assert W.expand_seq(items if r is a else [i for i, _, _ in b["seq"]]) == r["lit_lens"] + r["dist_lens"]
+    r, = rec("dyn_counts_extremes_286_30")
+    assert (r["hlit"], r["hdist"], r["hclen"]) == (286, 30, 19) and all(r["cl_lens"]) and 7 in r["cl_used"]
+    assert {i if isinstance(i, int) else i[0] for i, _, _ in r["seq"]} == set(range(19))
+    r, = rec("dyn_len_284_31")
+    assert {(284, 31), (285, 0)} <= {m[:2] for m in r["matches"]}
+    r, = rec("dyn_dist_32768")
+    assert {(29, 8191), (29, 8181), (28, 8191)} == {m[2:] for m in r["matches"]} and len(W.case_raw("dyn_dist_32768")) == 131 * 256
+    a, b = rec("dyn_fixed_dyn_fixed")
+    assert b["stored_at"] % 8 not in (0, 5)                               # the stored block begins off a byte boundary and is padded to one
+    assert max(b["lit_used"]) == 11 and a["lit_lens"] != b["lit_lens"] and b["dist_used"] == {1, 2}
+    # the window edge: the refill comes where the device begins to read something more than WINDOW_BITS - 32 bits into the stream
+    for variant, (key, index, want) in W.WINDOW_EDGE_VARIANTS.items():
+        r, = rec("dyn_header_on_window_edge_" + variant)
+        points = [("block_at", 0, r["block_at"]), ("counts", 0, r["block_at"] + 3)]
+        points += [(k, i, at) for k in ("hclen_at", "item_at", "op_at") for i, at in enumerate(r[k])]
+        past = [(k, i) for k, i, at in points if at + 16 > W.WINDOW_BITS - 32]
+        print(variant, "refill at", past[0], "block begins at bit", r["block_at"] + 16)
+        assert r[key][index] + 16 == want and r["block_at"] + 16 < W.WINDOW_BITS - 32
+        if variant in ("hclen", "extra", "literal"):
+            assert past[0] == (key.replace("extra_at", "item_at"), index)
+        if variant == "hclen":
+            assert r["hclen_at"][14] + 16 < W.WINDOW_BITS < r["hclen_at"][15] + 16
+        if variant == "extra":
+            assert r["seq"][index][0][0] == 18
+        if variant == "extra_across":
+            assert r["seq"][index][0][0] == 18 and r["extra_at"][index] + 16 < W.WINDOW_BITS < r["item_at"][index + 1] + 16
+        if variant == "literal_across":
+            assert r["op_at"][0] + 16 < W.WINDOW_BITS < r["op_at"][1] + 16
 
 
 @pytest.mark.parametrize("name", sorted(W.damaged_cases()))
@@ -82,6 +150,29 @@ def test_which_damage_is_which():
             assert st["truncated_%s_%d" % (form, cut)] == 0
         for cut in range(5, 13):
             assert st["truncated_%s_%d" % (form, cut)] & R.CORRUPT
+    # the dynamic-block rules, one stream each: CORRUPT and nothing else, and zlib names the rule the stream was built for
+    said = {}
+    for k in W.DAMAGED_DYNAMIC:
+        assert st[k] == R.CORRUPT, k
+        with pytest.raises(zlib.error) as e:
+            zlib.decompress(joined_stream(c[k])[1])
+        said[k] = str(e.value)
+    rules = {"too many length or distance symbols": ["hlit_field_30", "hlit_field_31", "hdist_field_30", "hdist_field_31"],
+             "invalid code lengths set": ["cl_oversubscribed", "cl_incomplete", "cl_single"],
+             "invalid literal/lengths set": ["lit_oversubscribed", "lit_incomplete", "lit_single_length_2"],
+             "missing end-of-block": ["lit_no_eob"],
+             "invalid distances set": ["dist_oversubscribed", "dist_incomplete", "dist_single_length_2"],
+             "invalid bit length repeat": ["repeat_16_first", "repeat_16_past_total", "repeat_17_past_total", "repeat_18_past_total",
+                                           "repeat_18_from_literals"],
+             "invalid distance code": ["single_distance_unused_1", "length_without_distance", "fixed_distance_30", "fixed_distance_31"],
+             "invalid literal/length code": ["lone_eob_unused_1", "fixed_length_286", "fixed_length_287"],
+             "invalid distance too far back": ["dyn_distance_before_start"]}
+    for words, names in rules.items():
+        for k in names:
+            assert words in said[k], (k, said[k])
+    cuts = [k for k in W.DAMAGED_DYNAMIC if k.startswith("truncated_dyn_repeats_")]
+    assert sorted(cuts + sum(rules.values(), [])) == W.DAMAGED_DYNAMIC and 40 <= len(cuts) <= 80
+    assert all("incomplete or truncated" in said[k] for k in cuts)
 
 
 @pytest.mark.parametrize("name", sorted(W.refused_cases()))
