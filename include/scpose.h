@@ -523,6 +523,29 @@ int32_t scpose_events_aedat4_unpack(const uint8_t* src, int64_t n_packets, int32
                                     int32_t* y, int8_t* p, int64_t capacity, int64_t* count_status, void* workspace,
                                     size_t workspace_bytes, void* stream);
 
+/* (ABI 7, additive) ZSTD / ZSTD_HIGH payloads (csrc/events_aedat4_zstd.hip, which states the format: RFC 8878, no dictionary): the
+ * Zstandard counterpart of _measure and _decode, with their argument lists, their total_status, their per-packet slots and their
+ * limit of 2^23 - 16 decoded bytes per packet, so _count (staged != 0) and _unpack follow unchanged on the SAME workspace.
+ *   workspace  scpose_events_aedat4_zstd_workspace_bytes(n_packets): the workspace of the four calls above, its slots in
+ *              their places, then one 128 KiB slot per workgroup for a block's regenerated literals.
+ *   _zstd_measure  walks frames and blocks without storing: Frame_Content_Size where a frame states it, else Raw and RLE sizes from
+ *              the block headers and Compressed ones from the literals header plus the sum of the match lengths.
+ *   _zstd_decode   decodes every payload into its piece of `staging`; verify != 0 checks the content checksum (the low 32 bits of
+ *              XXH64) of the frames that carry one.
+ *   status     SCPOSE_AEDAT4_CORRUPT: a magic that is neither a Zstandard nor a skippable frame's, no Zstandard frame at all, the
+ *              reserved bit, a dictionary ID, block type 3, a size above min(window, 128 KiB), a block, table or bitstream that
+ *              overruns its input or does not end where it must, an accuracy above its limit, probabilities or Huffman weights
+ *              that do not add up to a power of two, Treeless or Repeat with nothing before it, an offset of 0, beyond the window
+ *              or before the frame's output, literals that run out, a size that differs from Frame_Content_Size or from
+ *              _zstd_measure.  SCPOSE_AEDAT4_CHECKSUM: a content checksum differs.
+ * Argument errors as above, under the names events_aedat4_zstd_*.  No allocation, no synchronisation, integer work only; two
+ * runs on the same bytes give bitwise equal outputs. */
+int32_t scpose_events_aedat4_zstd_workspace_bytes(int64_t n_packets, size_t* bytes);
+int32_t scpose_events_aedat4_zstd_measure(const uint8_t* file, const int64_t* packets, int64_t n_packets, int64_t* total_status,
+                                          void* workspace, size_t workspace_bytes, void* stream);
+int32_t scpose_events_aedat4_zstd_decode(const uint8_t* file, const int64_t* packets, int64_t n_packets, uint8_t* staging,
+                                         int64_t staging_bytes, int32_t verify, void* workspace, size_t workspace_bytes, void* stream);
+
 /* (ABI 7, additive) The event packets of an AEDAT-4.0 recording, written on the device (csrc/events_aedat4_write.hip, which states
  * what is written): the four columns and the packets' row boundaries -> the byte string `int32 streamID, int32 size, payload` of
  * every packet, one after the other, as it stands in the file between the IOHeader and the file data table.  The host writes the

@@ -170,6 +170,10 @@ SYMBOLS = {
     "scpose_events_aedat4_count": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
     "scpose_events_aedat4_unpack": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                               c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "scpose_events_aedat4_zstd_workspace_bytes": (c_int32, [c_int64, POINTER(c_size_t)]),
+    "scpose_events_aedat4_zstd_measure": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "scpose_events_aedat4_zstd_decode": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_size_t,
+                                                   c_void_p]),
     "scpose_events_aedat4_pack_sizes": (c_int32, [c_int64, c_int64, c_int32, POINTER(c_size_t), POINTER(c_size_t)]),
     "scpose_events_aedat4_pack": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32,
                                             c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

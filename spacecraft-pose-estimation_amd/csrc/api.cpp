@@ -304,11 +304,13 @@ extern "C" int32_t scpose_events_aedat3_unpack(const uint8_t* file, const int64_
                                      static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
 }
 
-// n_packets in range, the workspace, then the pointers: `a` and `b` are needed when there are packets, `result` always
+// n_packets in range, the workspace, then the pointers: `a` and `b` are needed when there are packets, `result` always.
+// zstd: the call belongs to the ZSTD pair, whose workspace is the larger one.
 static int32_t aedat4_args_ok(const char* who, int64_t n_packets, const void* a, const void* b, const void* result,
-                              const void* workspace, size_t workspace_bytes) {
+                              const void* workspace, size_t workspace_bytes, bool zstd = false) {
   SCP_REQUIRE(n_packets >= 0 && n_packets <= 0x7fffffff, "%s: n_packets=%lld (0 .. 2^31 - 1)", who, (long long)n_packets);
-  if (int32_t rc = workspace_ok(who, workspace, workspace_bytes, events_aedat4_workspace_bytes(n_packets), 16)) return rc;
+  const size_t need = zstd ? events_aedat4_zstd_workspace_bytes(n_packets) : events_aedat4_workspace_bytes(n_packets);
+  if (int32_t rc = workspace_ok(who, workspace, workspace_bytes, need, 16)) return rc;
   SCP_REQUIRE(result && (n_packets == 0 || (a && b)), "%s: null argument", who);
   return SCPOSE_OK;
 }
@@ -360,6 +362,35 @@ extern "C" int32_t scpose_events_aedat4_unpack(const uint8_t* src, int64_t n_pac
     return rc;
   return events_aedat4_unpack_launch(src, n_packets, h, w, rebase != 0, t, x, y, p, capacity, count_status,
                                      static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+// the ZSTD pair: the same checks on the larger workspace
+extern "C" int32_t scpose_events_aedat4_zstd_workspace_bytes(int64_t n_packets, size_t* bytes) {
+  SCP_REQUIRE(bytes, "events_aedat4_zstd_workspace_bytes: null argument");
+  SCP_REQUIRE(n_packets >= 0 && n_packets <= 0x7fffffff, "events_aedat4_zstd_workspace_bytes: n_packets=%lld (0 .. 2^31 - 1)",
+              (long long)n_packets);
+  *bytes = events_aedat4_zstd_workspace_bytes(n_packets);
+  return SCPOSE_OK;
+}
+
+extern "C" int32_t scpose_events_aedat4_zstd_measure(const uint8_t* file, const int64_t* packets, int64_t n_packets,
+                                                     int64_t* total_status, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int32_t rc = aedat4_args_ok("events_aedat4_zstd_measure", n_packets, file, packets, total_status, workspace, workspace_bytes, true))
+    return rc;
+  return events_aedat4_zstd_measure_launch(file, packets, n_packets, total_status, static_cast<uint8_t*>(workspace),
+                                           static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t scpose_events_aedat4_zstd_decode(const uint8_t* file, const int64_t* packets, int64_t n_packets, uint8_t* staging,
+                                                    int64_t staging_bytes, int32_t verify, void* workspace, size_t workspace_bytes,
+                                                    void* stream) {
+  if (int32_t rc = aedat4_args_ok("events_aedat4_zstd_decode", n_packets, file, packets, workspace, workspace, workspace_bytes, true))
+    return rc;
+  SCP_REQUIRE(staging_bytes >= 0 && (staging || staging_bytes == 0), "events_aedat4_zstd_decode: staging of %lld bytes%s",
+              (long long)staging_bytes, staging ? "" : " is null");
+  SCP_REQUIRE(aligned(staging, 16), "events_aedat4_zstd_decode: staging must be 16-byte aligned");
+  return events_aedat4_zstd_decode_launch(file, packets, n_packets, staging, staging_bytes, verify != 0,
+                                          static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
 }
 
 static const int64_t kMaxWritePackets = (int64_t)1 << 24;     // one wavefront per packet and per block in one grid

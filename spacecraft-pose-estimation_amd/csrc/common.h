@@ -382,6 +382,20 @@ int32_t events_aedat4_count_launch(const uint8_t* src, const int64_t* packets, i
                                    hipStream_t stream);
 int32_t events_aedat4_unpack_launch(const uint8_t* src, int64_t n, int h, int w, int rebase, int64_t* t, int32_t* x, int32_t* y,
                                     int8_t* p, int64_t capacity, int64_t* count_status, uint8_t* ws, hipStream_t stream);
+// events_aedat4_zstd.hip: the measure / decode pair for ZSTD payloads, on a workspace that starts with the reader's.  It fills
+// the reader's per-packet slots (events_aedat4_slots) and closes its measure step with the reader's sizes step.
+struct Aedat4Slots {
+  int32_t* size;
+  int64_t* off;
+  int32_t* status;
+};
+Aedat4Slots events_aedat4_slots(int64_t n_packets, uint8_t* ws);
+int32_t events_aedat4_sizes_launch(int64_t n, int64_t* total_status, uint8_t* ws, hipStream_t stream);
+size_t events_aedat4_zstd_workspace_bytes(int64_t n_packets);
+int32_t events_aedat4_zstd_measure_launch(const uint8_t* file, const int64_t* packets, int64_t n, int64_t* total_status, uint8_t* ws,
+                                          hipStream_t stream);
+int32_t events_aedat4_zstd_decode_launch(const uint8_t* file, const int64_t* packets, int64_t n, uint8_t* staging,
+                                         int64_t staging_bytes, int verify, uint8_t* ws, hipStream_t stream);
 // the limits of one packet that the reader holds its input to and the writer its output (events_aedat4_read.hip says why)
 constexpr int kAedat4MaxDecoded = (1 << 23) - 16;
 constexpr int kAedat4MaxCount = (1 << 23) - 1;

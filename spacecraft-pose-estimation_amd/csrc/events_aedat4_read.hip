@@ -349,15 +349,26 @@ inline unsigned blocks_of(int64_t n) { return (unsigned)((n + kThreads - 1) / kT
 
 size_t events_aedat4_workspace_bytes(int64_t n_packets) { return plan(n_packets, nullptr).bytes; }
 
+// what a measure / decode pair of another compression (events_aedat4_zstd.hip) shares with this one
+Aedat4Slots events_aedat4_slots(int64_t n, uint8_t* wsp) {
+  const Plan pl = plan(n, wsp);
+  return {pl.size, pl.off, pl.status};
+}
+
+int32_t events_aedat4_sizes_launch(int64_t n, int64_t* total_status, uint8_t* wsp, hipStream_t stream) {
+  const Plan pl = plan(n, wsp);
+  hipLaunchKernelGGL(aedat4_sizes_kernel, dim3(1), dim3(kThreads), 0, stream, pl.size, pl.padded, pl.status, n, pl.off, total_status);
+  SCP_CHECK_HIP(hipGetLastError());
+  return SCPOSE_OK;
+}
+
 int32_t events_aedat4_measure_launch(const uint8_t* file, const int64_t* packets, int64_t n, int64_t* total_status, uint8_t* wsp,
                                      hipStream_t stream) {
   const Plan pl = plan(n, wsp);
   if (n > 0)
     hipLaunchKernelGGL(aedat4_lz4_kernel<false>, dim3((unsigned)n), dim3(kWave), 0, stream, file, packets, pl.size, pl.off,
                        (uint8_t*)nullptr, (int64_t)0, 0, pl.status);
-  hipLaunchKernelGGL(aedat4_sizes_kernel, dim3(1), dim3(kThreads), 0, stream, pl.size, pl.padded, pl.status, n, pl.off, total_status);
-  SCP_CHECK_HIP(hipGetLastError());
-  return SCPOSE_OK;
+  return events_aedat4_sizes_launch(n, total_status, wsp, stream);
 }
 
 int32_t events_aedat4_decode_launch(const uint8_t* file, const int64_t* packets, int64_t n, uint8_t* staging, int64_t staging_bytes,

@@ -9,9 +9,10 @@ the AEDAT-2.0 entry points: callers sniff the first 14 bytes (is_aedat4_path) an
 
 An AEDAT-4.0 file (a DVXplorer / DV recording) is `#!AER-DAT4.0\r\n`, a length-prefixed IOHeader flatbuffer (compression, the
 position of the file data table, an XML node that names the streams), then packets: int32 stream id, int32 size, the payload, a
-flatbuffer that is raw or one LZ4 frame.  parse_aedat4 reads the header and walks the packet headers on the host (eight bytes
+flatbuffer that is raw, one LZ4 frame or Zstandard frames.  parse_aedat4 reads the header and walks the packet headers on the host (eight bytes
 per packet); read_events_aedat4 uploads the file in one piece and the payloads of the event streams are decompressed and
-unpacked on the device (csrc/events_aedat4_read.hip, which states the format, through ops.unpack_events_aedat4).
+unpacked on the device (csrc/events_aedat4_read.hip and, for ZSTD, csrc/events_aedat4_zstd.hip, which state the formats, through
+ops.unpack_events_aedat4).
 
 An AEDAT-3.1 file (a cAER / early DV recording of a DAVIS or DVS128 camera) is a '#' text header with '\\r\\n' line ends that
 starts with `#!AER-DAT3.1` and ends with `#!END-HEADER`, then packets: a 28-byte header and eventCapacity * eventSize payload bytes.
@@ -149,7 +150,8 @@ AEDAT4_COMPRESSION = {0: "NONE", 1: "LZ4", 2: "LZ4_HIGH", 3: "ZSTD", 4: "ZSTD_HI
 
 
 class UnsupportedAedat4(ValueError):
-    """An AEDAT-4.0 file this reader does not take: ZSTD packets, an unknown compression, no IOHeader, no event stream."""
+    """An AEDAT-4.0 file this reader does not take: ZSTD packets where no ZSTD decoder is on offer, an unknown compression, no
+    IOHeader, no event stream."""
 
 
 class Aedat4Header:
@@ -216,11 +218,12 @@ def _aedat4_streams(xml):
     return streams
 
 
-def parse_aedat4(data):
+def parse_aedat4(data, zstd=False):
     """The header and packet table of an AEDAT-4.0 file (its bytes) -> Aedat4Header.  Packets run to dataTablePosition when that is
     >= 0, else to the end; a last packet whose header or payload is cut off is dropped and reported as trailing_bytes, as the
-    AEDAT-2.0 reader reports a partial record.  Raises UnsupportedAedat4 for ZSTD / ZSTD_HIGH (there is no host fallback: no zstd
-    module is at hand), an unknown compression value, a missing IOHE identifier and a file without an event stream."""
+    AEDAT-2.0 reader reports a partial record.  zstd: whether the caller has a ZSTD decoder on offer (read_events_aedat4 has the
+    device's); without one, raises UnsupportedAedat4 for ZSTD / ZSTD_HIGH (there is no host fallback: no zstd module is at hand).
+    Raises it too for an unknown compression value, a missing IOHE identifier and a file without an event stream."""
     buf = data if isinstance(data, (bytes, bytearray, memoryview)) else bytes(data)       # a memoryview is walked, not copied
     if buf[:len(AEDAT4_MAGIC)] != AEDAT4_MAGIC:
         raise UnsupportedAedat4("not an AEDAT-4.0 file: the first 14 bytes are %r" % bytes(buf[:14]))
@@ -242,7 +245,7 @@ def parse_aedat4(data):
         spos = f + struct.unpack_from("<I", head, f)[0]
         if spos + 4 <= n:
             xml = head[spos + 4:spos + 4 + struct.unpack_from("<I", head, spos)[0]]
-    if compression in (3, 4):
+    if compression in (3, 4) and not zstd:
         raise UnsupportedAedat4("the packets are %s compressed: only NONE, LZ4 and LZ4_HIGH are read, and there is no host "
                                 "fallback (no zstd module)" % AEDAT4_COMPRESSION[compression])
     if compression not in AEDAT4_COMPRESSION:
@@ -273,12 +276,12 @@ def read_events_aedat4(path_or_bytes, hw=None, stream=None, rebase=True, verify=
     """An AEDAT-4.0 file (a path, or its bytes) -> (t int64, x int32, y int32, p int8, info) on `device` (default: the current
     one), the events of the file's EVTS streams in file order -- what the reference's aedat_to_csv.py loop collects.  hw defaults
     to the stream's (sizeY, sizeX); stream: one stream id, default every EVTS stream; rebase: subtract the first event's time
-    stamp, as the reference does; verify: check the LZ4 block and content checksums the file carries.  The file is uploaded
+    stamp, as the reference does; verify: check the LZ4 block and content checksums or ZSTD content checksums the file carries.  The file is uploaded
     once, as ops.parse_events_csv uploads its text.  info: n_events, n_packets, t0, n_backward, n_out_of_range, compression, hw,
     streams, trailing_bytes.  Raises UnsupportedAedat4 (parse_aedat4) and ValueError (ops.unpack_events_aedat4)."""
     from . import ops
     host = _load(path_or_bytes)
-    head = parse_aedat4(memoryview(host))
+    head = parse_aedat4(memoryview(host), zstd=True)
     if stream is None:
         ids = head.event_streams()
     else:

@@ -654,6 +654,11 @@ _AEDAT4_STATUS = (
     (nat.AEDAT4_CHECKSUM, ValueError, "%(who)s: an LZ4 block or content checksum differs (status CHECKSUM)"),
     (nat.AEDAT4_FLATBUFFER, ValueError, "%(who)s: an event packet's flatbuffer is damaged (status FLATBUFFER)"),
     (nat.AEDAT4_RANGE, ValueError, "%(who)s: an event lies outside the %(w)d x %(h)d sensor (status RANGE)"))
+_AEDAT4_ZSTD_STATUS = (
+    (nat.AEDAT4_CORRUPT, ValueError, "%(who)s: a packet is not a valid Zstandard frame (status CORRUPT: a bad magic, a reserved bit, "
+                                     "a dictionary, a damaged table or bitstream, an offset of 0, beyond the window or before the "
+                                     "output's start, an input overrun, a size that differs)"),
+    (nat.AEDAT4_CHECKSUM, ValueError, "%(who)s: a Zstandard content checksum differs (status CHECKSUM)")) + _AEDAT4_STATUS[2:]
 _AEDAT4_WRITE_STATUS = (
     (nat.AEDAT4_WRITE_RANGE, ValueError, "%(who)s: an event lies outside the %(w)d x %(h)d sensor, or a polarity is neither 0 nor 1"),
     (nat.AEDAT4_WRITE_SIZE, ValueError, "%(who)s: a packet is larger than the reader takes (2^23 - 16 bytes: 524284 events)"))
@@ -663,37 +668,40 @@ def unpack_events_aedat4(buf, packets, compression, hw, rebase=True, verify=True
     """The event packets of an AEDAT-4.0 file -> (t int64, x int32, y int32, p int8, info), events in file order, decompressed
     and unpacked on the device (csrc/events_aedat4_read.hip), in the dtypes render_events takes.  buf: a uint8 device tensor, the
     whole file.  packets: (n, 2) int64, payload offset and size of each EVENT packet (event_read.parse_aedat4 finds them).
-    compression: the IOHeader's value, 0 NONE or 1 / 2 LZ4.  hw = (height, width) of the sensor.  rebase: t minus the first
-    event's t.  verify: check the checksums the LZ4 frames carry.  Two small read-backs size the staging buffer and the columns,
+    compression: the IOHeader's value, 0 NONE, 1 / 2 LZ4 or 3 / 4 ZSTD (csrc/events_aedat4_zstd.hip).  hw = (height, width) of the
+    sensor.  rebase: t minus the first event's t.  verify: check the checksums the frames carry.  Two small read-backs size the staging buffer and the columns,
     a third brings the counters.  info: n_events, n_packets, t0, n_backward, n_out_of_range.  Raises ValueError for a damaged
     frame, a checksum that differs, a damaged flatbuffer and an event outside the sensor."""
     who = "unpack_events_aedat4"
     buf, pk, n = _packet_descriptors(who, buf, packets, 2)
-    if compression not in (0, 1, 2):
-        raise ValueError("unpack_events_aedat4: compression %r (0 NONE, 1 LZ4, 2 LZ4_HIGH)" % (compression,))
+    if compression not in (0, 1, 2, 3, 4):
+        raise ValueError("unpack_events_aedat4: compression %r (0 NONE, 1 LZ4, 2 LZ4_HIGH, 3 ZSTD, 4 ZSTD_HIGH)" % (compression,))
+    zstd = compression in (3, 4)
+    stem = "events_aedat4_zstd_" if zstd else "events_aedat4_"              # the measure / decode pair and its workspace
+    table = _AEDAT4_ZSTD_STATUS if zstd else _AEDAT4_STATUS
     if n and (pk.min() < 0 or int((pk[:, 0] + pk[:, 1]).max()) > buf.numel()):
         raise ValueError(_NOT_INSIDE % (who, buf.numel()))
     h, w = int(hw[0]), int(hw[1])
     lib = nat.lib()
-    ws = _query_bytes("events_aedat4_workspace_bytes", n)
+    ws = _query_bytes(stem + "workspace_bytes", n)
     with torch.cuda.device(buf.device):
         work = torch.empty(ws, dtype=torch.uint8, device=buf.device)
         cs = torch.empty(6, dtype=torch.int64, device=buf.device)
         pkd = torch.from_numpy(pk).to(buf.device)
         src = buf
         if compression:
-            nat.check(lib.scpose_events_aedat4_measure(_ptr(buf), _ptr(pkd), n, _ptr(cs), _ptr(work), ws, _stream()),
-                      "events_aedat4_measure")
+            nat.check(getattr(lib, "scpose_" + stem + "measure")(_ptr(buf), _ptr(pkd), n, _ptr(cs), _ptr(work), ws, _stream()),
+                      stem + "measure")
             total, status = cs.tolist()[:2]                         # small read-back: the staging buffer's size
-            _raise_status(who, status, hw, _AEDAT4_STATUS)
+            _raise_status(who, status, hw, table)
             if total < 0 or total % 16 or total > n * (1 << 23):
-                raise nat.NativeError("unpack_events_aedat4: events_aedat4_measure reports %d staging bytes for %d packets" % (total, n))
+                raise nat.NativeError("unpack_events_aedat4: %smeasure reports %d staging bytes for %d packets" % (stem, total, n))
             src = torch.empty(max(int(total), 16), dtype=torch.uint8, device=buf.device)
-            nat.check(lib.scpose_events_aedat4_decode(_ptr(buf), _ptr(pkd), n, _ptr(src), int(total), int(bool(verify)), _ptr(work), ws,
-                                                      _stream()),
-                      "events_aedat4_decode")
+            nat.check(getattr(lib, "scpose_" + stem + "decode")(_ptr(buf), _ptr(pkd), n, _ptr(src), int(total), int(bool(verify)),
+                                                                _ptr(work), ws, _stream()),
+                      stem + "decode")
         return _count_then_unpack(
-            who, hw, _AEDAT4_STATUS, n, cs,
+            who, hw, table, n, cs,
             lambda: nat.check(lib.scpose_events_aedat4_count(_ptr(src), _ptr(pkd), n, int(bool(compression)), _ptr(cs), _ptr(work), ws,
                                                              _stream()), "events_aedat4_count"),
             lambda t, x, y, p, rows: nat.check(

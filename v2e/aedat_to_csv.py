@@ -7,7 +7,7 @@ Same name and arguments as the reference script, and the same bytes: one `t,x,y,
 file order, no header line, t in microseconds counted from the first event -- what the reference's pandas
 `to_csv(index=False, header=False)` writes.  Nothing loops over events on the host: the file is uploaded once, its LZ4 packets
 are decompressed and unpacked on the device (event_read.read_events_aedat4, csrc/events_aedat4_read.hip) and the text is
-formatted there too (ops.format_events_text).  ZSTD recordings are refused by name.
+formatted there too (ops.format_events_text).  ZSTD recordings are decoded on the device too (csrc/events_aedat4_zstd.hip).
 
 An --events_file that ends in .aedat3 (or starts with '#!AER-DAT3.', whatever its name) is an AEDAT-3.1 recording of a DAVIS or
 DVS128 camera: the valid events of its polarity packets are unpacked on the device (event_read.read_events_aedat3,
