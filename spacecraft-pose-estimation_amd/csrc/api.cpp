@@ -315,31 +315,59 @@ static int32_t aedat4_args_ok(const char* who, int64_t n_packets, const void* a,
   return SCPOSE_OK;
 }
 
-extern "C" int32_t scpose_events_aedat4_workspace_bytes(int64_t n_packets, size_t* bytes) {
-  SCP_REQUIRE(bytes, "events_aedat4_workspace_bytes: null argument");
-  SCP_REQUIRE(n_packets >= 0 && n_packets <= 0x7fffffff, "events_aedat4_workspace_bytes: n_packets=%lld (0 .. 2^31 - 1)",
-              (long long)n_packets);
-  *bytes = events_aedat4_workspace_bytes(n_packets);
+// The workspace query, MEASURE and DECODE exist once per payload codec (LZ4, ZSTD): one body each, and `who` and `zstd` say which
+// entry point runs it.  DECODE's kernels store nothing past a packet's measured size and nothing outside staging_bytes.
+static int32_t aedat4_workspace_query(const char* who, int64_t n_packets, size_t* bytes, bool zstd) {
+  SCP_REQUIRE(bytes, "%s: null argument", who);
+  SCP_REQUIRE(n_packets >= 0 && n_packets <= 0x7fffffff, "%s: n_packets=%lld (0 .. 2^31 - 1)", who, (long long)n_packets);
+  *bytes = zstd ? events_aedat4_zstd_workspace_bytes(n_packets) : events_aedat4_workspace_bytes(n_packets);
   return SCPOSE_OK;
+}
+
+static int32_t aedat4_measure(const char* who, bool zstd, const uint8_t* file, const int64_t* packets, int64_t n_packets,
+                              int64_t* total_status, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int32_t rc = aedat4_args_ok(who, n_packets, file, packets, total_status, workspace, workspace_bytes, zstd)) return rc;
+  return (zstd ? events_aedat4_zstd_measure_launch : events_aedat4_measure_launch)(
+      file, packets, n_packets, total_status, static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+static int32_t aedat4_decode(const char* who, bool zstd, const uint8_t* file, const int64_t* packets, int64_t n_packets,
+                             uint8_t* staging, int64_t staging_bytes, int32_t verify, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int32_t rc = aedat4_args_ok(who, n_packets, file, packets, workspace, workspace, workspace_bytes, zstd)) return rc;
+  SCP_REQUIRE(staging_bytes >= 0 && (staging || staging_bytes == 0), "%s: staging of %lld bytes%s", who, (long long)staging_bytes,
+              staging ? "" : " is null");
+  SCP_REQUIRE(aligned(staging, 16), "%s: staging must be 16-byte aligned", who);
+  return (zstd ? events_aedat4_zstd_decode_launch : events_aedat4_decode_launch)(
+      file, packets, n_packets, staging, staging_bytes, verify != 0, static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t scpose_events_aedat4_workspace_bytes(int64_t n_packets, size_t* bytes) {
+  return aedat4_workspace_query("events_aedat4_workspace_bytes", n_packets, bytes, false);
+}
+extern "C" int32_t scpose_events_aedat4_zstd_workspace_bytes(int64_t n_packets, size_t* bytes) {
+  return aedat4_workspace_query("events_aedat4_zstd_workspace_bytes", n_packets, bytes, true);
 }
 
 extern "C" int32_t scpose_events_aedat4_measure(const uint8_t* file, const int64_t* packets, int64_t n_packets, int64_t* total_status,
                                                 void* workspace, size_t workspace_bytes, void* stream) {
-  if (int32_t rc = aedat4_args_ok("events_aedat4_measure", n_packets, file, packets, total_status, workspace, workspace_bytes)) return rc;
-  return events_aedat4_measure_launch(file, packets, n_packets, total_status, static_cast<uint8_t*>(workspace),
-                                      static_cast<hipStream_t>(stream));
+  return aedat4_measure("events_aedat4_measure", false, file, packets, n_packets, total_status, workspace, workspace_bytes, stream);
+}
+extern "C" int32_t scpose_events_aedat4_zstd_measure(const uint8_t* file, const int64_t* packets, int64_t n_packets,
+                                                     int64_t* total_status, void* workspace, size_t workspace_bytes, void* stream) {
+  return aedat4_measure("events_aedat4_zstd_measure", true, file, packets, n_packets, total_status, workspace, workspace_bytes, stream);
 }
 
 extern "C" int32_t scpose_events_aedat4_decode(const uint8_t* file, const int64_t* packets, int64_t n_packets, uint8_t* staging,
                                                int64_t staging_bytes, int32_t verify, void* workspace, size_t workspace_bytes,
                                                void* stream) {
-  // the kernel stores nothing past a packet's measured size and nothing outside staging_bytes
-  if (int32_t rc = aedat4_args_ok("events_aedat4_decode", n_packets, file, packets, workspace, workspace, workspace_bytes)) return rc;
-  SCP_REQUIRE(staging_bytes >= 0 && (staging || staging_bytes == 0), "events_aedat4_decode: staging of %lld bytes%s",
-              (long long)staging_bytes, staging ? "" : " is null");
-  SCP_REQUIRE(aligned(staging, 16), "events_aedat4_decode: staging must be 16-byte aligned");
-  return events_aedat4_decode_launch(file, packets, n_packets, staging, staging_bytes, verify != 0, static_cast<uint8_t*>(workspace),
-                                     static_cast<hipStream_t>(stream));
+  return aedat4_decode("events_aedat4_decode", false, file, packets, n_packets, staging, staging_bytes, verify, workspace,
+                       workspace_bytes, stream);
+}
+extern "C" int32_t scpose_events_aedat4_zstd_decode(const uint8_t* file, const int64_t* packets, int64_t n_packets, uint8_t* staging,
+                                                    int64_t staging_bytes, int32_t verify, void* workspace, size_t workspace_bytes,
+                                                    void* stream) {
+  return aedat4_decode("events_aedat4_zstd_decode", true, file, packets, n_packets, staging, staging_bytes, verify, workspace,
+                       workspace_bytes, stream);
 }
 
 extern "C" int32_t scpose_events_aedat4_count(const uint8_t* src, const int64_t* packets, int64_t n_packets, int32_t staged,
@@ -362,35 +390,6 @@ extern "C" int32_t scpose_events_aedat4_unpack(const uint8_t* src, int64_t n_pac
     return rc;
   return events_aedat4_unpack_launch(src, n_packets, h, w, rebase != 0, t, x, y, p, capacity, count_status,
                                      static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
-}
-
-// the ZSTD pair: the same checks on the larger workspace
-extern "C" int32_t scpose_events_aedat4_zstd_workspace_bytes(int64_t n_packets, size_t* bytes) {
-  SCP_REQUIRE(bytes, "events_aedat4_zstd_workspace_bytes: null argument");
-  SCP_REQUIRE(n_packets >= 0 && n_packets <= 0x7fffffff, "events_aedat4_zstd_workspace_bytes: n_packets=%lld (0 .. 2^31 - 1)",
-              (long long)n_packets);
-  *bytes = events_aedat4_zstd_workspace_bytes(n_packets);
-  return SCPOSE_OK;
-}
-
-extern "C" int32_t scpose_events_aedat4_zstd_measure(const uint8_t* file, const int64_t* packets, int64_t n_packets,
-                                                     int64_t* total_status, void* workspace, size_t workspace_bytes, void* stream) {
-  if (int32_t rc = aedat4_args_ok("events_aedat4_zstd_measure", n_packets, file, packets, total_status, workspace, workspace_bytes, true))
-    return rc;
-  return events_aedat4_zstd_measure_launch(file, packets, n_packets, total_status, static_cast<uint8_t*>(workspace),
-                                           static_cast<hipStream_t>(stream));
-}
-
-extern "C" int32_t scpose_events_aedat4_zstd_decode(const uint8_t* file, const int64_t* packets, int64_t n_packets, uint8_t* staging,
-                                                    int64_t staging_bytes, int32_t verify, void* workspace, size_t workspace_bytes,
-                                                    void* stream) {
-  if (int32_t rc = aedat4_args_ok("events_aedat4_zstd_decode", n_packets, file, packets, workspace, workspace, workspace_bytes, true))
-    return rc;
-  SCP_REQUIRE(staging_bytes >= 0 && (staging || staging_bytes == 0), "events_aedat4_zstd_decode: staging of %lld bytes%s",
-              (long long)staging_bytes, staging ? "" : " is null");
-  SCP_REQUIRE(aligned(staging, 16), "events_aedat4_zstd_decode: staging must be 16-byte aligned");
-  return events_aedat4_zstd_decode_launch(file, packets, n_packets, staging, staging_bytes, verify != 0,
-                                          static_cast<uint8_t*>(workspace), static_cast<hipStream_t>(stream));
 }
 
 static const int64_t kMaxWritePackets = (int64_t)1 << 24;     // one wavefront per packet and per block in one grid

@@ -30,7 +30,7 @@
 //   aedat4_lz4_kernel<true>   DECODE, one wavefront per packet: the same wave-uniform walk; literals and matches are copied by all
 //                             lanes, an overlapping match reads source byte start + (i mod offset).  The output goes straight to
 //                             the packet's piece of the staging buffer in global memory and a match reads it back from there:
-//                             before a match's loads the wave waits for its own stores (own_stores_done below).  Block and content
+//                             before a match's loads the wave waits for its own stores (own_stores_done of aedat4_payload.h).  Block and content
 //                             checksums are verified when asked.  Under NONE none of these three run: the staging buffer is the file.
 //   aedat4_count_kernel       one thread per packet: the flatbuffer walk down to the vector's count.
 //   aedat4_counts_kernel      one workgroup, packet_counts of events_packets.h: event offsets, n_events, status, the first time stamp.
@@ -39,8 +39,9 @@
 // the ones the AEDAT-3.1 reader uses too: events_packets.h states them once.
 // The kernels DETECT a damaged stream and never interpret one: every read is checked against the payload, every match against the
 // output produced so far, every store against the measured size.  Integer work on fixed positions: two runs are bitwise equal.
+#include "aedat4_payload.h"
 #include "events_packets.h"
-#include "xxh32_wave.h"
+#include "xxh_wave.h"
 
 namespace scpose {
 
@@ -81,15 +82,6 @@ struct In {
     return byte(pos) | (byte(pos + 1) << 8) | (byte(pos + 2) << 16) | (byte(pos + 3) << 24);
   }
 };
-
-// A match reads what this wave stored earlier, through other lanes: the loads must not overtake the stores.  One wavefront's
-// vector memory operations reach the cache in the order they are issued; the wait below makes the stores complete first all the
-// same, and the fence keeps the compiler from moving the loads above them.
-__device__ __forceinline__ void own_stores_done() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 
 // a length nibble of 15 extended by bytes; -> false: the block ends inside the extension
 __device__ __forceinline__ bool extend(In& in, long long& ip, long long iend, long long& len) {

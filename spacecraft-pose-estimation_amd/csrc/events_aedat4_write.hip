@@ -36,12 +36,12 @@
 //                          positions by two scans (the sizes split at 2^16, so that 256 of them sum within an int32).
 //   aedat4w_emit_kernel    one wavefront per block: the size word and the compressed bytes (or the source bytes, when stored) to
 //                          their place in the contiguous output; one wavefront per packet: record header, frame header with HC,
-//                          end mark and the content checksum (xxh32_wave.h).
+//                          end mark and the content checksum (xxh_wave.h).
 // The same last four stages frame arbitrary bytes (events_aedat4_frame_launch): `bounds` then cuts a byte string into packets.
 // Integer work on fixed positions only: two runs on the same columns are bitwise equal.
 #include "common.h"
 #include "scan_device.h"
-#include "xxh32_wave.h"
+#include "xxh_wave.h"
 
 namespace scpose {
 

@@ -56,13 +56,15 @@
 //                              the workspace (128 KiB: a block's literals do not fit in LDS beside the tables).  Every lane decodes
 //                              every sequence, redundantly and in step (the same bits, the same branch: no lane waits for
 //                              another's result), and every copy is executed by all 64 lanes.  Match history is the staging
-//                              buffer itself: before a match's loads the wave waits for its own stores (own_stores_done).
+//                              buffer itself: before a match's loads the wave waits for its own stores (own_stores_done of aedat4_payload.h).
 //                              The content checksum is verified when asked; the decoded size must equal what MEASURE found and
 //                              the Frame_Content_Size.
 // A launch has at most kZstdGrid workgroups, each walking packets blockIdx.x, + gridDim.x, ...: the literal slots are per workgroup.
 // The kernels DETECT a damaged stream and never interpret one: every read is checked against the payload, every store against
 // the packet's slot.  Integer work on fixed positions: two runs are bitwise equal.
+#include "aedat4_payload.h"
 #include "events_packets.h"
+#include "xxh_wave.h"
 
 namespace scpose {
 
@@ -102,13 +104,6 @@ struct ZLds {
   uint8_t weight[256];
   int ret, log;                                      // what lane 0 hands to the wave
 };
-
-// see events_aedat4_read.hip: a match (and the checksum) reads what this wave stored earlier, through other lanes
-__device__ __forceinline__ void own_stores_done() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 
 __device__ __forceinline__ int highbit(uint32_t v) { return 31 - __clz((int)v); }
 
@@ -328,43 +323,6 @@ __device__ int huf_table(ZLds& s, const uint8_t* p, long long n) {
   }
   s.log = maxbits;
   return used;
-}
-
-// XXH64 (seed 0) of p[0, n), the same value in every lane; lanes 0..3 carry the four accumulators.  All lanes.
-__device__ unsigned long long xxh64_wave(const uint8_t* p, long long n) {
-  constexpr unsigned long long P1 = 11400714785074694791ull, P2 = 14029467366897019727ull, P3 = 1609587929392839161ull,
-                               P4 = 9650029242287828579ull, P5 = 2870177450012600261ull;
-  auto rotl = [](unsigned long long v, int r) { return (v << r) | (v >> (64 - r)); };
-  auto round = [&](unsigned long long acc, unsigned long long in) { return rotl(acc + in * P2, 31) * P1; };
-  unsigned long long h;
-  long long at = 0;
-  if (n >= 32) {
-    const int k = threadIdx.x & 3;
-    unsigned long long v = k == 0 ? P1 + P2 : k == 1 ? P2 : k == 2 ? 0 : 0 - P1;
-    const long long stripes = n / 32;
-    if (threadIdx.x < 4)
-      for (long long i = 0; i < stripes; ++i) v = round(v, (unsigned long long)ld64(p + 32 * i + 8 * k));
-    const unsigned long long v1 = __shfl(v, 0), v2 = __shfl(v, 1), v3 = __shfl(v, 2), v4 = __shfl(v, 3);
-    h = rotl(v1, 1) + rotl(v2, 7) + rotl(v3, 12) + rotl(v4, 18);
-    h = (h ^ round(0, v1)) * P1 + P4;
-    h = (h ^ round(0, v2)) * P1 + P4;
-    h = (h ^ round(0, v3)) * P1 + P4;
-    h = (h ^ round(0, v4)) * P1 + P4;
-    at = 32 * stripes;
-  } else h = P5;
-  h += (unsigned long long)n;
-  for (; at + 8 <= n; at += 8) h = rotl(h ^ round(0, (unsigned long long)ld64(p + at)), 27) * P1 + P4;
-  if (at + 4 <= n) {
-    h = rotl(h ^ ((unsigned long long)ld32(p + at) * P1), 23) * P2 + P3;
-    at += 4;
-  }
-  for (; at < n; ++at) h = rotl(h ^ (p[at] * P5), 11) * P1;
-  h ^= h >> 33;
-  h *= P2;
-  h ^= h >> 29;
-  h *= P3;
-  h ^= h >> 32;
-  return h;
 }
 
 // What a frame carries from block to block

@@ -254,6 +254,67 @@ def test_damaged_files_raise(er):
     check(er, good, "still fine")                                          # the device is in order after all of that
 
 
+# ------------------------------------------------------------------ the measure / decode pair alone, on the staging buffer
+def test_nothing_stored_past_the_measured_size(gpu_ops):
+    """LZ4 frames that decode to 0, 1, 15, 16 and 17 bytes (the head of an event payload, cut there: an empty slot, slots that
+    end 15, 1 and 15 bytes before a multiple of 16, and one that ends on it) and a two-block linked frame whose second block
+    matches into the first (436 bytes, 4 past a multiple of 16), in one launch on a staging buffer of 0xA5: every slot holds its
+    bytes at its 16-byte-rounded offset, and the pad behind it is untouched."""
+    from aedat4_payload_driver import decode_payloads, padded
+    payload = W.evts_payload(*zero_led(20, 5))
+    planned = [payload[:n] for n in (0, 1, 15, 16, 17)] + [payload]
+    frames = [W.lz4_frame(d, content_checksum=bool(k & 1)) for k, d in enumerate(planned[:-1])]
+    frames.append(W.lz4_frame(payload, block_bytes=256, plans={1: [(256, 10, 40)]}))
+    assert len(payload) == 436 and all(R.lz4_frame(f) == d for f, d in zip(frames, planned))
+    total, st_measure, st, staging = decode_payloads(frames, codec="lz4")
+    assert st_measure == 0 and total == sum(padded(len(d)) for d in planned) == 80 + 448
+    at = 0
+    for d in planned:
+        assert staging[at:at + len(d)].tobytes() == d, len(d)
+        assert (staging[at + len(d):at + padded(len(d))] == 0xA5).all(), len(d)
+        at += padded(len(d))
+    assert st & ~gpu_ops.nat.AEDAT4_FLATBUFFER == 0                       # the cut payloads are no event packets: only that bit may be set
+
+
+def test_damaged_packet_between_good_ones(gpu_ops):
+    """A frame whose first match has offset 0, between two good frames: CORRUPT, the packet gets no slot, the neighbours decode."""
+    from aedat4_payload_driver import decode_payloads, padded
+    nat = gpu_ops.nat
+    payload = W.evts_payload(*W.random_events(12, HW, 11))
+    good = W.lz4_frame(payload, content_checksum=True)
+    bad = W.lz4_frame(payload, overrides={0: W.lz4_sequence(payload[:4], 0, 4) + W.lz4_sequence(payload[8:])})
+    for verify in (True, False):
+        total, st_measure, st, staging = decode_payloads([good, bad, good], verify, codec="lz4")
+        assert (st_measure | st) & (nat.AEDAT4_CORRUPT | nat.AEDAT4_CHECKSUM) == nat.AEDAT4_CORRUPT
+        assert st_measure & nat.AEDAT4_CORRUPT and total == 2 * padded(len(payload))
+        for at in (0, padded(len(payload))):
+            assert staging[at:at + len(payload)].tobytes() == payload
+            assert (staging[at + len(payload):at + padded(len(payload))] == 0xA5).all()
+
+
+@pytest.mark.parametrize("codec", ["lz4", "zstd"])
+def test_staging_shorter_than_measured(gpu_ops, codec):
+    """DECODE told that the staging buffer ends 16 bytes before what MEASURE asked for (the tensor itself is whole): the last
+    packet's slot no longer lies inside, so it is refused as CORRUPT and nothing of it is stored; the two before it decode."""
+    from aedat4_payload_driver import decode_payloads, padded
+    nat = gpu_ops.nat
+    if codec == "lz4":
+        planned = [W.evts_payload(*W.random_events(n, HW, 12 + n)) for n in (3, 1, 2)]
+        frames = [W.lz4_frame(d) for d in planned]
+    else:
+        import zstd_cases as C
+        frames, planned = zip(*(C.valid()["sequences_fse"][:2] for _ in range(3)))
+    assert all(len(d) > 0 for d in planned)
+    total, st_measure, st, staging = decode_payloads(list(frames), codec=codec)
+    assert st_measure == 0 and st & nat.AEDAT4_CORRUPT == 0 and total == sum(padded(len(d)) for d in planned)
+    short = decode_payloads(list(frames), codec=codec, staging_bytes=total - 16)
+    assert short[:2] == (total, 0) and short[2] & nat.AEDAT4_CORRUPT and len(short[3]) == total
+    last = total - padded(len(planned[2]))
+    assert np.array_equal(short[3][:last], staging[:last])               # the first two slots, pads included, as in the whole buffer
+    assert short[3][:len(planned[0])].tobytes() == planned[0]
+    assert (short[3][last:] == 0xA5).all()
+
+
 def test_one_event_outside_the_sensor_is_tallied(er, gpu_ops):
     """A NONE recording whose only packet holds exactly one event, outside the sensor: one lane with anything to add, so the
     tally's own barrier is all that orders the zeroing of its LDS pair before the one atomic."""
